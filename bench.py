@@ -20,11 +20,11 @@ one-stream eager loop.
 
 The headline runs at `--precision exact`: every contraction in the f16x3 mode (fp16 split pairs, three MFMA products per
 accumulator, fp32-class), i.e. the reference's own fp32 arithmetic class; the narrower `fast` precision (north-star tolerance
-1e-3) is timed as `second_precision`.
+1e-3) is timed as `second_precision` under `--full`.
 
-Prints ONE JSON line on rank 0 (contract in the task brief) incl. `roofline` (dominant kernel = the f16x3 MFMA
-GEMM, measured with HIP events around every launch of an instrumented step) and `cpu_baseline` (the oracle = CPU
-port of the reference path, timed on the host cores on a bounded sample, rank 0, N=1 only).
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step, ...  A plain run only sets up, warms up, times
+`--steps` steps and (`--dump-outputs DIR`) writes the last timed step's label maps and low-res logits as float32 .npy.  `--full` adds
+the rest (benchlib/headline.py): timed outputs checked, second precision, PCIe-inclusive rates, `roofline`, `cpu_baseline`, ...
 """
 from __future__ import annotations
 
@@ -87,6 +87,8 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="torch intra-op threads of the CPU baseline (16 was the fastest of 8..128 on the 2x64-core GPU box)")
     ap.add_argument("--dry-launch", action="store_true", help="print the rank launcher's command line (JSON) for --gpus N and exit; no GPU is touched")
+    ap.add_argument("--full", action="store_true", help="c2 / c4: also every measurement and check beyond the headline figure (see benchlib/headline.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="c2 / c4 / c5: write what the last timed step computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
     args.inflight_given = any(a == "--inflight" or a.startswith("--inflight=") for a in sys.argv[1:])
     if args.precision is None:

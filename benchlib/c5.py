@@ -7,7 +7,7 @@ import time
 
 import torch
 
-from .common import PRECISION_DTYPE, PRECISION_TEXT
+from .common import PRECISION_DTYPE, PRECISION_TEXT, dump_outputs
 from .roofline import gemm_roofline
 
 
@@ -92,6 +92,8 @@ def bench_c5(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"embeddings": emb})           # the last timed step's image embeddings (this rank's batch)
     # ---- the pipeline's second half (datasets/index_dataset.py:158-167): per-category top-500 retrieval over the extracted embeddings.
     # Rank r holds the embeddings of images [r*B, (r+1)*B) of the last step; every rank takes the exact top-k of ITS shard, the [C, k]
     # candidates are all-gathered (the only collective of this config besides the embeddings gather) and merged identically everywhere.

@@ -3,6 +3,8 @@ from __future__ import annotations
 
 import os
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH_PY = os.path.join(ROOT, "bench.py")            # the script the driver (and the live counter passes) run
 
@@ -24,3 +26,21 @@ FLOPS_PER_IMAGE_C2 = 124.4e9 + 0.146e9  # forward + semantic p
 def rank_env():
     """(world, rank, local_rank) from the launcher's environment (torch.distributed.run); 1, 0, 0 for a plain run."""
     return int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
+
+
+DUMP_BUDGET_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: `arrays` (name -> tensor / ndarray, what the timed path returned in its last step) as DIR/<name>.npy in float32
+    (integer label ids up to 2^24 are exact).  An array too large for its share of DUMP_BUDGET_BYTES is written as a fixed, seeded sample
+    of its flattened elements (DIR/<name>_sample.npy, same indices every run for the same shape), so two builds compare element for element."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(dirname, name + ".npy"), a)

@@ -1,5 +1,10 @@
 """The headline line: BASELINE config 2 (and `--workload c4`, the same path at 518 px / 920 classes) — ViT-B/16 ZUTIS forward + semantic
-predict, batches sharded by rank, `--inflight` launch plans in flight, one all-gather of the low-res logits per step at N > 1."""
+predict, batches sharded by rank, `--inflight` launch plans in flight, one all-gather of the low-res logits per step at N > 1.
+
+A plain run sets up, warms up, times `--steps` steps, writes the last timed step's outputs (`--dump-outputs`) and prints the line.
+Everything else runs only under `--full`: the timed outputs checked against an eager step (and the all-gather verified at N > 1, with
+its exposed cost), the other precision, the PCIe-inclusive rates, the roofline (with its rocprofv3 counter passes), the CPU and
+stock-PyTorch baselines with parity, the batch-1 object and the bounded objects of the other BASELINE configs."""
 from __future__ import annotations
 
 import json
@@ -11,7 +16,7 @@ import torch
 
 from .baselines import cpu_baseline_c2, parity_of, torch_gpu_baseline
 from .c3 import batch1_object
-from .common import FLOPS_PER_IMAGE_C2, PRECISION_DTYPE, PRECISION_TEXT, rank_env
+from .common import FLOPS_PER_IMAGE_C2, PRECISION_DTYPE, PRECISION_TEXT, dump_outputs, rank_env
 from .lanes import build_lanes, check_timed_outputs, make_launch
 from .objects import c4_object, c5_object, pseudo_label_object, solver_object
 from .roofline import gemm_roofline, live_pmc_traffic
@@ -49,12 +54,13 @@ def run(args):
 
     coll_box = {}
 
-    def timed_run(precision: str, steps: int, warmup: int, h2d: bool = False, d2h: bool = False, check: bool = False, gather=None):
+    def timed_run(precision: str, steps: int, warmup: int, h2d: bool = False, d2h: bool = False, check: bool = False, gather=None, dump=None):
         """Builds the engine for `precision`, one lane (engine fork + launch plan + stream + gather buffer) per step in
         flight, and times `steps` steps through zutis_amd.distributed.StepPipeline.  Returns (engine, seconds).
         h2d: every step first copies its batch from pinned host memory; d2h: every step ends with its label maps copied to
         pinned host memory (both asynchronous, in stream order on the step's own stream).  gather: None = as the run is configured
-        (the all-gather per step whenever there is a process group); False = the same steps without it (the exposed-gather A/B)."""
+        (the all-gather per step whenever there is a process group); False = the same steps without it (the exposed-gather A/B).
+        dump: directory for the outputs of the last timed step (rank 0)."""
         gather = dist_on if gather is None else gather
         eng = engines.get(precision)
         if eng is None:
@@ -91,11 +97,15 @@ def run(args):
                          gathers_retired_in_timed_region=pipe.retired - retired0, steps=steps,
                          per_rank_images_per_s={"min": round(B * steps / float(every.max().item()), 2), "max": round(B * steps / float(every.min().item()), 2)})
                 coll_box[precision] = c
+        if dump is not None and rank == 0:
+            last = max(lanes, key=lambda ln: ln.step)          # the lane that ran the last timed step
+            dump_outputs(dump, {"labels": last.state["labels"], "logits_lowres": last.payload.view(last.state["lo_shape"])})
         # the outputs of the plans that were just timed (outside the timed region): bitwise an eager step, lane by lane
         checked = check_timed_outputs(lanes) if check else None
         return eng, dt, checked
 
-    eng, elapsed, timed_out = timed_run(args.precision, args.steps, args.warmup, h2d=args.h2d, d2h=args.d2h, check=True)
+    eng, elapsed, timed_out = timed_run(args.precision, args.steps, args.warmup, h2d=args.h2d, d2h=args.d2h, check=args.full,
+                                        dump=args.dump_outputs)
     collective = coll_box.get(args.precision)
     if collective is not None:
         # what the per-step gather costs on the critical path: the same steps, same lanes, without it (max over ranks both times)
@@ -105,14 +115,14 @@ def run(args):
     # second line (N = 1 only, bounded): the same workload at the other precision (default: "fast", narrower than the reference
     # in the transformer bodies — reported, not the headline)
     other = None
-    if world == 1 and not args.no_second_precision:
+    if args.full and world == 1 and not args.no_second_precision:
         oprec = "exact" if args.precision != "exact" else "fast"
         osteps = args.steps
         oeng, odt, otimed = timed_run(oprec, osteps, max(1, args.warmup // 2), h2d=args.h2d, d2h=args.d2h, check=True)
         other = {"precision": oprec, "eng": oeng, "timed": otimed, "value": round(B * osteps / odt, 2), "ms_per_step": round(odt / osteps * 1e3, 3), "steps": osteps}
     # PCIe-inclusive rates of the headline precision (N = 1, same number of steps): labels out, and batch in + labels out
     io_rates = None
-    if world == 1 and not args.no_io_rates and not (args.h2d or args.d2h):
+    if args.full and world == 1 and not args.no_io_rates and not (args.h2d or args.d2h):
         io_rates = {}
         for key, kw in (("d2h", dict(d2h=True)), ("h2d_d2h", dict(h2d=True, d2h=True))):
             _, idt, _ = timed_run(args.precision, args.steps, max(1, args.warmup // 2), **kw)
@@ -124,7 +134,7 @@ def run(args):
 
     # ---- roofline of the dominant kernel: HIP events (torch current stream == launch stream) around every launch
     roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         def one_eager_step():
             out = eng.forward(x)
             eng.predict_semantic(out["patch_tokens"], text, (S, S))
@@ -157,25 +167,25 @@ def run(args):
     # ---- CPU baseline: the oracle (CPU port of the reference path) on a bounded sample, rank 0 at N=1 only
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, refs = cpu_baseline_c2(args, cfg, x, text, S, n, B)
         parity = parity_of(timed_out, refs, n, S)
         if other is not None:
             other["parity"] = parity_of(other["timed"], refs, n, S)
 
     torch_gpu = None
-    if rank == 0 and world == 1 and args.torch_gpu_baseline and not args.no_torch_gpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.torch_gpu_baseline and not args.no_torch_gpu_baseline:
         torch_gpu = torch_gpu_baseline(P, cfg, x, text, S, B)
 
     batch1 = None
-    if rank == 0 and world == 1 and not args.no_batch1:
+    if args.full and rank == 0 and world == 1 and not args.no_batch1:
         for e in engines.values():                    # the headline's engines are done: free their buffers first
             e._bufs.clear()
         batch1 = batch1_object(args.precision, dev)
     # ---- the other BASELINE configs, bounded, in the driver-run line (N = 1, default workload only): c4 (518 px / 920 classes / 8 per step),
     # c5 (ViT-L/14@336 embedding extraction, one 256-image step, at the reference's fp16 arithmetic class) and the bilateral solver
     c4o = c5o = solvero = pseudoo = None
-    if rank == 0 and world == 1 and not args.no_configs and args.workload == "c2" and (S, n) == (336, 81):
+    if args.full and rank == 0 and world == 1 and not args.no_configs and args.workload == "c2" and (S, n) == (336, 81):
         for e in engines.values():
             e._bufs.clear()
         engines.clear()
@@ -208,10 +218,11 @@ def run(args):
             "model_tflops": round(total_images * FLOPS_PER_IMAGE_C2 / elapsed / 1e12 / world, 1) if (S, n) == (336, 81) else None,
             "model_tflops_note": "images/s x the REFERENCE model's 124.5 GFLOP per image (SURVEY 8d; MFU convention) per GPU — not executed flops: "
                                  "the engine executes fewer (roofline.executed_algorithmic_flops_per_step, DESIGN 2a)",
-            "timed_outputs_checked": bool(timed_out is not None and timed_out[0]),
+            "timed_outputs_checked": bool(timed_out[0]) if timed_out is not None else None,
             "timed_outputs_note": "after the timed region every lane's label maps and low-res logits (as the last replay of its launch plan "
                                   "left them) were compared bitwise with one eager step of the lane's engine on the same batch; `parity` "
-                                  "compares lane 0's timed outputs with the oracle",
+                                  "compares lane 0's timed outputs with the oracle" if timed_out is not None else
+                                  "not checked: a plain run only times (bench.py --full checks them and adds roofline, baselines, parity)",
             **({"collective": collective} if collective is not None else {}),
             "roofline": roof, "cpu_baseline": cpu, "parity": parity,
             **({"batch1": batch1} if batch1 else {}),

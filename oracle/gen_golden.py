@@ -405,6 +405,20 @@ def gen_encode_image():
     np.savez_compressed(os.path.join(GOLD, "encode_image.npz"), **d)
 
 
+def gen_training_interface():
+    """What the training delegate relies on in the reference's ZUTIS (zutis_amd/dropin/networks/zutis.py::_training_delegate): its
+    constructor's argument names and its parameter names (tiny config) -> tests/golden/reference_zutis_interface.json."""
+    import inspect
+    import json
+    net = build_reference_zutis(detgen.TINY, 7)
+    d = {"init_args": [a for a in inspect.signature(type(net).__init__).parameters if a != "self"],
+         "parameter_names": sorted(n for n, _ in net.named_parameters())}
+    with open(os.path.join(GOLD, "reference_zutis_interface.json"), "w") as f:
+        json.dump(d, f, indent=0)
+        f.write("\n")
+    print("training interface", len(d["init_args"]), "arguments,", len(d["parameter_names"]), "parameters")
+
+
 class _FakeCuda:
     """`clip.tokenize(texts).cuda()` in the reference loop: hand the CPU tensor back."""
     def __init__(self, t):
@@ -436,6 +450,9 @@ if __name__ == "__main__":
     if "--encode-image-only" in sys.argv:
         gen_encode_image()
         sys.exit(0)
+    if "--training-interface-only" in sys.argv:
+        gen_training_interface()
+        sys.exit(0)
     gen_ops()
     gen_selfmask()
     gen_bilateral()
@@ -446,3 +463,4 @@ if __name__ == "__main__":
     gen_c3()
     gen_a4()
     gen_encode_image()
+    gen_training_interface()

@@ -50,3 +50,22 @@ def test_live_traffic_failed_pass_returns_three_values(monkeypatch, tmp_path):
     monkeypatch.setenv("PATH", str(tmp_path) + os.pathsep + os.environ["PATH"])
     traffic, note, per = roofline.live_pmc_traffic([], 1, timeout_s=30)
     assert traffic is None and per is None and "failed" in note
+
+
+def test_dump_outputs_float32_within_budget_same_sample_every_run(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 files, at most the budget in all, and an over-budget array is written as the same seeded sample
+    of its elements every run (two builds compare element for element)."""
+    import numpy as np
+    import torch
+    from benchlib import common
+    monkeypatch.setattr(common, "DUMP_BUDGET_BYTES", 1 << 16)
+    labels = torch.arange(12, dtype=torch.int64).reshape(3, 4)
+    logits = np.random.default_rng(1).standard_normal(100000)
+    for d in ("a", "b"):
+        common.dump_outputs(str(tmp_path / d), {"labels": labels, "logits": logits})
+    assert sorted(os.listdir(tmp_path / "a")) == ["labels.npy", "logits_sample.npy"]
+    lab = np.load(tmp_path / "a" / "labels.npy")
+    assert lab.dtype == np.float32 and np.array_equal(lab, labels.numpy())
+    s1, s2 = np.load(tmp_path / "a" / "logits_sample.npy"), np.load(tmp_path / "b" / "logits_sample.npy")
+    assert s1.dtype == np.float32 and np.array_equal(s1, s2) and np.isin(s1, logits.astype(np.float32)).all()
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= (1 << 16) + 2 * 128

@@ -55,7 +55,7 @@ def test_rccl_one_rank_bench_headline_force_dist(dev):
     env = {**os.environ, "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "HSA_ENABLE_IPC_MODE_LEGACY": "0"}
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "6", "--warmup", "3", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "6", "--warmup", "3", "--full", "--no-cpu-baseline",
                         "--no-torch-gpu-baseline", "--no-second-precision", "--no-io-rates", "--no-batch1", "--no-configs", "--no-live-traffic"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])

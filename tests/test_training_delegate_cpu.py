@@ -5,10 +5,14 @@
 * not importable -> NotImplementedError (the HIP path is inference-only);
 * no_grad / frozen parameters never take that route (the engine is asked, and on this CPU-only box refuses to run).
 
-CPU only.  The first test uses a stand-in "reference" class; the second the REAL reference when /root/reference is present (this
-authoring container; skipped on the GPU box, where it does not exist)."""
+CPU only.  The first test uses a stand-in "reference" class; the two after it a reference checkout written by the test itself
+(`_reference_checkout`): laid out like the reference's (networks/zutis.py importing its own networks.* / utils.* siblings), its ZUTIS
+taking the reference's constructor arguments and holding the reference's parameter names, both as recorded from the real reference in
+tests/golden/reference_zutis_interface.json (oracle/gen_golden.py::gen_training_interface)."""
+import json
 import os
 import sys
+import textwrap
 import types
 
 import pytest
@@ -20,7 +24,67 @@ DROPIN = os.path.join(REPO, "zutis_amd", "dropin")
 sys.path.insert(0, DROPIN)
 from zutis_amd import detgen  # noqa: E402
 
-REF = "/root/reference"
+GOLDEN_INTERFACE = os.path.join(REPO, "tests", "golden", "reference_zutis_interface.json")
+
+
+def _reference_checkout(root, cfg):
+    """A reference-shaped checkout under `root`: networks/zutis.py defines ZUTIS over the parameter names (shapes of `cfg`) and
+    constructor arguments the real reference has, and imports sibling modules of the checkout's own `networks` and `utils` packages —
+    the packages whose names the overlay shadows.  Its forward is a differentiable function of the input and every parameter."""
+    golden = json.load(open(GOLDEN_INTERFACE))
+    sd = detgen.zutis_state_dict(cfg)
+    shapes = {k: list(sd[k].shape) for k in golden["parameter_names"]}
+    files = {
+        "networks/__init__.py": "",
+        "networks/arch.py": f"""
+            import torch
+            import torch.nn as nn
+
+            INIT_ARGS = {golden["init_args"]!r}
+            SHAPES = {shapes!r}
+
+
+            def build(root):
+                for name, shape in SHAPES.items():
+                    *path, leaf = name.split(".")
+                    m = root
+                    for p in path:
+                        if p not in m._modules:
+                            m.add_module(p, nn.Module())
+                        m = m._modules[p]
+                    m.register_parameter(leaf, nn.Parameter(torch.zeros(shape)))
+            """,
+        "networks/zutis.py": """
+            import torch
+            import torch.nn as nn
+            import torch.nn.functional as F
+
+            import utils.iou  # noqa: F401
+            from networks.arch import INIT_ARGS, build
+
+
+            class ZUTIS(nn.Module):
+                def __init__(self, **kwargs):
+                    super().__init__()
+                    assert set(kwargs) <= set(INIT_ARGS), sorted(set(kwargs) - set(INIT_ARGS))
+                    build(self)
+                    self.text_embeddings = None
+
+                def forward(self, x):
+                    w = self.encoder.conv1.weight
+                    f = F.conv2d(x, w, stride=w.shape[-1])
+                    s = sum(p.sum() for p in self.parameters())
+                    return {"mask_proposals": torch.sigmoid(f.mean(1, keepdim=True)), "patch_tokens": f.permute(0, 2, 3, 1) + s}
+            """,
+        "utils/__init__.py": "",
+        "utils/iou.py": "def compute_iou(a, b):\n    return (a & b).sum() / max(1, (a | b).sum())\n",
+    }
+    for rel, text in files.items():
+        path = os.path.join(root, rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(textwrap.dedent(text).lstrip("\n"))
+    return str(root)
 
 
 def _overlay(monkeypatch, cfg):
@@ -118,42 +182,33 @@ def test_refuses_without_a_reference_and_delegates_with_one(monkeypatch):
         net(x)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "networks")), reason="needs the reference checkout (authoring container only)")
-def test_delegate_is_the_real_reference(monkeypatch):
-    """With the one-line arrangement of INTEGRATION.md ("Training") the overlay's forward under autograd returns the REAL reference
-    module's outputs (bitwise: it is the reference's code over the same parameters), back-propagates, and state_dict round-trips."""
-    sys.path.insert(0, REPO)
-    from oracle import gen_golden as G
+def test_delegate_is_the_real_reference(monkeypatch, tmp_path):
+    """With the one-line arrangement of INTEGRATION.md ("Training") the overlay's forward under autograd returns the reference
+    module's outputs (bitwise: it is the reference checkout's code over the same parameters), back-propagates, and state_dict
+    round-trips; the overlay's constructor arguments and parameter names are those of the real reference (golden)."""
     cfg = detgen.TINY
+    ref_root = _reference_checkout(tmp_path / "reference", cfg)
     saved = {k: v for k, v in sys.modules.items() if k == "networks" or k.startswith("networks.") or k == "utils" or k.startswith("utils.")
-             or k in ("clip", "torchvision", "torchvision.ops", "pycocotools", "pycocotools.mask")}
+             or k == "clip"}
     path0 = list(sys.path)
     try:
-        G.install_stubs(cfg)                               # stand-ins for clip / torchvision.ops / pycocotools (SURVEY Appendix B)
         for m in [k for k in sys.modules if k == "networks" or k.startswith("networks.") or k == "utils" or k.startswith("utils.")]:
             del sys.modules[m]
-        sys.path.insert(0, REF)
+        sys.path.insert(0, ref_root)
         import networks.zutis as ref_mod                   # the reference's own module ...
-        import networks.clip_arch as ref_arch
-        assert ref_mod.__file__.startswith(REF)
-
-        def load(name, device=None):                       # the stand-in `clip.load`: the reference's own CLIP class, random init
-            m = ref_arch.CLIP(embed_dim=cfg.embed_dim, image_resolution=cfg.patch * cfg.grid, vision_layers=cfg.layers, vision_width=cfg.width,
-                              vision_patch_size=cfg.patch, context_length=8, vocab_size=64, transformer_width=64, transformer_heads=1,
-                              transformer_layers=1)
-            return m.float().eval(), None
-        sys.modules["clip"].load = load                    # (gen_golden's stub imports networks.clip_arch by name: shadowed below)
+        assert ref_mod.__file__.startswith(ref_root)
         sys.modules["zutis_reference_networks_zutis"] = ref_mod      # ... kept importable under another name: THE one line
         for m in [k for k in sys.modules if k == "networks" or k.startswith("networks.")]:
             del sys.modules[m]
-        sys.path.remove(REF)
+        sys.path.remove(ref_root)
         sys.path.insert(0, DROPIN)
-        import networks.zutis as NZ                        # the overlay shadows networks.zutis from here on
+        NZ = _overlay(monkeypatch, cfg)                    # the overlay shadows networks.zutis from here on
         assert NZ.__file__.startswith(DROPIN) and NZ.reference_zutis_class() is ref_mod.ZUTIS
-        sys.path.insert(1, REF)                            # the reference's constructor imports its own utils.* / networks.* siblings lazily
-        monkeypatch.setattr(NZ, "_clip", sys.modules["clip"])
         net = NZ.ZUTIS(categories=[f"c{i}" for i in range(7)], clip_arch="ViT-B/16", n_queries=cfg.n_queries,
                        n_decoder_layers=cfg.dec_layers, n_heads=cfg.dec_heads, device=torch.device("cpu"))
+        golden = json.load(open(GOLDEN_INTERFACE))
+        assert set(net._ctor_args) <= set(golden["init_args"])
+        assert sorted(n for n, _ in net.named_parameters()) == golden["parameter_names"]
         sd = {k: torch.from_numpy(v) for k, v in detgen.zutis_state_dict(cfg).items()}
         net.load_state_dict(sd, strict=True)
         net.train()
@@ -176,25 +231,21 @@ def test_delegate_is_the_real_reference(monkeypatch):
     finally:
         sys.path[:] = path0
         for m in [k for k in sys.modules if k == "networks" or k.startswith("networks.") or k == "utils" or k.startswith("utils.")
-                  or k in ("clip", "torchvision", "torchvision.ops", "pycocotools", "pycocotools.mask", "zutis_reference_networks_zutis")]:
+                  or k in ("clip", "zutis_reference_networks_zutis")]:
             del sys.modules[m]
         sys.modules.update(saved)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "networks")), reason="needs the reference checkout (authoring container only)")
-def test_keep_reference_helper_leaves_the_overlay_canonical(monkeypatch):
+def test_keep_reference_helper_leaves_the_overlay_canonical(monkeypatch, tmp_path):
     """`keep_reference_for_training(<reference>/networks/zutis.py)` (round-5 advisor: the hand-written alias left the reference's
     `networks` / `utils` cached and the overlay was silently never loaded): the reference's class becomes the delegate, and afterwards
     `networks.zutis`, `utils.running_score`, ... are still the overlay's modules — a later `from networks.zutis import ZUTIS`
     (utils/utils.py:166-174) gets the HIP module."""
-    sys.path.insert(0, REPO)
-    from oracle import gen_golden as G
-    cfg = detgen.TINY
-    keep = ("clip", "torchvision", "torchvision.ops", "pycocotools", "pycocotools.mask")
+    ref_root = _reference_checkout(tmp_path / "reference", detgen.TINY)
+    keep = ("clip",)
     saved = {k: v for k, v in sys.modules.items() if k == "networks" or k.startswith("networks.") or k == "utils" or k.startswith("utils.") or k in keep}
     path0 = list(sys.path)
     try:
-        G.install_stubs(cfg)
         for m in [k for k in sys.modules if k == "networks" or k.startswith("networks.") or k == "utils" or k.startswith("utils.")]:
             del sys.modules[m]
         sys.modules.pop("zutis_reference_networks_zutis", None)
@@ -202,7 +253,7 @@ def test_keep_reference_helper_leaves_the_overlay_canonical(monkeypatch):
         import networks.zutis as NZ
         import utils.running_score as RS
         assert NZ.__file__.startswith(DROPIN) and RS.__file__.startswith(DROPIN) and NZ.reference_zutis_class() is None
-        cls = NZ.keep_reference_for_training(os.path.join(REF, "networks", "zutis.py"))
+        cls = NZ.keep_reference_for_training(os.path.join(ref_root, "networks", "zutis.py"))
         assert cls.__module__ == "zutis_reference_networks_zutis" and NZ.reference_zutis_class() is cls and cls is not NZ.ZUTIS
         import importlib
         assert importlib.import_module("networks.zutis") is NZ and sys.modules["networks"].__file__.startswith(DROPIN)

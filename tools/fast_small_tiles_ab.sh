@@ -3,7 +3,7 @@
 # one-round tiles as selected until round 5 (variant library, built by
 #   tools/build_variant_lib.sh tools/_abl/libzh_r4tiles_f16.so "-DZH_F16_ROUND4_SMALL_TILES" gemm.hip
 # ) against this build, ABAB on one box.  usage (on the GPU box): bash tools/fast_small_tiles_ab.sh
-Q="--precision fast --no-second-precision --no-live-traffic --no-io-rates --no-batch1 --no-configs --no-cpu-baseline --no-torch-gpu-baseline --steps 40"
+Q="--precision fast --full --no-second-precision --no-live-traffic --no-io-rates --no-batch1 --no-configs --no-cpu-baseline --no-torch-gpu-baseline --steps 40"
 val() { python -c "import sys, json; d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d.get('timed_outputs_checked'))"; }
 for i in 1 2; do
   echo "== round-4 tiles, 3 in flight: $(ZUTIS_HIP_LIB=$PWD/tools/_abl/libzh_r4tiles_f16.so python bench.py $Q 2>/dev/null | val)"
