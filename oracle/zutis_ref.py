@@ -277,13 +277,14 @@ def instance_scores(mask_proposals: Tensor, patch_tokens: Tensor, text: Tensor,
                     threshold: float = 0.5, temperature: float = 5.0):
     """networks/zutis.py:376-420: per-query confidence, category id and score from last-layer proposals.
 
-    Returns (binary_lowres bool[B,Q,h,w], category_ids int64[B,Q], scores float32[B,Q]).
+    Returns (binary_lowres bool[B,Q,h,w], category_ids int64[B,Q], scores float32[B,Q]).  Generic in the dtype of the tokens: on
+    .double() inputs with threshold=float(np.float32(thr)) it is the float64 reference of the same fp32 binary masks.
     """
     mp = mask_proposals[:, -1] if mask_proposals.dim() == 5 else mask_proposals
     binary = mp > threshold
     sizes = binary.sum(dim=(-2, -1))
     conf = (mp * binary).sum(dim=(-2, -1)) / (sizes + 1e-7)
-    bf = binary.flatten(2).float()                                               # [B,Q,hw]
+    bf = binary.flatten(2).to(patch_tokens.dtype)                                # [B,Q,hw]; float64 inputs give the float64 reference
     avg = torch.einsum("bqn,bnc->bqc", bf, patch_tokens.flatten(1, 2)) / (sizes.unsqueeze(-1) + 1e-7)
     sem = torch.sigmoid(torch.einsum("nc,bqc->bqn", text, avg / (avg.norm(dim=-1, keepdim=True) + 1e-7)) * temperature)
     cat = torch.argmax(sem, dim=-1)

@@ -759,7 +759,13 @@ def test_range_flag_of_the_instance_statistics(dev):
         binary = torch.empty((B, Q, M), dtype=torch.uint8, device=dev)
         ops.instance_mask_stats(x.to(dev), Q * M, 0.5, B, Q, M, sizes, conf, binary, flag)
         assert bool(flag.item()) == bad
-        assert torch.equal(binary.cpu(), (x > 0.5).to(torch.uint8))
+        on = x > 0.5
+        assert torch.equal(binary.cpu(), on.to(torch.uint8))
+        # the statistics themselves (M = 300: the 4-wide path); a NaN proposal counts as off (NaN > thr is false)
+        n_on = on.sum(-1).double().flatten()
+        assert torch.equal(sizes.cpu().double(), n_on)
+        want = torch.where(on, x.double(), 0.0).sum(-1).flatten() / (n_on + 1e-7)
+        assert float((conf.cpu().double() - want).abs().max()) <= 2e-6
 
 
 @pytest.mark.parametrize("h,w,H,W", [(120, 160, 480, 640), (107, 160, 427, 640), (30, 40, 123, 164), (21, 21, 336, 336), (9, 13, 50, 1030)])

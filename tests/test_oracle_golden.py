@@ -64,6 +64,34 @@ def test_oracle_instance_predict_matches_reference(golden_dir):
             assert np.array_equal(up[i, q], ref_masks[j])
 
 
+@pytest.mark.parametrize("thr", [0.5, 0.7, 0.3])
+def test_float64_instance_scores_agree_with_the_fp32_oracle(thr):
+    """instance_scores on .double() inputs with threshold = fp32(thr) is the float64 reference of the GPU scoring tests: the same
+    binary masks as the fp32 form (torch compares an fp32 tensor with a Python scalar in fp32), the same categories wherever the
+    float64 top-two probabilities are more than 1e-6 apart, scores within 1e-6."""
+    g = torch.Generator().manual_seed(int(thr * 10))
+    B, Q, h, w, E, n = 2, 20, 12, 15, 64, 30
+    t = np.float32(thr)
+    mp = torch.rand((B, Q, h, w), generator=g)
+    mp.view(-1)[::7] = float(t)                                     # proposals equal to fp32(thr): off in both forms
+    mp.view(-1)[3::14] = float(np.nextafter(t, np.float32(1)))
+    pt = torch.randn((B, h, w, E), generator=g) + torch.randn((B, 1, 1, E), generator=g)
+    text = torch.from_numpy(detgen.text_embeddings(n, E))
+    b32, cat32, score32 = O.instance_scores(mp, pt, text, threshold=thr)
+    b64, cat64, score64 = O.instance_scores(mp.double(), pt.double(), text.double(), threshold=float(t))
+    assert torch.equal(b32, b64) and b32.view(-1)[::7].sum() == 0
+    if thr == 0.3:
+        assert bool((mp.double().view(-1)[::7] > thr).all())      # a float64 compare with 0.3 itself would set them
+    assert score64.dtype == np.float64 and np.abs(score64 - score32).max() < 1e-6
+    bf = b64.flatten(2).double()
+    avg = torch.einsum("bqn,bnc->bqc", bf, pt.double().flatten(1, 2)) / (bf.sum(-1, keepdim=True) + 1e-7)
+    prob = torch.sigmoid(torch.einsum("nc,bqc->bqn", text.double(), avg / (avg.norm(dim=-1, keepdim=True) + 1e-7)) * 5.0)
+    top2 = prob.topk(2, dim=-1).values
+    clear = (top2[..., 0] - top2[..., 1] > 1e-6).numpy()
+    assert clear.mean() > 0.9 and np.array_equal(cat64[clear], cat32[clear])
+    assert np.array_equal(cat64, prob.argmax(-1).numpy())
+
+
 def test_oracle_ops_match_reference(golden_dir):
     g = np.load(f"{golden_dir}/ops.npz")
     for gr, (h, w) in [(14, (21, 21)), (14, (32, 32)), (7, (7, 7)), (14, (30, 40)), (4, (5, 7))]:

@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void instance_classify_kernel(const float* avg
                                                                 int n, int E, long long* category, float* score) {
   __shared__ float sv[1024];
   __shared__ float red[4];
-  __shared__ float bestv[4];
+  __shared__ int bestk[4];
   __shared__ int besti[4];
   const long r = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void instance_classify_kernel(const float* avg
   if (lane == 0) red[wave] = q;
   __syncthreads();
   const float inv = 1.0f / (sqrtf((red[0] + red[1]) + (red[2] + red[3])) + 1e-7f);
-  float bv = -1.f;
+  int bk = -1;                                            // key of the best class: the bits of its probability, sign cleared
   int bi = 0x7fffffff;
   // CPP classes per pass (cls, cls + 4, ...): their rows are loaded together — one class at a time was 21 dependent passes of
   // load -> reduce -> exp per wave, 48 us for 100 queries x 81 classes at batch 1.  Each class's dot product keeps its summation
@@ -186,18 +186,21 @@ __global__ __launch_bounds__(256) void instance_classify_kernel(const float* avg
     for (int j = 0; j < CPP; ++j) {
       const float dj = wave_sum(d[j]);
       const float pr = 1.0f / (1.0f + expf(-temperature * dj));
-      if (cls + 4 * j < n && pr > bv) { bv = pr; bi = cls + 4 * j; }          // classes ascend within a wave -> first max kept
+      // classes ascend within a wave -> first max kept.  A probability is +0 .. 1 or NaN; as the integer bits with the sign cleared
+      // it orders the same and every NaN ranks above 1: the first NaN is kept, as torch.argmax / max take a NaN as the maximum
+      const int key = __float_as_int(pr) & 0x7fffffff;
+      if (cls + 4 * j < n && key > bk) { bk = key; bi = cls + 4 * j; }
     }
   }
-  if (lane == 0) { bestv[wave] = bv; besti[wave] = bi; }
+  if (lane == 0) { bestk[wave] = bk; besti[wave] = bi; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    float v = bestv[0];
+    int k = bestk[0];
     int i = besti[0];
     for (int w = 1; w < 4; ++w)
-      if (bestv[w] > v || (bestv[w] == v && besti[w] < i)) { v = bestv[w]; i = besti[w]; }
+      if (bestk[w] > k || (bestk[w] == k && besti[w] < i)) { k = bestk[w]; i = besti[w]; }
     category[r] = i;
-    score[r] = conf[r] * v;
+    score[r] = conf[r] * __int_as_float(k);
   }
 }
 

@@ -443,7 +443,7 @@ def mask_iou_counts(masks_u8, n, pixels, inter, uni, workspace=None):
     need = L.zh_mask_iou_workspace_size(n, pixels)
     ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=masks_u8.device)
     if ws.numel() * ws.element_size() < need:
-        raise ZutisHipError(f"mask_iou_counts: workspace holds {ws.numel() * ws.element_size()} bytes, {need} needed")
+        raise _lib.ZutisHipError(f"mask_iou_counts: workspace holds {ws.numel() * ws.element_size()} bytes, {need} needed")
     _lib.check(L.zh_mask_iou_counts(_p(masks_u8), n, pixels, _p(inter), _p(uni), _p(ws), need, _stream()), "zh_mask_iou_counts")
 
 
@@ -481,7 +481,7 @@ def mask_runs_kept(masks_u8, kept_index, kept_count, max_runs, pos, nr, ba, pack
     _chk(pos, torch.int32, "mask_runs_kept pos")
     B, Q, H, W = masks_u8.shape
     if not packed and pos.numel() < B * Q * max_runs:
-        raise ZutisHipError(f"mask_runs_kept: pos holds {pos.numel()} ints, the row form needs {B * Q * max_runs}")
+        raise _lib.ZutisHipError(f"mask_runs_kept: pos holds {pos.numel()} ints, the row form needs {B * Q * max_runs}")
     need = int(_lib.load(raw=True).zh_mask_runs_workspace_size(B * Q, W))
     ws = torch.empty(need, dtype=torch.uint8, device=masks_u8.device)
     _lib.check(L.zh_mask_runs_kept(_p(masks_u8), _p(kept_index), _p(kept_count), B, Q, H, W, max_runs, _p(pos), pos.numel() if packed else 0,
@@ -514,7 +514,7 @@ def mask_rle_fused_kept(masks_u8, kept_index, kept_count, max_runs, out, cursor,
     if bits is not None:
         _chk(bits, torch.int64, "mask_rle_fused_kept bits")
         if bits.numel() != B * Q * ((H * W + 63) // 64):
-            raise ZutisHipError(f"mask_rle_fused_kept: bits holds {bits.numel()} words, {B * Q * ((H * W + 63) // 64)} expected")
+            raise _lib.ZutisHipError(f"mask_rle_fused_kept: bits holds {bits.numel()} words, {B * Q * ((H * W + 63) // 64)} expected")
     _lib.check(L.zh_mask_rle_fused_kept(_p(masks_u8), None if bits is None else _p(bits), _p(kept_index), _p(kept_count), B, Q, H, W, max_runs,
                                         _p(out), out.numel(), _p(cursor), _p(info), _stream()), "zh_mask_rle_fused_kept")
 
