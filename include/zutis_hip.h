@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 225 /* 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 226 /* 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -153,6 +153,7 @@ int zh_layernorm_f32(const float* x, long in_group_rows, long in_group_stride, l
  * forward (at its next synchronisation) and raises; bit 0 of the same word is zh_instance_mask_stats' range flag. */
 #define ZH_STATUS_RANGE 1
 #define ZH_STATUS_NONFINITE 2
+#define ZH_STATUS_LABEL 4 /* zh_upsample_ce_fwd: a label that is neither < n_cat nor ignore_index (never used as an index) */
 
 /* Split-K combine + bias + residual + LayerNorm (+ a second, chained LayerNorm) in one pass over each row (round 4):
  *   x = ((parts[0] + ... + parts[n_parts-1]) + bias) + residual      parts f32 [n_parts][rows, D] at part_stride, in plane order
@@ -353,6 +354,52 @@ int zh_mask_rle_kept(const int* positions, long packed_capacity, const int* nrun
 int zh_mask_rle_fused_supported(int H, int W, int max_runs);
 int zh_mask_rle_fused_kept(const unsigned char* masks, const unsigned long long* bits, const int* kept_index, const int* kept_count, int B, int Q,
                            int H, int W, int max_runs, unsigned char* out, long out_capacity, int* cursor, int* info, zh_stream_t stream);
+
+/* ---- Training criterion, criterion.py::Criterion (called by Trainer.fit, trainer.py:105-160).  All fp32; the full-resolution
+ * proposals, tokens, logits and their gradients are never written: every full-res value is a bilinear sample (ATen size= form,
+ * scale_* = float32(in)/float32(out)) of the low-res input, formed where it is reduced.  Sums are blocked and reduced in a fixed
+ * order (no float atomics): costs, losses and gradients are bitwise reproducible run to run.
+ *
+ * Matching costs, criterion.py:97-135 (dice_loss :26-41, binary_cross_entropy_loss :43-61, cost_matrix :131), every (image, layer) in
+ * one call.  proposals f32 [B, L, Q, h, w] in [0, 1]; gt_u8 [n_tot, H, W] (non-zero = in the mask): image b's instances are rows
+ * inst_off[b] .. inst_off[b+1]-1 (inst_off int32 [B+1], device); n_max = max instances of an image.  Outputs: costs f32 — image b's
+ * [L, n_b, Q] block at offset L * inst_off[b] * Q — = weight_dice * dice + weight_bce * bce with
+ *   dice = 1 - (2 sum(g p) + 1) / (sum p + sum g + 1),  bce = -(sum B + sum g (A - B)) / (H W),  A = max(log p, -100), B = max(log(1-p), -100);
+ * stat_p f32 [B, L, Q] (sum p), stat_pg (sum g p, the layout of costs), stat_g f32 [n_tot] (sum g) for zh_mask_match_grad;
+ * skip int32 [B] = 1 where an image's GT masks sum to 0 (criterion.py:116-118); ZH_STATUS_RANGE OR-ed into *status when a proposal
+ * is outside [0, 1] or NaN (the asserts of criterion.py:71-72).  workspace >= zh_mask_match_cost_workspace_size. */
+size_t zh_mask_match_cost_workspace_size(int B, int L, int Q, int H, int n_max);
+int zh_mask_match_cost(const float* proposals, const unsigned char* gt_u8, const int* inst_off, float* costs, float* stat_p,
+                       float* stat_pg, float* stat_g, int* skip, int* status, int B, int L, int Q, int h, int w, int H, int W,
+                       int n_max, float weight_dice, float weight_bce, float scale_h, float scale_w, void* workspace,
+                       size_t workspace_bytes, zh_stream_t stream);
+/* Backward of the matched costs, criterion.py:136-149 (the autograd of cost_matrix[i, q] through F.interpolate, :124-125).
+ * pairs int32 [n_pairs, 4] = (b, l, q, i) with i local to image b, at most one pair per (b, l, q).  grad_proposals f32 [B, L, Q, h, w]
+ * is zeroed and each matched plane gets the adjoint upsample of
+ *   grad_out[0] * loss_scale * ( weight_dice * -(2 g D - N) / D^2 + weight_bce * (p - g) / max(p (1 - p), 1e-12) / (H W) ),
+ * D = sum p + sum g + 1, N = 2 sum(g p) + 1 (stat_* of zh_mask_match_cost); loss_scale = weight_mask_loss / batch_size (:150,152). */
+int zh_mask_match_grad(const float* proposals, const unsigned char* gt_u8, const int* inst_off, const int* pairs, int n_pairs,
+                       const float* stat_p, const float* stat_pg, const float* stat_g, const float* grad_out, float* grad_proposals,
+                       int B, int L, int Q, int h, int w, int H, int W, float weight_dice, float weight_bce, float loss_scale,
+                       float scale_h, float scale_w, zh_stream_t stream);
+/* Cross-entropy on upsampled logits, criterion.py:77-95: einsum(te, upsample(tok)) = upsample(einsum(te, tok)), so the caller
+ * passes the low-res logits f32 [B, n_cat, h, w] (zh_gemm_f32_strided); labels int64 [B, H, W].  lse f32 [B, H, W] (log-sum-exp
+ * per pixel, kept for the backward); out f32 [2] = (mean NLL over the pixels whose label != ignore_index — NaN when there is none,
+ * as torch —, that count).  A label that is neither in [0, n_cat) nor ignore_index counts as ignored and OR-s ZH_STATUS_LABEL into
+ * *status.  workspace >= zh_upsample_ce_workspace_size. */
+size_t zh_upsample_ce_workspace_size(int B, int H, int W);
+int zh_upsample_ce_fwd(const float* logits_lo, const long long* labels, float* lse, float* out, int* status, int B, int n_cat,
+                       int h, int w, int H, int W, int ignore_index, float scale_h, float scale_w, void* workspace,
+                       size_t workspace_bytes, zh_stream_t stream);
+/* Its backward: grad_logits_lo f32 [B, n_cat, h, w] (fully written) = adjoint upsample of grad_out[0] / out[1] * (softmax - onehot),
+ * 0 on ignored pixels (ce_out = the `out` of zh_upsample_ce_fwd). */
+int zh_upsample_ce_bwd(const float* logits_lo, const long long* labels, const float* lse, const float* ce_out,
+                       const float* grad_out, float* grad_logits_lo, int B, int n_cat, int h, int w, int H, int W,
+                       int ignore_index, float scale_h, float scale_w, zh_stream_t stream);
+/* C[t](m, n) = sum_k A[t](m, k) B[t](n, k), every operand by element strides (batch, row, k): the low-res text contraction
+ * einsum("nc,bchw->bnhw") of criterion.py:88-90 and its transpose for the token gradient.  fp32, fixed k order. */
+int zh_gemm_f32_strided(const float* A, long sAb, long sAm, long sAk, const float* Bm, long sBb, long sBn, long sBk, float* C,
+                        long sCb, long sCm, long sCn, int batch, int M, int N, int K, zh_stream_t stream);
 
 /* Native launch plans (zutis_amd/plan.py): replay n recorded calls of the entry points above (op id + 24 argument words
  * each; dispatcher generated from this header) in one C loop; zh_plan_run2 alternates two plans on two streams. */

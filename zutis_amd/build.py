@@ -20,7 +20,7 @@ MAX_SCRATCH = int(os.environ.get("ZH_BUILD_MAX_SCRATCH", "0"))    # bytes per la
 MIN_OCCUPANCY = {"attn_f16_kernelILi64ELi4ELi1ELi0ELi1E": 3, "attn_f16_kernelILi64ELi4ELi0ELi0ELi1E": 3, "attn_f16_kernelILi64ELi4ELi1ELi1ELi1E": 2,
                  "attn_f16_kernelILi96ELi4ELi1ELi0ELi1E": 2, "attn_f16_kernelILi96ELi4ELi0ELi0ELi1E": 2, "attn_f16_kernelILi96ELi4ELi1ELi1ELi1E": 2,
                  "attn_f16_kernelILi64ELi4ELi1ELi0ELi2E": 2}
-SOURCES = ["capi.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "bilateral.hip", "retrieval.hip", "text.hip", "plan.hip"]
+SOURCES = ["capi.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "bilateral.hip", "retrieval.hip", "text.hip", "criterion.hip", "plan.hip"]
 
 
 def _hipcc() -> str:

@@ -94,6 +94,19 @@ __device__ __forceinline__ void zh_store_h1(half_t* p, long lo_plane, float y) {
   if (lo_plane) p[lo_plane] = (half_t)(y - (float)h);
 }
 
+// bilinear index/weight (resample.hip, criterion.hip), ATen compute_source_index_and_lambda (align_corners=False)
+struct LinW { int i0, i1; float l0, l1; };
+__device__ __forceinline__ LinW lin_weights(int dst, int in_size, int out_size, float scale) {
+  LinW r;
+  if (in_size == out_size) { r.i0 = r.i1 = dst; r.l0 = 1.f; r.l1 = 0.f; return r; }
+  const float src = fmaxf(__fmaf_rn(scale, (float)dst + 0.5f, -0.5f), 0.f);
+  r.i0 = min((int)src, in_size - 1);
+  r.i1 = min(r.i0 + 1, in_size - 1);
+  r.l1 = fminf(fmaxf(src - (float)r.i0, 0.f), 1.f);
+  r.l0 = 1.f - r.l1;
+  return r;
+}
+
 // activation codes shared by the GEMM epilogue (include/zutis_hip.h ZH_ACT_*)
 #define ZH_ACT_NONE 0
 #define ZH_ACT_QUICKGELU 1   // x * sigmoid(1.702 x)      networks/clip_arch.py:295-297

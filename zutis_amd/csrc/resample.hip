@@ -273,18 +273,7 @@ extern "C" int zh_cast_f32_f16(const float* x, const float* add, int add_rows, v
   return ZH_OK;
 }
 
-// ---- bilinear index/weight, ATen compute_source_index_and_lambda (align_corners=False)
-struct LinW { int i0, i1; float l0, l1; };
-__device__ __forceinline__ LinW lin_weights(int dst, int in_size, int out_size, float scale) {
-  LinW r;
-  if (in_size == out_size) { r.i0 = r.i1 = dst; r.l0 = 1.f; r.l1 = 0.f; return r; }
-  const float src = fmaxf(__fmaf_rn(scale, (float)dst + 0.5f, -0.5f), 0.f);
-  r.i0 = min((int)src, in_size - 1);
-  r.i1 = min(r.i0 + 1, in_size - 1);
-  r.l1 = fminf(fmaxf(src - (float)r.i0, 0.f), 1.f);
-  r.l0 = 1.f - r.l1;
-  return r;
-}
+// (bilinear index/weight: lin_weights, common.h)
 
 // ---- fused bilinear upsample + argmax over classes (networks/zutis.py:366-372), never materialising
 //      [B,n,H,W].  logits [B,n,h,w] fp32 (NCHW, low-res) -> labels int64 [B,H,W]; first index on ties.

@@ -267,7 +267,7 @@ def group_mean_l2norm(x, out, groups, T, E):
     _lib.check(L.zh_group_mean_l2norm(_p(x), _p(out), groups, T, E, _stream()), "zh_group_mean_l2norm")
 
 
-STATUS_RANGE, STATUS_NONFINITE = 1, 2        # bits of the status word (zutis_hip.h ZH_STATUS_*)
+STATUS_RANGE, STATUS_NONFINITE, STATUS_LABEL = 1, 2, 4     # bits of the status word (zutis_hip.h ZH_STATUS_*)
 UNIT_NORM_SCALE = 1024.0                     # f16_scale of the unit-norm producers (2^10): see zutis_hip.h
 
 
@@ -633,3 +633,74 @@ def mask_runs(masks_u8, sel, max_runs=8192):
     ws = torch.empty(need, dtype=torch.uint8, device=masks_u8.device)
     _lib.check(L.zh_mask_runs(_p(masks_u8), _p(sel), m, H, W, max_runs, _p(pos), _p(nr), _p(ba), _p(ws), need, _stream()), "zh_mask_runs")
     return pos, nr, ba
+
+
+# ---- training criterion (criterion.py::Criterion): zutis_amd/criterion.py
+
+def mask_match_cost(proposals, gt_u8, inst_off, n_max, H, W, costs, stat_p, stat_pg, stat_g, skip, status, weight_dice=1.0, weight_bce=1.0):
+    """proposals f32 [B, L, Q, h, w]; gt_u8 [n_tot, H, W]; inst_off int32 [B + 1] (device).  Writes costs / stat_pg (image b's [L, n_b, Q]
+    at L * inst_off[b] * Q), stat_p [B, L, Q], stat_g [n_tot], skip int32 [B] and ORs STATUS_RANGE into status (see zutis_hip.h)."""
+    L = _lib.load()
+    _chk(proposals, f32, "mask_match_cost proposals")
+    _chk(gt_u8, torch.uint8, "mask_match_cost gt_u8")
+    _chk(inst_off, torch.int32, "mask_match_cost inst_off")
+    B, Ly, Q, h, w = proposals.shape
+    need = int(_lib.load(raw=True).zh_mask_match_cost_workspace_size(B, Ly, Q, H, n_max))
+    ws = torch.empty(need, dtype=torch.uint8, device=proposals.device)
+    _lib.check(L.zh_mask_match_cost(_p(proposals), _p(gt_u8) if gt_u8.numel() else None, _p(inst_off), _p(costs), _p(stat_p), _p(stat_pg),
+                                    _p(stat_g), _p(skip), _p(status), B, Ly, Q, h, w, H, W, n_max, float(weight_dice), float(weight_bce),
+                                    lin_scale(h, H), lin_scale(w, W), _p(ws), need, _stream()), "zh_mask_match_cost")
+
+
+def mask_match_grad(proposals, gt_u8, inst_off, pairs, stat_p, stat_pg, stat_g, grad_out, H, W, weight_dice, weight_bce, loss_scale, out=None):
+    """pairs int32 [P, 4] = (b, l, q, i local) on the device -> grad f32 [B, L, Q, h, w] (0 outside the matched planes)."""
+    L = _lib.load()
+    _chk(proposals, f32, "mask_match_grad proposals")
+    _chk(pairs, torch.int32, "mask_match_grad pairs")
+    _chk(grad_out, f32, "mask_match_grad grad_out")
+    B, Ly, Q, h, w = proposals.shape
+    out = torch.empty_like(proposals) if out is None else out
+    _chk(out, f32, "mask_match_grad out")
+    n_pairs = pairs.shape[0]
+    _lib.check(L.zh_mask_match_grad(_p(proposals), _p(gt_u8) if gt_u8.numel() else None, _p(inst_off), _p(pairs) if n_pairs else None,
+                                    n_pairs, _p(stat_p), _p(stat_pg), _p(stat_g), _p(grad_out), _p(out), B, Ly, Q, h, w, H, W,
+                                    float(weight_dice), float(weight_bce), float(loss_scale), lin_scale(h, H), lin_scale(w, W), _stream()),
+               "zh_mask_match_grad")
+    return out
+
+
+def upsample_ce_fwd(logits_lo, labels, ignore_index, out, status, lse=None):
+    """logits_lo f32 [B, n_cat, h, w], labels int64 [B, H, W] -> out f32 [2] = (mean NLL, valid count); lse f32 [B, H, W] returned."""
+    L = _lib.load()
+    _chk(logits_lo, f32, "upsample_ce logits_lo")
+    _chk(labels, torch.int64, "upsample_ce labels")
+    B, n, h, w = logits_lo.shape
+    H, W = labels.shape[-2:]
+    lse = torch.empty((B, H, W), dtype=f32, device=logits_lo.device) if lse is None else lse
+    need = int(_lib.load(raw=True).zh_upsample_ce_workspace_size(B, H, W))
+    ws = torch.empty(need, dtype=torch.uint8, device=logits_lo.device)
+    _lib.check(L.zh_upsample_ce_fwd(_p(logits_lo), _p(labels), _p(lse), _p(out), _p(status), B, n, h, w, H, W, int(ignore_index),
+                                    lin_scale(h, H), lin_scale(w, W), _p(ws), need, _stream()), "zh_upsample_ce_fwd")
+    return lse
+
+
+def upsample_ce_bwd(logits_lo, labels, lse, ce_out, grad_out, ignore_index, out=None):
+    L = _lib.load()
+    _chk(logits_lo, f32, "upsample_ce_bwd logits_lo")
+    _chk(grad_out, f32, "upsample_ce_bwd grad_out")
+    B, n, h, w = logits_lo.shape
+    H, W = labels.shape[-2:]
+    out = torch.empty_like(logits_lo) if out is None else out
+    _lib.check(L.zh_upsample_ce_bwd(_p(logits_lo), _p(labels), _p(lse), _p(ce_out), _p(grad_out), _p(out), B, n, h, w, H, W,
+                                    int(ignore_index), lin_scale(h, H), lin_scale(w, W), _stream()), "zh_upsample_ce_bwd")
+    return out
+
+
+def gemm_f32_strided(A, a_strides, Bm, b_strides, C, c_strides, batch, M, N, K):
+    """C[t](m, n) = sum_k A[t](m, k) Bm[t](n, k); *_strides = (batch, row, k) / (batch, m, n) in elements; fp32 tensors."""
+    L = _lib.load()
+    for t, nm in ((A, "A"), (Bm, "B"), (C, "C")):
+        if t.dtype != f32:
+            raise _lib.ZutisHipError(f"gemm_f32_strided {nm}: expected float32, got {t.dtype}")
+    _lib.check(L.zh_gemm_f32_strided(_p(A), *a_strides, _p(Bm), *b_strides, _p(C), *c_strides, batch, M, N, K, _stream()),
+               "zh_gemm_f32_strided")
