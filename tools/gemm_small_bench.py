@@ -85,9 +85,6 @@ if __name__ == "__main__":
         bench(442, 3072, 768, "fc336", (0, 3064, 6496), act=ops.ACT_QUICKGELU)
         bench(442, 768, 3072, "proj336", (0, 3064), out="f32", resid=True)
         bench(442, 768, 3072, "proj336/S", (0, 3064), splits=(2, 4, 8), out="f32")
-    if which == "abl":        # K-loop ablations (ZUTIS_HIP_LIB = a -DZH_X3_NO* variant library): timing only, results are garbage
-        bench(T, 2304, 768, "qkv", (96, 1288, 64, 3064))
-        bench(T, 3072, 768, "fc", (64, 1288, 3064), act=ops.ACT_QUICKGELU)
     if which == "warm":       # where do the weights come from: 40 buffers (HBM, as in the model), 4 (Infinity Cache), 1 (L2 / Infinity Cache)
         for nw in (40, 4, 1):
             bench(T, 2304, 768, f"qkv/w{nw}", (96, 1288), NW=nw)

@@ -16,10 +16,11 @@ EXTRA_FLAGS = {"bilateral.hip": ["-ffp-contract=off"]}
 # the MFMA kernels live at the register budget of their occupancy: a spill is a 2-3x slowdown, so it is a build error
 NO_SCRATCH = {"gemm.hip", "gemm_x3.hip", "attention.hip"}
 MAX_SCRATCH = int(os.environ.get("ZH_BUILD_MAX_SCRATCH", "0"))    # bytes per lane tolerated: the MFMA loops must not spill (developer builds may raise it)
-# waves per SIMD the design of a kernel relies on (mangled-name substring -> minimum), checked against the compiler's remarks
-MIN_OCCUPANCY = {"attn_f16_kernelILi64ELi4ELi1ELi0ELi1E": 3, "attn_f16_kernelILi64ELi4ELi0ELi0ELi1E": 3, "attn_f16_kernelILi64ELi4ELi1ELi1ELi1E": 2,
-                 "attn_f16_kernelILi96ELi4ELi1ELi0ELi1E": 2, "attn_f16_kernelILi96ELi4ELi0ELi0ELi1E": 2, "attn_f16_kernelILi96ELi4ELi1ELi1ELi1E": 2,
-                 "attn_f16_kernelILi64ELi4ELi1ELi0ELi2E": 2}
+# waves per SIMD the design of a kernel relies on (source -> mangled-name substring -> minimum), checked against the compiler's
+# remarks; a key that matches no kernel of its source is a build error (a renamed template would otherwise drop its guard)
+MIN_OCCUPANCY = {"attention.hip": {"attn_f16_kernelILi64ELi4ELi1ELi0EE": 3, "attn_f16_kernelILi64ELi4ELi0ELi0EE": 3,
+                                   "attn_f16_kernelILi64ELi4ELi1ELi1EE": 2, "attn_f16_kernelILi96ELi4ELi1ELi0EE": 2,
+                                   "attn_f16_kernelILi96ELi4ELi0ELi0EE": 2, "attn_f16_kernelILi96ELi4ELi1ELi1EE": 2}}
 SOURCES = ["capi.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "bilateral.hip", "retrieval.hip", "text.hip", "criterion.hip", "plan.hip"]
 
 
@@ -80,14 +81,21 @@ def build(force: bool = False, verbose: bool = True) -> str:
             if spills:
                 raise RuntimeError(f"{os.path.basename(src)}: a kernel spills to scratch (register budget exceeded): {spills[0].strip()}")
             fn = None
+            min_occ = MIN_OCCUPANCY.get(os.path.basename(src), {})
+            matched = set()
             for ln in err.splitlines():
                 if "Function Name:" in ln:
                     fn = ln.split("Function Name:")[1].split()[0]
                 elif "Occupancy [waves/SIMD]:" in ln and fn:
                     occ = int(ln.split("Occupancy [waves/SIMD]:")[1].split()[0])
-                    for key, need in MIN_OCCUPANCY.items():
-                        if key in fn and occ < need:
-                            raise RuntimeError(f"{os.path.basename(src)}: {fn} compiles to {occ} waves/SIMD, its design needs {need}")
+                    for key, need in min_occ.items():
+                        if key in fn:
+                            matched.add(key)
+                            if occ < need:
+                                raise RuntimeError(f"{os.path.basename(src)}: {fn} compiles to {occ} waves/SIMD, its design needs {need}")
+            unmatched = sorted(set(min_occ) - matched)
+            if unmatched:
+                raise RuntimeError(f"{os.path.basename(src)}: MIN_OCCUPANCY names no kernel of the compiler's remarks: {', '.join(unmatched)}")
         else:
             sys.stderr.write(err)
     cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs

@@ -16,7 +16,6 @@
 // LDS strides: K rows dh+8 halves (conflict-free ds_read_b128), V rows 96 halves (4 consecutive rows cover
 // disjoint 16-dword bank ranges for the transposed read).
 #include "common.h"
-#include <stdlib.h>
 #include <type_traits>
 
 struct AttnArgs {
@@ -32,18 +31,7 @@ struct AttnArgs {
   // UNNORMALISED fp32 accumulators + running max (log2 units) + row sum in the workspace; attn_combine_kernel merges them
   int ksplit, kchunk;
   float* part_o; float* part_m; float* part_l;   // [ksplit][B*Tq][H*dh], [ksplit][B*H][Tq] x 2
-#ifdef ZH_ATTN_STAMP
-  long long* stamp;   // developer build (tools/attn_stamp.py): [workgroup][wave][16] cycle sums per loop segment + clocks
-#endif
 };
-#ifdef ZH_ATTN_STAMP
-static long long* g_attn_stamp = nullptr;
-extern "C" void zh_attn_set_stamp(long long* p) { g_attn_stamp = p; }
-#define ZH_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); const long long n_ = __builtin_amdgcn_s_memtime(); st_acc[i] += n_ - st_prev; st_prev = n_; \
-                         __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define ZH_STAMP(i)
-#endif
 
 typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef __attribute__((address_space(3))) fp16x4* lds_fp16x4_ptr;
@@ -62,10 +50,6 @@ typedef __attribute__((address_space(3))) fp16x4* lds_fp16x4_ptr;
 // 38.2, 518-px encoder 111.8 -> 101.6 / 56.9 -> 50.6, ViT-L/14 1335 -> 1246 / 681 -> 625, SelfMask T = 5505 251 -> 231 / 128 -> 113;
 // each piece alone 1 - 3 %.  Not kept: s_setprio 1 around the K.Q^T MFMAs, the P.V MFMAs or the softmax (all within noise),
 // -fno-slp-vectorize (the packed multiplies left are the now rare rescale).
-// ZH_ATTN_PIPE (developer A/B): -1 = the launcher's rule, 0 / 1 = the split-pair kernels never / always run the pipelined loop
-#ifndef ZH_ATTN_PIPE
-#define ZH_ATTN_PIPE -1
-#endif
 #define ZH_ATTN_LAZY_LOG2 8.0f
 
 // max over the two lanes l, l ^ 32 (both get it)
@@ -90,16 +74,9 @@ __device__ __forceinline__ float zh_xor32_sum(float x) {
 // three workgroups per CU at dh = 64, two at dh = 96.  The occupancy is checked at build time (build.py MIN_OCCUPANCY reads the
 // compiler's resource remarks): asking for 3 through __launch_bounds__ makes hipcc pick a 168-VGPR allocation WITH 16 bytes of
 // scratch, while the looser bound compiles to 165 VGPRs and none — so the bound stays loose and the build fails on a regression.
-#ifndef ZH_ATTN_ABL
-#define ZH_ATTN_ABL 0      // developer ablations (tools/attn_ablate.py): 1 no exp, 2 no P.V, 4 no K.Q^T, 8 no tile traffic and no
-#endif                     // barriers, 16 no barriers, 32 barriers only, 64 no LDS stores.  0 in the product build.
-// QT = 2 (round 5, developer A/B behind ZH_ATTN_QT=2; split-pair dh = 64 only): a wave owns TWO 32-query tiles.  Every K / V fragment
-// read from LDS feeds both tiles' MFMAs and a key tile's loads / stores / barrier serve 256 queries per workgroup: the kernel is
-// bound by the SIMD's instruction issue (profiles/NOTES.md round 3), and those are the instructions that do not scale with the scores.
-template <int DH, int NWAVE, int X3, int PIPE, int QT = 1>
+template <int DH, int NWAVE, int X3, int PIPE>
 __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_f16_kernel(AttnArgs p) {
   static_assert(!PIPE || X3, "the pipelined loop exists for the split-pair kernels");
-  static_assert(QT == 1 || (QT == 2 && X3 && !PIPE && DH == 64), "two query tiles per wave: split-pair dh = 64, plain loop");
   constexpr int NT = 64 * NWAVE;
   constexpr int KS = DH + 8;          // K row stride (halves)
   constexpr int NKS = DH / 16;        // k-steps of QK^T
@@ -108,11 +85,7 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
   // keys per tile: 64, except the split-pair kernels — their lo planes double the LDS tiles and their three-product
   // accumulators the registers, so at 64 keys only one workgroup fits a CU (one wave per SIMD, nothing to overlap with);
   // 32-key tiles halve both and two or three workgroups fit
-#ifdef ZH_ATTN_X3_KT64
-  constexpr int KTT = KT;
-#else
   constexpr int KTT = X3 ? 32 : KT;        // (fp16 dh = 96 with 32 keys: cross-attention 44 -> 63 us — 256 workgroups, occupancy is not its limit)
-#endif
   constexpr int NU = KTT / 32;        // 32-key slot tiles per key tile
   constexpr int NLD = (KTT * CPR + NT - 1) / NT;              // chunk passes per thread (the last may be partial: dh = 96 x 32 keys)
   constexpr bool LDFULL = (KTT * CPR) % NT == 0;
@@ -122,9 +95,6 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
   __shared__ __attribute__((aligned(16))) half_t sVl[X3 ? 2 : 1][X3 ? KTT * VS : 8];   // lo plane of V (X3)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef ZH_ATTN_STAMP
-  const long long st_e0 = __builtin_amdgcn_s_memtime(), st_re0 = __builtin_amdgcn_s_memrealtime();
-#endif
   // XCD-aware block order: workgroups are dealt round-robin to the 8 XCDs (linear id % 8), each with its own L2.  The work items
   // (group = image * heads + head, query block, key split) are numbered group-major and every XCD takes a CONTIGUOUS eighth of
   // that list: the query blocks / key splits of one (image, head) — which stream the same K / V — meet in one L2 (two at a range
@@ -132,17 +102,13 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
   // heads of one image four XCDs got two heads and four got one — the batch-1 encoder ran at the pace of the loaded half.)
   const int id = blockIdx.y * gridDim.x + blockIdx.x;
   const int per_group = p.nqb * p.ksplit;
-#ifdef ZH_ATTN_PLAIN_ORDER                               // developer A/B build: query blocks of a group on consecutive ids
-  const int item = id;
-#else
   const int item = (id & 7) * (int)(gridDim.x >> 3) + (id >> 3);   // the grid is 8 x (items per XCD)
-#endif
   if (item >= p.groups * per_group) return;             // surplus workgroups of the last XCD share (whole workgroup, before any barrier)
   const int group = item / per_group;
   const int qbs = item - group * per_group;
   const int qb = qbs / p.ksplit, ks = qbs - qb * p.ksplit;
   const int head = group % p.H, img = group / p.H;
-  const int q0 = qb * (32 * NWAVE * QT) + wave * (32 * QT);     // first query of this wave (its tile a starts at q0 + 32 a)
+  const int q0 = qb * (32 * NWAVE) + wave * 32;     // first query of this wave
   const int ql = lane & 31, hh = lane >> 5;
   const long hoff = (long)head * DH;
 
@@ -154,30 +120,21 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
   const half_t* V = p.V + (long)img * p.sV + hoff;
 
   // Q fragments (B operand: col = query, k = d)
-  half8_t qf[QT][NKS], qfl[QT][X3 ? NKS : 1];
+  half8_t qf[NKS], qfl[X3 ? NKS : 1];
+  const half_t* qp = Q + (long)min(q0 + ql, p.Tq - 1) * p.ldq + 8 * hh;     // (a wave beyond Tq reads the last query row)
 #pragma unroll
-  for (int a = 0; a < QT; ++a) {
-    int qr = q0 + 32 * a + ql;
-    qr = qr < p.Tq ? qr : p.Tq - 1;
-    const half_t* qp = Q + (long)qr * p.ldq + 8 * hh;
+  for (int ks = 0; ks < NKS; ++ks) qf[ks] = *(const half8_t*)(qp + 16 * ks);
+  if (X3) {
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) qf[a][ks] = *(const half8_t*)(qp + 16 * ks);
-    if (X3) {
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) qfl[a][ks] = *(const half8_t*)(qp + p.planeQ + 16 * ks);
-    }
+    for (int ks = 0; ks < NKS; ++ks) qfl[ks] = *(const half8_t*)(qp + p.planeQ + 16 * ks);
   }
 
-  f32x16 oacc[QT][NDT];
+  f32x16 oacc[NDT];
 #pragma unroll
-  for (int a = 0; a < QT; ++a)
+  for (int d = 0; d < NDT; ++d)
 #pragma unroll
-    for (int d = 0; d < NDT; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) oacc[a][d][r] = 0.f;
-  float m_run[QT];
-#pragma unroll
-  for (int a = 0; a < QT; ++a) m_run[a] = -INFINITY;
+    for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
+  float m_run = -INFINITY;
   // Row sums of P ride the MFMA pipe: one extra "d tile" whose V^T operand is all ones accumulates sum_k P[k][q] in every row
   // of lacc (32 v_add_f32 per key tile leave the VALU, which is the bound; the sum is of the SAME rounded P the numerator uses).
   // Split-pair kernels (X3) keep the row sum on the VALU instead: they are MFMA-bound (three products per score and per P.V
@@ -187,9 +144,7 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
   f32x16 lacc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) lacc[r] = 0.f;
-  float l_run[QT];
-#pragma unroll
-  for (int a = 0; a < QT; ++a) l_run[a] = 0.f;
+  float l_run = 0.f;
   half8_t ones;
 #pragma unroll
   for (int i = 0; i < 8; ++i) ones[i] = (half_t)1.0f;
@@ -268,44 +223,30 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
 
   int ntiles = (max(key_end - key0, 0) + KTT - 1) / KTT;
   if (p.causal) {                                           // key tiles entirely above this block's last query are skipped
-    const int qlast = min(p.Tq, (qb + 1) * (32 * NWAVE * QT)) - 1;
+    const int qlast = min(p.Tq, (qb + 1) * (32 * NWAVE)) - 1;
     ntiles = min(ntiles, qlast / KTT + 1);
   }
   const int qidx = q0 + ql;
   // a wave whose 32 queries all lie beyond Tq (T = 442: two of the last block's four) only helps with the tile loads
   const bool active = q0 < p.Tq;
-#ifdef ZH_ATTN_STAMP
-  long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-  long long st_prev = st_t0;
-#endif
 
   // ---- S^T(t) = K(t) Q^T from K buffer t & 1 (NU 32-key slot tiles)
-  auto qk = [&](int t, f32x16 (&s)[QT][NU]) {
+  auto qk = [&](int t, f32x16 (&s)[NU]) {
     const half_t* sK = sKb[t & 1];
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
 #pragma unroll
-      for (int a = 0; a < QT; ++a)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[a][u][r] = 0.f;
+      for (int r = 0; r < 16; ++r) s[u][r] = 0.f;
       const half_t* kp = sK + (32 * u + krow) * KS + 8 * hh;
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
         half8_t kf = *(const half8_t*)(kp + 16 * ks);
         half8_t kl;
         if (X3) kl = *(const half8_t*)(sKl[t & 1] + (32 * u + krow) * KS + 8 * hh + 16 * ks);
-#pragma unroll
-        for (int a = 0; a < QT; ++a) {                   // (QT = 2: the K fragments just read serve both query tiles)
-#if ZH_ATTN_ABL & 4
-          s[a][u][ks] += (float)kf[0] * (float)qf[a][ks][0];
-#else
-          s[a][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[a][ks], s[a][u], 0, 0, 0);
-#endif
-          if (X3) {
-            s[a][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qf[a][ks], s[a][u], 0, 0, 0);
-            s[a][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qfl[a][ks], s[a][u], 0, 0, 0);
-          }
+        s[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[u], 0, 0, 0);
+        if (X3) {
+          s[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qf[ks], s[u], 0, 0, 0);
+          s[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qfl[ks], s[u], 0, 0, 0);
         }
       }
     }
@@ -316,7 +257,7 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
   // ---- online softmax of tile t: scores -> P (fp16, or a split pair), accumulators rescaled when the reference point moves
   // (MASKED = false: the caller knows the tile is full and the attention not causal — no branch splits the block, so the
   //  pipelined loop's K.Q^T MFMAs of the next tile can be scheduled in among these instructions)
-  auto softmax = [&](int t, f32x16 (&s)[NU], PFrag& P, auto masked, int a = 0) {
+  auto softmax = [&](int t, f32x16 (&s)[NU], PFrag& P, auto masked) {
     constexpr bool MASKED = decltype(masked)::value;
     const int kbase = key0 + t * KTT;
     // register r of slot tile u holds key kbase + 32u + 16(r>>3) + 8*hh + (r&7)
@@ -344,25 +285,20 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
       mx = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
     }
     mx = zh_xor32_max(mx);
-    ZH_STAMP(2);
     // running max kept in log2 units (scale_log2 > 0 commutes with max): p = 2^(s*c - m) is ONE fma + v_exp_f32.
     // Lazy: the reference point only moves when the tile's max exceeds it by more than 2^8 (any fixed reference gives the same
     // softmax; both key halves of a query see the same mx and m_run, so they decide alike)
     const float m_cand = mx * p.scale_log2;
-    const float m_new = m_cand > m_run[a] + ZH_ATTN_LAZY_LOG2 ? m_cand : m_run[a];
-    const float alpha = __builtin_amdgcn_exp2f(m_run[a] - m_new);
-    m_run[a] = m_new;
+    const float m_new = m_cand > m_run + ZH_ATTN_LAZY_LOG2 ? m_cand : m_run;
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+    m_run = m_new;
     float lsum2[2] = {0.f, 0.f};                             // scalar adds: packed fp32 VALU is an anti-lever beside MFMAs (v_pk_add_f32 ~ +13 issue cycles)
 #pragma unroll
     for (int u = 0; u < NU; ++u)
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
-#if ZH_ATTN_ABL & 1
-        const float e0 = __builtin_fmaf(s[u][r], p.scale_log2, -m_new), e1 = __builtin_fmaf(s[u][r + 1], p.scale_log2, -m_new);
-#else
         const float e0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[u][r], p.scale_log2, -m_new));
         const float e1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[u][r + 1], p.scale_log2, -m_new));
-#endif
         if (X3) { lsum2[0] += e0; lsum2[1] += e1; }
         const half2_t eh2 = {(half_t)e0, (half_t)e1};      // one v_cvt_pk_f16_f32
         unsigned eh = __builtin_bit_cast(unsigned, eh2);
@@ -382,27 +318,22 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
 #pragma unroll
       for (int d = 0; d < NDT; ++d)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[a][d][r] *= alpha;
+        for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
       if (!X3) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) lacc[r] *= alpha;
       }
     }
-    if (X3) l_run[a] = l_run[a] * alpha + (lsum2[0] + lsum2[1]);
-    ZH_STAMP(3);
+    if (X3) l_run = l_run * alpha + (lsum2[0] + lsum2[1]);
   };
   // ---- O^T += V(t)^T P^T from V buffer t & 1
-  auto pv = [&](int t, const PFrag (&P)[QT]) {
+  auto pv = [&](int t, const PFrag& P) {
     const half_t* sV = sVb[t & 1];
-#if ZH_ATTN_ABL & 2
-    oacc[0][0][0] += (float)__builtin_bit_cast(half8_t, P[0].hi[0][0])[0] + (float)__builtin_bit_cast(half8_t, P[0].hi[NU - 1][1])[7];
-    lacc[0] += 1.0f; l_run[0] += 1.0f;
-#else
 #pragma unroll
     for (int u = 0; u < NU; ++u)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        if (!X3) lacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, __builtin_bit_cast(half8_t, P[0].hi[u][ks]), lacc, 0, 0, 0);
+        if (!X3) lacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, __builtin_bit_cast(half8_t, P.hi[u][ks]), lacc, 0, 0, 0);
         const half_t* vp = sV + (32 * u + 16 * ks + tr_row) * VS + tr_col;
 #pragma unroll
         for (int d = 0; d < NDT; ++d) {
@@ -419,26 +350,20 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
             __builtin_memcpy(&vl, &llo, 8);
             __builtin_memcpy(((char*)&vl) + 8, &lhi, 8);
           }
-#pragma unroll
-          for (int a = 0; a < QT; ++a) {                 // (QT = 2: the V fragments just read serve both query tiles)
-            const half8_t pf = __builtin_bit_cast(half8_t, P[a].hi[u][ks]);
-            oacc[a][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[a][d], 0, 0, 0);
-            if (X3) {
-              oacc[a][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, pf, oacc[a][d], 0, 0, 0);
-              oacc[a][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, __builtin_bit_cast(half8_t, P[a].lo[u][ks]), oacc[a][d], 0, 0, 0);
-            }
+          const half8_t pf = __builtin_bit_cast(half8_t, P.hi[u][ks]);
+          oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[d], 0, 0, 0);
+          if (X3) {
+            oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, pf, oacc[d], 0, 0, 0);
+            oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, __builtin_bit_cast(half8_t, P.lo[u][ks]), oacc[d], 0, 0, 0);
           }
         }
       }
-#endif
-    ZH_STAMP(4);
   };
 
-#if !ZH_ATTN_ABL
   if (PIPE && !p.causal) {
     // ---- software-pipelined loop (split-pair kernels): K runs ONE TILE AHEAD of V, and a wave issues the 12 K.Q^T MFMAs of tile
     // t+1 — which depend on nothing the softmax of tile t touches — in among that softmax's ~95 vector instructions, which
-    // then issue in the shadow of the MFMAs instead of next to an idle matrix pipe (in-kernel stamps, tools/attn_stamp.py: with
+    // then issue in the shadow of the MFMAs instead of next to an idle matrix pipe (in-kernel stamps, profiles/r03_attn_stamp_x3.txt: with
     // three uncoordinated waves per SIMD the pipe was 62 % busy inside the loop; a wave spent 19 % of a tile in exp / split /
     // pack with no MFMA of its own in flight).  Step t: global loads of K(t+2), V(t+1) -> [S(t+1) || softmax(t)] -> P(t).V(t) ->
     // stores -> barrier.  K(t+2) overwrites the buffer of K(t), last read in step t-1; V(t+1) that of V(t-1), last read in step
@@ -449,26 +374,23 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
     store_v(0, ra);
     if (ntiles > 1) { load_k(key0 + KTT, ra); store_k(1, ra); }
     __syncthreads();
-    f32x16 sA[QT][NU], sB[QT][NU];
-    PFrag P[QT];
+    f32x16 sA[NU], sB[NU];
+    PFrag P;
     if (active) qk(0, sA);
     __syncthreads();                               // step 0 stores K(2) over K(0): every wave's reads of K(0) come first
     // one step: tile t has a successor; par = t & 1 as a compile-time constant
-    auto step = [&](int t, auto par, f32x16 (&cur)[QT][NU], f32x16 (&nxt)[QT][NU]) {
+    auto step = [&](int t, auto par, f32x16 (&cur)[NU], f32x16 (&nxt)[NU]) {
       constexpr int PAR = decltype(par)::value;
       if (t + 2 < ntiles) load_k(key0 + (t + 2) * KTT, ra);
       load_v(key0 + (t + 1) * KTT, ra);
-      ZH_STAMP(0);
       if (active) {
         qk(PAR ^ 1, nxt);
-        softmax(t, cur[0], P[0], std::false_type{});
+        softmax(t, cur, P, std::false_type{});
         pv(PAR, P);
       }
       if (t + 2 < ntiles) store_k(PAR, ra);
       store_v(PAR ^ 1, ra);
-      ZH_STAMP(5);
       __syncthreads();
-      ZH_STAMP(6);
     };
     int t = 0;
     for (; t + 2 < ntiles; t += 2) {              // two tiles per trip: buffer indices and the S register sets are compile-time
@@ -477,14 +399,12 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
     }
     if (t + 1 < ntiles) {                         // two tiles left
       step(t, std::integral_constant<int, 0>{}, sA, sB);
-      if (active) { softmax(t + 1, sB[0], P[0], std::true_type{}); pv(1, P); }
+      if (active) { softmax(t + 1, sB, P, std::true_type{}); pv(1, P); }
     } else if (active) {                          // one tile left
-      softmax(t, sA[0], P[0], std::true_type{});
+      softmax(t, sA, P, std::true_type{});
       pv(0, P);
     }
-  } else
-#endif
-  {
+  } else {
   auto load_tile = [&](int kbase, TileRegs& r) { load_k(kbase, r); load_v(kbase, r); };
   auto store_tile = [&](int buf, const TileRegs& r) { store_k(buf, r); store_v(buf, r); };
   load_tile(key0, ra);
@@ -492,75 +412,34 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
   __syncthreads();
   auto compute = [&](int t) {
     if (active) {
-      f32x16 s[QT][NU];
-      PFrag P[QT];
+      f32x16 s[NU];
+      PFrag P;
       qk(t, s);
-      ZH_STAMP(1);
-#pragma unroll
-      for (int a = 0; a < QT; ++a) softmax(t, s[a], P[a], std::true_type{}, a);   // (a tile beyond Tq computes on a clamped query row and stores nothing)
+      softmax(t, s, P, std::true_type{});
       pv(t, P);
     }
   };
 
   // buffer (t+1)&1 was last read in iteration t-1 and every wave passed the barrier that ended it => free to overwrite
-#if ZH_ATTN_ABL & 8                                      // ablation: no tile traffic, no barriers
-  for (int t = 0; t < ntiles; ++t) compute(t & 1);
-#elif ZH_ATTN_ABL & 16                                   // ablation: tile traffic kept, barriers removed (racy: timing only)
-  for (int t = 0; t < ntiles; t += 2) {
-    if (t + 1 < ntiles) load_tile((t + 1) * KTT, ra);
-    compute(t);
-    if (t + 1 < ntiles) store_tile(1, ra);
-    if (t + 1 >= ntiles) break;
-    if (t + 2 < ntiles) load_tile((t + 2) * KTT, ra);
-    compute(t + 1);
-    if (t + 2 < ntiles) store_tile(0, ra);
-  }
-#elif ZH_ATTN_ABL & 32                                   // ablation: barriers kept, tile traffic removed
-  for (int t = 0; t < ntiles; ++t) { compute(t & 1); __syncthreads(); }
-#elif ZH_ATTN_ABL & 64                                   // ablation: global loads kept (consumed by a cheap op), no LDS stores
-  for (int t = 0; t < ntiles; ++t) {
-    if (t + 1 < ntiles) load_tile((t + 1) * KTT, ra);
-    compute(t & 1);
-    if (t + 1 < ntiles) m_run[0] += 1e-30f * (float)ra.k[0][0] * (float)ra.v[NLD - 1][7];
-    __syncthreads();
-  }
-#else
   for (int t = 0; t < ntiles; t += 2) {           // two tiles per trip: the LDS buffer index is a compile-time constant
     if (t + 1 < ntiles) load_tile(key0 + (t + 1) * KTT, ra);
-    ZH_STAMP(0);
     compute(t);
     if (t + 1 < ntiles) store_tile(1, ra);
-    ZH_STAMP(5);
     __syncthreads();
-    ZH_STAMP(6);
     if (t + 1 >= ntiles) break;
     if (t + 2 < ntiles) load_tile(key0 + (t + 2) * KTT, ra);
-    ZH_STAMP(0);
     compute(t + 1);
     if (t + 2 < ntiles) store_tile(0, ra);
-    ZH_STAMP(5);
     __syncthreads();
-    ZH_STAMP(6);
   }
-#endif
   }
-#ifdef ZH_ATTN_STAMP
-  if (p.stamp && lane == 0) {
-    long long* sp = p.stamp + ((long)id * NWAVE + wave) * 16;
-    const long long st_t1 = __builtin_amdgcn_s_memtime(), st_r1 = __builtin_amdgcn_s_memrealtime();
-    for (int i = 0; i < 7; ++i) sp[i] = st_acc[i];
-    sp[7] = st_t0 - st_e0;                               // prologue: block decode, Q fragments, first tile
-    sp[8] = st_t1 - st_t0; sp[9] = st_r1 - st_r0; sp[10] = ntiles; sp[11] = q0 < p.Tq;
-    sp[12] = st_re0; sp[13] = st_r1;                     // absolute 100-MHz times: kernel entry, end of the tile loop
-  }
-#endif
 
   // f16: every row of lacc holds the full row sum of this lane's query (the MFMA already summed both key halves);
-  // split pairs: this lane's half of the keys + the other half's (lane ^ 32)
-#pragma unroll
-  for (int a = 0; a < QT; ++a) {
-  const float l_row = X3 ? zh_xor32_sum(l_run[a]) : lacc[0];
-  const int qr = q0 + 32 * a + ql;
+  // split pairs: this lane's half of the keys + the other half's (lane ^ 32).  (The one-trip loop is the form this epilogue had when a
+  // wave could own two query tiles: written as straight-line code, hipcc rearranges the kernels' address arithmetic and register use.)
+  for (int once = 0; once < 1; ++once) {
+  const float l_row = X3 ? zh_xor32_sum(l_run) : lacc[0];
+  const int qr = q0 + ql;
   if (p.ksplit > 1) {                                   // partial result of this key chunk: unnormalised O, running max, row sum
     if (qr < p.Tq) {
       float* po = p.part_o + (((long)ks * (p.groups / p.H) + img) * p.Tq + qr) * ((long)p.H * DH) + hoff + 4 * hh;
@@ -568,10 +447,10 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
       for (int d = 0; d < NDT; ++d)
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-          *(f32x4*)(po + 32 * d + 8 * g) = (f32x4){oacc[a][d][4 * g], oacc[a][d][4 * g + 1], oacc[a][d][4 * g + 2], oacc[a][d][4 * g + 3]};
+          *(f32x4*)(po + 32 * d + 8 * g) = (f32x4){oacc[d][4 * g], oacc[d][4 * g + 1], oacc[d][4 * g + 2], oacc[d][4 * g + 3]};
       if (hh == 0) {
         const long mi = ((long)ks * p.groups + group) * p.Tq + qr;
-        p.part_m[mi] = m_run[a];
+        p.part_m[mi] = m_run;
         p.part_l[mi] = l_row;
       }
     }
@@ -584,17 +463,11 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
     for (int d = 0; d < NDT; ++d)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const f32x4 o = {oacc[a][d][4 * g] * inv, oacc[a][d][4 * g + 1] * inv, oacc[a][d][4 * g + 2] * inv, oacc[a][d][4 * g + 3] * inv};
+        const f32x4 o = {oacc[d][4 * g] * inv, oacc[d][4 * g + 1] * inv, oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv};
         zh_store_h4(op + 32 * d + 8 * g, p.planeO, o);
       }
   }
   }
-#ifdef ZH_ATTN_STAMP
-  if (p.stamp && lane == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    p.stamp[((long)id * NWAVE + wave) * 16 + 14] = __builtin_amdgcn_s_memrealtime();   // output stores done
-  }
-#endif
 }
 
 // Merge of the key-split partials: per (row = image * Tq + query, head), m = max_s m_s, w_s = 2^(m_s - m),
@@ -651,15 +524,9 @@ static int attention_launch(const void* Q, long ldq, long strideQ, const void* K
   // 128-query (4-wave) blocks: each K/V tile is shared four ways.  A 64-query (2-wave) variant was measured slower on
   // every shape of the model (encoder 301 vs 423 TF, cross-attention 230 vs 397 TF) and was dropped.
   const bool x3 = planeQ != 0;
-  // developer A/B (round 5): ZH_ATTN_QT=2 gives the split-pair dh = 64 kernel two 32-query tiles per wave (256 queries per workgroup)
-  static const int qt_env = [] { const char* e = getenv("ZH_ATTN_QT"); return e ? atoi(e) : 1; }();
-  const bool qt2 = qt_env == 2 && x3 && head_dim == 64 && !causal && ksplit <= 1;
-  p.nqb = zh_cdiv(Tq, qt2 ? 256 : 128);
+  p.nqb = zh_cdiv(Tq, 128);
   p.groups = heads * batch;
   p.ksplit = 1; p.kchunk = 0; p.part_o = p.part_m = p.part_l = nullptr;
-#ifdef ZH_ATTN_STAMP
-  p.stamp = g_attn_stamp;
-#endif
   if (ksplit > 1) {
     ZH_CHECK_ARG(!causal && ksplit <= 64, "zh_attention_f16_splitk: ksplit %d not in 1..64 (and not for the causal form)", ksplit);
     const int ktt = x3 ? 32 : 64;
@@ -681,10 +548,8 @@ static int attention_launch(const void* Q, long ldq, long strideQ, const void* K
   // cross-attention (dh = 96, two waves either way) 120.4 -> 103.7; SelfMask T = 5505 (264 workgroups) 240.1 -> 223.2; 518-px
   // encoder (864) 102.3 -> 98.7; 336-px encoder (1536) 76.5 -> 77.4; ViT-L/14 (20480) 1249 -> 1306.  So dh = 96 always takes it,
   // dh = 64 when the grid needs no more rounds of the chip at two workgroups per CU than at three.
-  bool pipe = x3 && (head_dim == 96 || zh_cdiv(nblk, 512L) <= zh_cdiv(nblk, 768L));
-  if (ZH_ATTN_PIPE >= 0) pipe = x3 && ZH_ATTN_PIPE;
-  if (qt2) hipLaunchKernelGGL((attn_f16_kernel<64, 4, 1, 0, 2>), grid, dim3(256), 0, stream, p);
-  else if (head_dim == 64) {
+  const bool pipe = x3 && (head_dim == 96 || zh_cdiv(nblk, 512L) <= zh_cdiv(nblk, 768L));
+  if (head_dim == 64) {
     if (x3 && pipe) hipLaunchKernelGGL((attn_f16_kernel<64, 4, 1, 1>), grid, dim3(256), 0, stream, p);
     else if (x3) hipLaunchKernelGGL((attn_f16_kernel<64, 4, 1, 0>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((attn_f16_kernel<64, 4, 0, 0>), grid, dim3(256), 0, stream, p);

@@ -1,5 +1,4 @@
 // zh_gemm_f16: fp16-operand / fp32-accumulate instantiations of the MFMA GEMM (kernel + design notes: gemm_kernel.h).
-#define ZH_GEMM_MAIN
 #include "gemm_kernel.h"
 
 // Instantiated (out type, activation) pairs = the ones the hot path uses; anything else is an argument error.
@@ -48,9 +47,6 @@ extern "C" int zh_gemm_f16(const void* A, long lda, long strideA, const void* W,
   // resident tiles share panels matters
   const GemmDevOverrides& dev = gemm_dev_overrides();
   p.group_m = dev.group_m;
-#ifdef ZH_GEMM_PROBE
-  p.probe = g_probe;
-#endif
   const int esz = out_f16 ? 2 : 4;
   p.vec_ok = (N % 4 == 0) && (ldc % 4 == 0) && (strideC % 4 == 0) && (((uintptr_t)C & (4 * esz - 1)) == 0) &&
              (!bias || ((uintptr_t)bias & 15) == 0) &&
@@ -70,7 +66,6 @@ extern "C" int zh_gemm_f16(const void* A, long lda, long strideA, const void* W,
   // blocks to work; measured 19.6 -> 16.5 us (K = 768) and 32.7 -> 28.8 us (K = 2048) with the residual epilogue, while
   // N = 1536 / 2048 keep 128 x 128 (tools/gemm_dec_tiles.py)
   else if (pick == 128 && t128 <= 256 && N <= 768) pick = 64;
-#ifndef ZH_F16_ROUND4_SMALL_TILES   // developer A/B (tools/build_variant_lib.sh): the one-round tiles as selected until round 5
   // Round 5: one-round tiles on 64-k slices (128-B row pieces) with several slices in flight (gemm_kernel.h K64 / gemm_k64_plain; the
   // finding of the split-pair tiles, tools/gemm_small_bench.py k64f): 64 x 64 on seven slots instead of eight 32-k ones (c_proj at one
   // image 18.6 -> 15.1 us, at 442 tokens 17.4 -> 13.7); 128 x 96 on five where it makes ONE round (the decoder's 3200 x 768 x 768
@@ -79,7 +74,6 @@ extern "C" int zh_gemm_f16(const void* A, long lda, long strideA, const void* W,
   if (pick == 3064) pick = 7032;
   else if ((pick == 64 || pick == 128) && N % 96 == 0 && (long)zh_cdiv(M, 128) * (N / 96) * batch <= 256) pick = 7096;
   else if (pick == 128 && t128 <= 256) pick = 7128;
-#endif
   const int forced = dev.tile ? dev.tile : (M <= 4096 ? dev.tile_small : 0);
   if (forced) {
     static const int known[] = {64, 128, 192, 256, 2064, 2128, 3064, 7032, 7096, 7128};

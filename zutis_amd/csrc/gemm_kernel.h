@@ -55,19 +55,7 @@ struct GemmArgs {
   const void* pos_y; const void* pos_x; long ld_pos; int pos_hw, pos_w, pos_f16;   // tables fp32, or fp16 (pos_f16)
   int M, N, K, act, nbm, nbn, vec_ok, group_m;
   int total;                     // tiles x batch items of the launch (the persistent big tiles walk them with stride gridDim.x)
-#ifdef ZH_GEMM_PROBE
-  long long* probe;   // developer build (tools/gemm_probe.py): 4 timestamps per block
-#endif
 };
-#ifdef ZH_GEMM_PROBE
-static long long* g_probe = nullptr;
-#ifdef ZH_GEMM_MAIN
-extern "C" void zh_gemm_set_probe(long long* p) { g_probe = p; }
-#endif
-#define ZH_PROBE(i) do { if (p.probe && tid == 0) { p.probe[(long)blockIdx.x * 8 + (i)] = wall_clock64(); p.probe[(long)blockIdx.x * 8 + 4 + (i)] = clock64(); } } while (0)
-#else
-#define ZH_PROBE(i)
-#endif
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* glb_ptr_t;
@@ -170,7 +158,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform values live in SGPRs
   const int wr = wave / WN, wc = wave % WN;
-  ZH_PROBE(0);
 
   // XCD-aware bijective remap: blocks b, b+8, ... share an XCD -> give each XCD a contiguous id range.  `vb` is the virtual block
   // id: blockIdx.x for one workgroup per tile; blockIdx.x + i * gridDim.x for the i-th tile of a persistent workgroup (gridDim.x is
@@ -189,11 +176,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
     const int gfirst = gid * p.group_m;
     const int grows = min(p.nbm - gfirst, p.group_m);
     const int gl = trem - gid * gsz;
-#ifdef ZH_X_WALK_N                                      // developer A/B: consecutive ids walk the n-tiles of one m-tile
-    tm_ = gfirst + gl / p.nbn; tn_ = gl % p.nbn;
-#else
     tm_ = gfirst + gl % grows; tn_ = gl / grows;
-#endif
   };
   int vb = blockIdx.x;
   int batch, tm, tn;
@@ -393,16 +376,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
   for (;;) {                                  // tiles of this workgroup: one, or (PERS) vb, vb + gridDim.x, ...
   const int vb_next = vb + (int)gridDim.x;
   const bool more = PERS && vb_next < p.total;
-#ifdef ZH_ABL_TAIL_SPLIT      // developer ablation (timing only, results are garbage; round 6): what an IDEAL stream-K / fixed-split tail round could
-  // return — the `rem` tiles of the last, partial round of a persistent launch run rem / gridDim.x of their K slices each, i.e. the round
-  // lasts as long as if its work were spread evenly over every workgroup, with no reduction traffic at all
-  int nk_tile = nk;
-  if (PERS && (int)gridDim.x < p.total) {
-    const int rem = p.total % (int)gridDim.x;
-    if (rem && vb >= p.total - rem) nk_tile = max(2 * DIST, ((nk * rem / (int)gridDim.x) + 1) & ~1);
-  }
-#define nk nk_tile
-#endif
 
   constexpr bool BIGT = SPLIT && BM * BN >= 192 * 256;    // the two-slot (SPLIT = 2: three-slot) big tiles
   static_assert(!SPLIT || K64 || BIGT == (STAGES == 2 || (SPLIT == 2 && STAGES == 3 && BM * BN >= 192 * 256)), "big split-pair tiles: 2 slots (x2: 2 or 3)");
@@ -438,7 +411,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
     if (nk > 1) issue_part(PIECES, i0_t{}, iN_t{});
     if (nk > 2) issue_part(2 * PIECES, i0_t{}, iH_t{});
     pos_after_prologue();
-    ZH_PROBE(1);
     half8_t fa[2][2 * TM], fw[2][NPLW * TN];
     const int lofs0 = foff + ((fk ^ sz) * 8), lofs1 = foff + (((4 | fk) ^ sz) * 8);   // lane offsets (halves) inside a subtile's two pieces, k-steps 0 / 1
     int st = 0;                                                // ring start (piece) of slice kt
@@ -489,7 +461,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
     for (int s = 0; s < KD; ++s)
       if (s < nk) issue_stage(s);
     pos_after_prologue();
-    ZH_PROBE(1);
     half8_t fa[2][NPL * TM], fw[2][NPLW * TN];
     int slot = 0, wslot = KD % STAGES;
     auto read_frags = [&]() {
@@ -542,7 +513,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
     }
   } else if constexpr (BIGT) {
     // ---- f16x3 loop, big tile (256 x 256, 8 waves of 128 x 64), TWO 64-KiB slots.  Ablations of the 3-slot 256 x 128 loop
-    // (tools/gemm_x3_probe.sh, round 3; QKV shape, model-shaped operands): all 160 us; MFMAs removed 116 us; operand
+    // (profiles/NOTES.md round 3; QKV shape, model-shaped operands): all 160 us; MFMAs removed 116 us; operand
     // movement removed (no DMA, no fragment reads) 119 us — the LDS-DMA stream (48 KiB per slice and CU, at its request-rate
     // limit) is as long a leg as the MFMAs, and the two overlap poorly.  A 256 x 256 tile moves 64 KiB per slice for TWICE
     // the MFMAs (-33 % bytes and -25 % fragment reads per MFMA).  Its ring has room for two slots only, but a slice now
@@ -557,7 +528,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       // wave-uniform by construction; readfirstlane makes it so for the compiler too (the "s" constraint below was handed a
-      // VGPR pair — an assembler error — in the -DZH_GEMM_PROBE build, where its uniformity analysis gave up)
+      // VGPR pair — an assembler error — in an instrumented build, where its uniformity analysis gave up)
       const uintptr_t gb = (uintptr_t)gbase[i];
       sbase[i] = (const half_t*)(((uintptr_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(gb >> 32)) << 32) |
                                  (uintptr_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)gb));
@@ -581,7 +552,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
     if constexpr (STAGES == 3) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), expcnt / lgkmcnt untouched
     issue2(0);
     pos_after_prologue();
-    ZH_PROBE(1);
     // Registers: 128 accumulators + A hi (32) + W hi (16) + W lo (16); a fourth fragment set does not fit (the build fails on
     // scratch).  The A lo fragments therefore REPLACE the A hi ones: the second sweep walks the A fragments in order and, as
     // soon as fragment mt has fed its TN MFMAs, its lo plane is read into the same registers — TM - 1 groups of MFMAs ahead
@@ -610,18 +580,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
     // `inflight` = whole stages that may still be in flight at the barrier (0: two slots, 1: the steady state of three)
     auto body = [&](int slot, int nslot, bool prefetch, auto inflight) {
       const int so = slot * STAGE_HALVES;
-#ifndef ZH_X3_NOBAR
       // lgkmcnt(0) too: hipcc moves the last MFMAs of the previous slice (register-only) below this point and with them the
       // wait for the fragment reads they consume — every read of the slot the DMA below overwrites must have RETURNED first
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(decltype(inflight)::value * NP) : "memory");
-#endif
-#ifndef ZH_X3_NOFRAG
       read_hi(slot);
-#endif
-#ifndef ZH_X3_NODMA
       if (prefetch) issue2(nslot);
-#endif
-#ifndef ZH_X3_NOMFMA
 #pragma unroll
       for (int nt = 0; nt < TN; ++nt)                  // hi_w * hi_a
 #pragma unroll
@@ -633,9 +596,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
 #pragma unroll
           for (int nt = 0; nt < TN; ++nt)
             acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[TN + nt], fa[mt], acc[nt][mt], 0, 0, 0);
-#ifndef ZH_X3_NOFRAG
           fa[mt] = *(const half8_t*)(rdA + so + (BM + mt * 16) * BK);
-#endif
         }
 #pragma unroll
         for (int mt = 0; mt < TM; ++mt)                  // hi_w * lo_a
@@ -647,10 +608,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
         // the W lo fragments would take), requested with the hi fragments and landing under the hi * hi sweep; the second half
         // replaces the first hi fragments as soon as that sweep has issued and lands under the first half's MFMAs.  (Left to
         // itself hipcc fused the sweeps per A fragment — 2 reads, wait, 8 MFMAs, 8 times per slice: every LDS latency exposed.)
-#ifndef ZH_X3_NOFRAG
 #pragma unroll
         for (int t = 0; t < H2; ++t) fa[t] = *(const half8_t*)(rdA + so + (BM + (H1 + t) * 16) * BK);
-#endif
 #pragma unroll
         for (int mt = 0; mt < H1; ++mt)                // hi_w * lo_a, rows of the first half
 #pragma unroll
@@ -662,13 +621,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
           for (int nt = 0; nt < TN; ++nt)
             acc[nt][H1 + mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[nt], fa[mt], acc[nt][H1 + mt], 0, 0, 0);
       }
-#else
-      acc[0][0] += (f32x4){(float)fa[0][0], (float)fw[0][1], (float)fa[TM - 1][2], (float)fw[(NPLW - 1) * TN][3]};
-#endif
     };
-#ifdef ZH_X3_NOFRAG
-    read_hi(0);
-#endif
     typedef std::integral_constant<int, 0> fl0_t;
     typedef std::integral_constant<int, 1> fl1_t;
     if constexpr (STAGES == 2) {
@@ -710,7 +663,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
     for (int s = 0; s < DISTX; ++s)
       if (s < nk) issue_stage(s);
     pos_after_prologue();
-    ZH_PROBE(1);
     half8_t fa[2 * TM], fw[NPLW * TN];
     int slot = 0, wslot = DISTX % STAGES;
     auto read_frags = [&]() {
@@ -742,29 +694,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
       wslot = wslot + 1 == STAGES ? 0 : wslot + 1;
     };
     int kt = 0;
-#ifdef ZH_X3_NOFRAG                      // developer ablations (tools/gemm_x3_probe.sh): timing only, results are garbage
-    read_frags();
-#endif
     for (; kt + DISTX < nk; ++kt) {      // steady: branch-free body so the reads / DMA issues interleave with the MFMAs
-#ifndef ZH_X3_NOBAR
       wait_vmcnt_barrier<AHEADX * NP>();
-#endif
-#ifdef ZH_X3_DMA_FIRST                   // developer A/B (round 4): the next slice's DMA in front of this slice's fragment reads
-      issue_stage(wslot);
       read_frags();
-#else
-#ifndef ZH_X3_NOFRAG
-      read_frags();
-#endif
-#ifndef ZH_X3_NODMA
       issue_stage(wslot);
-#endif
-#endif
-#ifndef ZH_X3_NOMFMA
       sweeps();
-#else
-      acc[0][0] += (f32x4){(float)fa[0][0], (float)fw[0][1], (float)fa[TM][2], (float)fw[(NPLW - 1) * TN][3]};
-#endif
       // hi fragments first, then 2 MFMAs per lo-fragment read / DMA issue
       __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
 #pragma unroll
@@ -822,18 +756,12 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
   // LDS fragment read or one LDS-DMA issue of the NEXT slices; the wave's stream stays MFMA-paced instead of
   // front-loading 16 memory instructions behind the barrier.
   auto steady = [&](int kt, half8_t (&fa)[TM], half8_t (&fw)[TN], half8_t (&na)[TM], half8_t (&nw)[TN]) {
-#ifndef ZH_X_NOBAR
     wait_vmcnt_barrier<AHEAD * NP>();
-#endif
     // program order = dependence order for the compiler: an LDS-DMA is a write to `smem`, so fragment reads placed after
     // it can never be scheduled above it.  Reads first, DMA second lets the reads spread under the first MFMAs and the DMA
     // issues under the last ones (the other order left all 12 ds_read_b128 + their latency exposed at the end of the slice).
-#ifndef ZH_X_NOFRAG
     load_frags(kt + 1, na, nw);
-#endif
-#ifndef ZH_X_NODMA
     issue_stage((kt + DIST) % STAGES);
-#endif
     mfma_all(fa, fw);
     constexpr int NMEM = TM + TN + NP, NMFMA = TM * TN;
     if (NMFMA >= NMEM) {
@@ -860,7 +788,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
   };
   if (nk >= DIST) wait_vmcnt_barrier<(DIST - 1) * NP>();   // stage 0 landed; the other DIST-1 may still be in flight
   else wait_vmcnt_barrier<0>();                            // short K: not worth a counted wait
-  ZH_PROBE(1);
   load_frags(0, fa0, fw0);
   int kt = 0;
   for (; kt + DIST + 1 < nk; kt += 2) {
@@ -873,10 +800,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
   }
   }
 
-#ifdef ZH_ABL_TAIL_SPLIT
-#undef nk
-#endif
-  ZH_PROBE(2);
   // ---- epilogue: lane owns rows m = ..+(lane&15), 4 consecutive n at 4*(lane>>4).  ACT / VEC are template
   // parameters: a runtime switch unrolled 32x blew the instruction cache (fc GEMM 1.4x slower in the model).
   // PERS: the epilogue sits inside the tile loop, and everything in it that depends on the lane alone is loop-invariant — hoisted in
@@ -947,9 +870,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
     char* slab = (char*)smem + SLAB_OFF + wave * (PR * RS);
 #pragma clang loop unroll(full)
     for (int pass = 0; pass < TM / MTP; ++pass) {
-#ifdef ZH_ABL_SKIP_EPI        // developer ablation (timing only, results are garbage): a persistent tile that has a successor skips its slab passes and stores
-      if (more) break;
-#endif
 #pragma clang loop unroll(full)
       for (int nt = 0; nt < TN; ++nt) {
         const f32x4 bv = bvs[nt];
@@ -970,7 +890,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
       }
       if constexpr (OUT == 2) {
         // split pair: a lane takes 8 consecutive columns — one 16-byte store per plane instead of two 8-byte ones (the epilogue
-        // of a 256 x 256 tile was 7.9 us of a 29.6-us K = 256 block, store-issue bound: tools/gemm_x3_stamp.py)
+        // of a 256 x 256 tile was 7.9 us of a 29.6-us K = 256 block, store-issue bound: profiles/r03_gemm_x3_stamp.txt)
         constexpr int UPR = CPRW / 2, NIT2 = PR * UPR / 64;
         static_assert(CPRW % 2 == 0 && (PR * UPR) % 64 == 0, "split-pair epilogue: 8-column units must tile the pass");
         // the residual (row-periodic table) of the whole pass is requested FIRST, branch-free (clamped addresses), so its loads
@@ -1004,7 +924,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
         // fp32 output + residual (out_proj, c_proj, the decoder's output projections): the loop used to load each residual
         // chunk right where it is added — read slab, ~30 address instructions (an integer modulo among them), ONE load, wait, add,
         // store — 24 exposed memory latencies per lane in a row: that, not bandwidth, was the 13-us epilogue of a 54-us out_proj
-        // block (tools/gemm_x3_stamp.py).  Now the pass's residual chunks are requested together, branch-free, before the slab is
+        // block (in-kernel stamps, profiles/NOTES.md).  Now the pass's residual chunks are requested together, branch-free, before the slab is
         // read, and `m % res_rows` is skipped when the residual has a row of its own for every output row.
         f32x4 rv[NIT];
         if (OUT == 0 && R) {
@@ -1029,9 +949,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
           const int m = m0 + wr * TM * 16 + pass * PR + row;
           const int n = n0 + wc * TN * 16 + ch * (16 / ESZ);
           f32x4 d = *(const f32x4*)(slab + row * RS + ch * 16);
-#ifdef ZH_ABL_SKIP_EPI_STORES  // developer ablation (timing only; round 6): the slab passes stay, the GLOBAL stores of a persistent tile that has a successor
-          if (more) { asm volatile("" :: "v"(d)); continue; }        // go — the most that moving the stores to other waves (wave-specialised roles) could hide
-#endif
           if (m < p.M && n < p.N) {
             // f32 output: the slab holds fp32, the residual joins before the store
             if (BIAS_LATE) d += bias_late;
@@ -1104,10 +1021,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
 #pragma unroll
     for (int j = 0; j < TM; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
-#ifdef ZH_GEMM_PROBE
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  ZH_PROBE(3);
-#endif
 }
 
 

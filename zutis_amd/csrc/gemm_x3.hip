@@ -16,9 +16,6 @@
 #ifndef ZH_SKINNY_MAX_BLOCKS
 #define ZH_SKINNY_MAX_BLOCKS 512
 #endif
-#ifdef ZH_GEMM_PROBE
-extern "C" void zh_gemm_x3_set_probe(long long* p) { g_probe = p; }   // developer build (tools/gemm_x3_stamp.py)
-#endif
 
 template <int WM, int WN, int TM, int TN, int STAGES, int VEC, int SP = 1>
 static bool launch_x3(const GemmArgs& p, int batch, int out_kind, hipStream_t stream) {
@@ -80,9 +77,6 @@ extern "C" int zh_gemm_f16x3(const void* A, long lda, long strideA, long planeA,
   p.pos_y = pos_y; p.pos_x = pos_x; p.ld_pos = ld_pos; p.pos_hw = pos_h * pos_w; p.pos_w = pos_w; p.pos_f16 = pos_f16;
   p.M = M; p.N = N; p.K = K; p.act = act; p.nbm = p.nbn = 0;
   p.group_m = gemm_dev_overrides().group_m;
-#ifdef ZH_GEMM_PROBE
-  p.probe = g_probe;
-#endif
   const int esz = out_kind == 0 ? 4 : 2;
   p.vec_ok = (N % 4 == 0) && (ldc % 4 == 0) && (strideC % 4 == 0) && (((uintptr_t)C & (4 * esz - 1)) == 0) &&
              (!bias || ((uintptr_t)bias & 15) == 0) &&
@@ -96,7 +90,7 @@ extern "C" int zh_gemm_f16x3(const void* A, long lda, long strideA, long planeA,
   // 1.73 rounds of the chip instead of 1.31) or 128 x 64 (4 waves, two blocks per CU) for small problems
   // ... or, for M >= 4096 rows, the two-slot big tiles (8 waves, 2 x 4): 256 x 256 (waves of 128 x 64, 64 KiB per K slice) and
   // 192 x 256 (waves of 96 x 64, 56 KiB) — a third fewer staged bytes per MFMA than 256 x 128, which is what bounds the 3-slot
-  // loop (tools/gemm_x3_probe.sh).  256 x 256 serves the wide GEMMs (QKV, c_fc, the K / V projections); 192 x 256 turns the
+  // loop (profiles/NOTES.md round 3).  256 x 256 serves the wide GEMMs (QKV, c_fc, the K / V projections); 192 x 256 turns the
   // N = 768 ones (out_proj, c_proj) into ONE round of 222 tiles where 192 x 128 needs two rounds of 444.
   // (Measured and not kept, round 3: a 128 x 128 two-slot tile at TWO blocks per CU, so that one block's epilogue overlaps the
   //  other's K loop — K / V 514 us against 454 for 256 x 256: the extra staged bytes per MFMA cost more than the overlap gives;
@@ -159,11 +153,7 @@ extern "C" int zh_gemm_f16x3(const void* A, long lda, long strideA, long planeA,
   // The 128 x 96 / 128 x 128 tiles of the one-image QKV / c_fc stage 56 / 64 KiB per 64-k slice: two slots, one slice in flight — a tie
   // with their 32-k forms (6496); fetching their A lo fragments straight into registers to make room (40 / 48 KiB slots) was slower
   // (QKV 24.4 -> 26.4 us: the duplicate requests of the waves that share rows cost the request rate more than the deeper ring returns).
-#ifndef ZH_X3_ROUND4_SMALL_TILES   // developer A/B (tools/build_variant_lib.sh): the one-round tiles as selected until round 5
   if (pick == 64 && (long)zh_cdiv(M, 128) * zh_cdiv(N, 64) * batch <= 256) pick = 6464;
-#else
-  if (pick == 3064) pick = 3066;
-#endif
   const int forced = gemm_dev_overrides().tile;
   if (forced == 64 || forced == 96 || forced == 192 || forced == 256 || forced == 512 || forced == 448 || forced == 3064) pick = forced;
   // M ~ 1200 rows (one image at native resolution: c_fc 1201 x 3072, the split-K planes of c_proj / out_proj): 128 x 64 tiles are 480
@@ -181,13 +171,11 @@ extern "C" int zh_gemm_f16x3(const void* A, long lda, long strideA, long planeA,
   // of slice kt + 2 — refills what slice kt - 1 left, 48 .. 104 KiB ahead of the reads instead of the 56 of two slots.  QKV at one image
   // 23.5 -> 21.8 us, the decoder's 3200 x 768 x 768 21.1 -> 20.8 (r05_gemm_k64_deep.txt; 128 x 128: c_fc 28.9 -> 27.5, c_proj planes 27.6 -> 26.5):
   // the pieces that go out ONE step ahead (an eighth of a 128 x 96 slice, half of a 128 x 128 one) still wait out their latency.
-#ifndef ZH_X3_ROUND4_SMALL_TILES
   if (!forced && !x2 && !pos_y) {
     if (pick == 96) pick = 7096;
     // (7128, the 128 x 128 tile on the same circle: half of every slice still goes out one step ahead — c_fc 28.9 -> 27.5 us back to
     //  back, but 26.5 -> 26.4 per launch inside one image's dependent chain (r05_c3_launch_list.txt): developer code, not selected)
   }
-#endif
   if ((forced == 5122 || forced == 5124 || forced == 4484) && x2) pick = forced;   // developer A/B: the x2 256 x 256 tile on TWO slots (2 x 4 waves of 128 x 64) / on three as 2 x 4 waves of 128 x 64
   // the two-slot tiles address operand rows as SGPR base + 32-bit per-lane BYTE offset
   if ((pick == 512 || pick == 448 || pick == 5122 || pick == 5124 || pick == 4484) && ((long)(M - 1) * lda + K > 0x7FFFFFFFL || (long)(N - 1) * ldw + K > 0x7FFFFFFFL)) pick = 256;

@@ -642,11 +642,6 @@ struct FusedRleArgs {
   unsigned char* out; long out_cap; int* cursor; int* info;
 };
 #define FRLE_ROWS 16                                         // rows per chunk (= counts per (chunk, column) fit the 5-plane counter)
-#ifdef ZH_FRLE_STAMP   // developer build (tools/rle_fused_stamp.py): thread 0's 100-MHz clock at the phase boundaries, in the LAST 64 B x slot of `out`
-#define FRLE_STAMP(i) do { if (tid == 0) ((long long*)(a.out + a.out_cap - 64L * (mi + 1)))[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define FRLE_STAMP(i) do { } while (0)
-#endif
 __device__ __forceinline__ unsigned rle_bits4(unsigned w) {  // bit k = byte k of w is non-zero
   const unsigned nz = zh_nz_bytes(w);
   return (nz & 1u) | ((nz >> 7) & 2u) | ((nz >> 14) & 4u) | ((nz >> 21) & 8u);
@@ -674,7 +669,6 @@ __global__ __launch_bounds__(1024) void mask_rle_fused_kernel(FusedRleArgs a) {
   if (mi % a.Q >= a.count[mi / a.Q]) return;                // whole workgroup, before any barrier
   const int H = a.H, W = a.W;
   const long HW = (long)H * W;
-  FRLE_STAMP(0);
   const long mask_index = (long)(mi / a.Q) * a.Q + a.sel[mi];
   const FrleLayout L = frle_layout(H, W, a.max_runs);
   unsigned long long* Bw = (unsigned long long*)dyn;
@@ -708,7 +702,6 @@ __global__ __launch_bounds__(1024) void mask_rle_fused_kernel(FusedRleArgs a) {
   }
   for (int i = tid; i < L.S * L.Wp / 2; i += nthr) ((unsigned*)part)[i] = 0;
   __syncthreads();
-  FRLE_STAMP(1);
   // 32 columns of row y, from column 32 p on (bits past the row's end are 0)
   auto rowword = [&](int y, int p) -> unsigned {
     const long f0 = (long)y * W + 32L * p;
@@ -782,7 +775,6 @@ __global__ __launch_bounds__(1024) void mask_rle_fused_kernel(FusedRleArgs a) {
   }
   if (lane == 0) { s_red[0][wave] = area; s_red[1][wave] = miny; s_red[2][wave] = maxy; s_red[3][wave] = minx; s_red[4][wave] = maxx; }
   __syncthreads();
-  FRLE_STAMP(2);
   // ---- per column: exclusive prefix over the chunks (in place), then a block scan of the column totals -> coloff
   int ctot = 0;
   if (tid < L.Wp) {
@@ -808,7 +800,6 @@ __global__ __launch_bounds__(1024) void mask_rle_fused_kernel(FusedRleArgs a) {
   }
   const int lead = (int)(B32[0] & 1u), nc = nt + 1 + lead;
   __syncthreads();
-  FRLE_STAMP(3);
   // ---- pass 2: the same threads write their transitions to their places in the list, column by column
   for (int it = tid; it < nitems; it += nthr) {
     const int p = it % L.P, sc = it / L.P, y0 = sc * FRLE_ROWS;
@@ -842,7 +833,6 @@ __global__ __launch_bounds__(1024) void mask_rle_fused_kernel(FusedRleArgs a) {
     }
   }
   __syncthreads();
-  FRLE_STAMP(4);
   // ---- the string (see mask_rle_kernel) into LDS, over the dead bits / counts
   unsigned char* cbuf = dyn;
   auto run = [&](int k) -> long {
@@ -887,11 +877,9 @@ __global__ __launch_bounds__(1024) void mask_rle_fused_kernel(FusedRleArgs a) {
     s_off = fits ? off : -1;
   }
   __syncthreads();
-  FRLE_STAMP(5);
   if (s_off < 0) return;
   unsigned char* o = a.out + s_off;
   for (int i = tid; i < base; i += nthr) o[i] = cbuf[i];
-  FRLE_STAMP(6);
 }
 static size_t rle_fused_lds(int H, int W, int max_runs) { return frle_layout(H, W, max_runs).total; }
 extern "C" int zh_mask_rle_fused_supported(int H, int W, int max_runs) {

@@ -558,8 +558,7 @@ extern "C" int zh_upsample_argmax(const float* logits_lo, long long* labels, int
   const size_t lds = (size_t)UA_CH * wr * (wc + UA_TW) * sizeof(float);
   const long tiles = (long)B * zh_cdiv(W, UA_TW) * zh_cdiv(H, UA_TH);
   const size_t lds_pk = (size_t)UA_CHP * wr * (wc + UA_TW) * sizeof(float);
-  static const bool pk_off = [] { const char* e = getenv("ZH_UPSAMPLE_ARGMAX_PK"); return e && atoi(e) == 0; }();   // developer A/B: 0 = the round-2 kernel
-  if (!pk_off && wr * wc <= 64 && lds_pk <= 48 * 1024 && tiles < (1L << 31)) {   // a window of <= 64 low-res pixels (upsampling by >= ~6x at 32 x 32 tiles)
+  if (wr * wc <= 64 && lds_pk <= 48 * 1024 && tiles < (1L << 31)) {   // a window of <= 64 low-res pixels (upsampling by >= ~6x at 32 x 32 tiles)
     const int tiles_y = zh_cdiv(H, UA_TH), tiles_x = zh_cdiv(W, UA_TW);
     hipLaunchKernelGGL(upsample_argmax_pk_kernel, dim3((unsigned)tiles), dim3(256), lds_pk, stream, logits_lo, labels,
                        n, h, w, H, W, scale_h, scale_w, tiles_x, tiles_y, wr, wc);
