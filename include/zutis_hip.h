@@ -364,7 +364,7 @@ int zh_mask_rle_fused_kept(const unsigned char* masks, const unsigned long long*
  * one call.  proposals f32 [B, L, Q, h, w] in [0, 1]; gt_u8 [n_tot, H, W] (non-zero = in the mask): image b's instances are rows
  * inst_off[b] .. inst_off[b+1]-1 (inst_off int32 [B+1], device); n_max = max instances of an image.  Outputs: costs f32 — image b's
  * [L, n_b, Q] block at offset L * inst_off[b] * Q — = weight_dice * dice + weight_bce * bce with
- *   dice = 1 - (2 sum(g p) + 1) / (sum p + sum g + 1),  bce = -(sum B + sum g (A - B)) / (H W),  A = max(log p, -100), B = max(log(1-p), -100);
+ *   dice = 1 - (2 sum(g p) + 1) / (sum p + sum g + 1),  bce = -sum (g ? A : B) / (H W),  A = max(log p, -100), B = max(log(1-p), -100);
  * stat_p f32 [B, L, Q] (sum p), stat_pg (sum g p, the layout of costs), stat_g f32 [n_tot] (sum g) for zh_mask_match_grad;
  * skip int32 [B] = 1 where an image's GT masks sum to 0 (criterion.py:116-118); ZH_STATUS_RANGE OR-ed into *status when a proposal
  * is outside [0, 1] or NaN (the asserts of criterion.py:71-72).  workspace >= zh_mask_match_cost_workspace_size. */

@@ -116,3 +116,153 @@ def unique_margin(cm: np.ndarray) -> float:
         r2, c2 = linear_sum_assignment(alt)
         gap = min(gap, alt[r2, c2].sum() - best)
     return float(gap)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Kernel-level float64 oracles: one per entry point of csrc/criterion.hip, on the kernels' own fp32 sample weights and positions
+# (oracle.resample.linear_index_weights, the fma included).  Every full-resolution proposal value is the fp32 value the kernels
+# interpolate (bilinear_nchw's arithmetic), taken to float64 only afterwards: at saturation the BCE gradient
+# (p - g) / max(p (1 - p), 1e-12) is defined by that fp32 value alone.
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+def lin_matrix(n_in: int, n_out: int, device="cpu") -> torch.Tensor:
+    """[n_out, n_in] float64 matrix of the kernels' bilinear weights along one axis (linear_index_weights)."""
+    from oracle.resample import linear_index_weights
+    i0, i1, l0, l1 = linear_index_weights(n_in, n_out)
+    M = np.zeros((n_out, n_in), np.float64)
+    np.add.at(M, (np.arange(n_out), i0), l0.astype(np.float64))
+    np.add.at(M, (np.arange(n_out), i1), l1.astype(np.float64))
+    return torch.from_numpy(M).to(device)
+
+
+def adjoint(G: torch.Tensor, My: torch.Tensor, Mx: torch.Tensor) -> torch.Tensor:
+    """[..., H, W] -> [..., h, w]: the adjoint of the bilinear upsample, My^T G Mx."""
+    return My.T @ G @ Mx
+
+
+def _fma(a, b, c):
+    # oracle.resample.fma on torch tensors: the product of two fp32 values is exact in float64
+    return (a.double() * b.double() + c.double()).float()
+
+
+def up_f32(x: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """[..., h, w] fp32 -> [..., H, W] fp32 with the arithmetic of oracle.resample.bilinear_nchw (pinned bitwise to it by
+    tests/test_criterion_cpu.py), on the tensor's device."""
+    from oracle.resample import linear_index_weights
+    dev = x.device
+    y0, y1, ly0, ly1 = (torch.from_numpy(a).to(dev) for a in linear_index_weights(x.shape[-2], H))
+    x0, x1, lx0, lx1 = (torch.from_numpy(a).to(dev) for a in linear_index_weights(x.shape[-1], W))
+    x = x.to(torch.float32)
+    top, bot = x[..., y0, :], x[..., y1, :]
+    r0 = _fma(top[..., x0], lx0, top[..., x1] * lx1)
+    r1 = _fma(bot[..., x0], lx0, bot[..., x1] * lx1)
+    return _fma(r0, ly0[:, None], r1 * ly1[:, None])
+
+
+def match_terms(p: torch.Tensor, g: torch.Tensor, wd: float = 1.0, wb: float = 1.0):
+    """Full resolution, float64: p [Q, HW] in [0, 1], g [n, HW] binary -> (cost [n, Q], sum p [Q], sum g.p [n, Q], sum g [n]).
+    cost = wd * dice + wb * mean BCE with torch's -100 log clamp, each pixel's loss taken whole (g ? log p : log(1 - p))."""
+    HW = p.shape[-1]
+    sp, sg, spg = p.sum(-1), g.sum(-1), g @ p.T
+    A = torch.clamp(torch.log(p), min=-100.0)
+    Bv = torch.clamp(torch.log(1.0 - p), min=-100.0)
+    dice = 1.0 - (2.0 * spg + 1.0) / (sp[None, :] + sg[:, None] + 1.0)
+    bce = -(g @ A.T + (1.0 - g) @ Bv.T) / HW
+    return wd * dice + wb * bce, sp, spg, sg
+
+
+BCE_EPS = float(np.float32(1e-12))
+
+
+def match_grad(p: torch.Tensor, g: torch.Tensor, rows, cols, wd: float = 1.0, wb: float = 1.0) -> torch.Tensor:
+    """Full resolution, float64: d/dp of sum over the pairs (instance rows[k], query cols[k]) of match_terms' cost -> [Q, HW].
+    The BCE part is torch's binary_cross_entropy_backward, (p - g) / max(p (1 - p), eps) / HW (the -100 log clamp does not enter),
+    with torch's eps, the fp32 value of 1e-12 (as the kernel's 1e-12f), in every dtype."""
+    HW = p.shape[-1]
+    out = torch.zeros_like(p)
+    sp, sg = p.sum(-1), g.sum(-1)
+    for i, q in zip(rows, cols):
+        gi, pq = g[i], p[q]
+        D = sp[q] + sg[i] + 1.0
+        N = 2.0 * (gi @ pq) + 1.0
+        out[q] += wd * (N - 2.0 * gi * D) / (D * D) + wb * (pq - gi) / torch.clamp((1.0 - pq) * pq, min=BCE_EPS) / HW
+    return out
+
+
+def mask_cost_ref(props: torch.Tensor, gts, wd: float = 1.0, wb: float = 1.0):
+    """zh_mask_match_cost in float64.  props fp32 [B, L, Q, h, w]; gts list of [n_b, H, W] -> dict(costs {b: [L, n_b, Q]},
+    stat_p [B, L, Q], stat_pg {b: [L, n_b, Q]}, stat_g [n_tot], skip [B] bool (an image whose masks are all empty))."""
+    B, L, Q = props.shape[:3]
+    H, W = gts[0].shape[-2:]
+    dev = props.device
+    stat_p = torch.zeros(B, L, Q, dtype=torch.float64, device=dev)
+    costs, stat_pg, stat_g, skip = {}, {}, [], []
+    for b in range(B):
+        g = gts[b].to(dev).flatten(1).ne(0).to(torch.float64)
+        stat_g.append(g.sum(-1))
+        skip.append(bool(g.sum() == 0))
+        cs, pgs = [], []
+        for l in range(L):
+            p = up_f32(props[b, l], H, W).reshape(Q, -1).double()
+            c, sp, spg, _ = match_terms(p, g, wd, wb)
+            stat_p[b, l] = sp
+            cs.append(c)
+            pgs.append(spg)
+        costs[b], stat_pg[b] = torch.stack(cs), torch.stack(pgs)
+    return {"costs": costs, "stat_p": stat_p, "stat_pg": stat_pg, "stat_g": torch.cat(stat_g), "skip": skip}
+
+
+def mask_grad_ref(props: torch.Tensor, gts, pairs, wd: float = 1.0, wb: float = 1.0, scale: float = 1.0) -> torch.Tensor:
+    """zh_mask_match_grad in float64: pairs (b, l, q, i) -> scale * d/dprops of the sum of their costs, [B, L, Q, h, w]
+    (0 outside the paired planes)."""
+    B, L, Q, h, w = props.shape
+    H, W = gts[0].shape[-2:]
+    dev = props.device
+    My, Mx = lin_matrix(h, H, dev), lin_matrix(w, W, dev)
+    out = torch.zeros(B, L, Q, h, w, dtype=torch.float64, device=dev)
+    by = {}
+    for b, l, q, i in pairs:
+        by.setdefault((int(b), int(l)), []).append((int(i), int(q)))
+    for (b, l), iq in by.items():
+        g = gts[b].to(dev).flatten(1).ne(0).to(torch.float64)
+        p = up_f32(props[b, l], H, W).reshape(Q, -1).double()
+        rows, cols = zip(*iq)
+        G = match_grad(p, g, rows, cols, wd, wb).reshape(Q, H, W)
+        out[b, l] = adjoint(G, My, Mx) * scale
+    return out
+
+
+def ce_ref(logits_lo: torch.Tensor, labels: torch.Tensor, ignore_index: int = 255, grad_out: float = 1.0):
+    """zh_upsample_ce_fwd / _bwd in float64.  logits_lo [B, n_cat, h, w]; labels int [B, H, W] -> dict(lse [B, H, W], mean, count,
+    dlogits [B, n_cat, h, w] = d (grad_out * mean) / d logits_lo).  A label is used when it is not ignore_index and lies in
+    [0, n_cat) (the kernels flag any other one and skip it); with no such label the mean is NaN and the count 0 (torch's mean over
+    an empty set) and dlogits is 0."""
+    B, n, h, w = logits_lo.shape
+    H, W = labels.shape[-2:]
+    dev = logits_lo.device
+    Ty, Tx = lin_matrix(h, H, dev), lin_matrix(w, W, dev)
+    lab = labels.to(dev).to(torch.int64)
+    valid = (lab != ignore_index) & (lab >= 0) & (lab < n)
+    count = int(valid.sum())
+    lse = torch.empty(B, H, W, dtype=torch.float64, device=dev)
+    dlo = torch.zeros(B, n, h, w, dtype=torch.float64, device=dev)
+    total = 0.0
+    for b in range(B):
+        up = Ty @ logits_lo[b].double() @ Tx.T
+        lse[b] = torch.logsumexp(up, 0)
+        li = torch.where(valid[b], lab[b], 0)
+        total += float(((lse[b] - up.gather(0, li[None])[0]) * valid[b]).sum())
+        if count:
+            G = torch.exp(up - lse[b])
+            G.scatter_add_(0, li[None], -torch.ones_like(G[:1]))
+            dlo[b] = adjoint(G * valid[b] * (grad_out / count), Ty, Tx)
+        del up
+    return {"lse": lse, "mean": total / count if count else float("nan"), "count": count, "dlogits": dlo}
+
+
+def gemm_strided_ref(A: torch.Tensor, a_strides, Bm: torch.Tensor, b_strides, batch: int, M: int, N: int, K: int):
+    """zh_gemm_f32_strided in float64: C[t](m, n) = sum_k A[t](m, k) B[t](n, k), strides (batch, row, k) in elements from the
+    start of A / Bm.  Returns (C [batch, M, N], sum_k |A B| [batch, M, N], the scale of fp32 rounding errors)."""
+    a = torch.as_strided(A.double(), (batch, M, K), a_strides)
+    b = torch.as_strided(Bm.double(), (batch, N, K), b_strides)
+    return a @ b.transpose(1, 2), a.abs() @ b.abs().transpose(1, 2)

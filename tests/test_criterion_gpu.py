@@ -42,11 +42,14 @@ def test_golden_case_through_the_dropin(golden_dir, dev, tag):
     assert rel(gt.cpu(), z[f"{tag}_grad_tokens"]) <= 1e-4
 
 
-@pytest.mark.parametrize("n_cat,five", [(81, True), (920, True), (81, False)])
-def test_training_shape_against_float64(dev, n_cat, five):
+@pytest.mark.parametrize("n_cat,five,hw", [(81, True, 48), (920, True, 48), (81, False, 48), (920, True, 24)],
+                         ids=["81-True", "920-True", "81-False", "vitb32-920-True"])
+def test_training_shape_against_float64(dev, n_cat, five, hw):
+    """hw = 48: ViT-B/16 (16-pixel patches of the 384 crop); hw = 24: ViT-B/32 (configs/*_vit_b_32.yaml), proposals and tokens
+    24x24, upsampled 16x."""
     from zutis_amd.criterion import HipCriterion
     L = 6 if five else 1
-    props, gts, tok, te, sem = make_case(8, L, 100, 48, 48, 384, 384, n_cat, 512, 48, 48, seed=11)
+    props, gts, tok, te, sem = make_case(8, L, 100, hw, hw, 384, 384, n_cat, 512, hw, hw, seed=11)
     if not five:
         props = props[:, 0]
     props, tok, te = props.to(dev), tok.to(dev), te.to(dev)

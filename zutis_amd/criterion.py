@@ -5,7 +5,7 @@ and, per (image, decoder layer), BCE on repeat()-ed [Q, n, H*W] copies of propos
 backward.  Here (csrc/criterion.hip):
 
   * the matching costs of every (image, layer) come from one launch of zh_mask_match_cost, which interpolates the low-res
-    proposals on the fly and reduces five sums per (instance, query);
+    proposals on the fly and reduces four sums per (instance, query);
   * the CE term is upsample(te . tok): a low-res GEMM (zh_gemm_f32_strided), then zh_upsample_ce_fwd (upsample -> log-sum-exp
     -> NLL, ignore_index) with a deterministic final reduction;
   * the host does ONE device -> host copy (status word, CE mean and count, skip flags, all cost matrices), solves the

@@ -2,8 +2,9 @@
 // tensors.  The reference upsamples the proposals / patch tokens to the GT resolution and runs BCE on repeat()-ed [Q, n, H*W] copies
 // (criterion.py:77-150).  Here every full-resolution value is interpolated from the low-res planes on the fly (lin_weights, the ATen
 // index / weight rule of resample.hip) and reduced at once:
-//   * cost:  per (image, layer) the [n, Q] dice + BCE matrix from five blocked sums (sum p, sum B, sum g.p, sum g.(A - B), sum g),
-//            A = max(log p, -100), B = max(log(1 - p), -100) (torch's clamp; g is binary so g.A + (1 - g).B = B + g.(A - B)).
+//   * cost:  per (image, layer) the [n, Q] dice + BCE matrix from four blocked sums (sum p, sum g.p, sum (g ? A : B), sum g),
+//            A = max(log p, -100), B = max(log(1 - p), -100) (torch's clamp).  Each pixel's BCE term is taken whole: the split
+//            B + g.(A - B) adds -100 and +100 per saturated pixel (p == 1, g == 1) and the fp32 sums do not cancel.
 //   * CE:    upsample(te . tok) = te . upsample(tok): the logits are a low-res GEMM; one kernel interpolates them per pixel,
 //            forms the log-sum-exp and the NLL and reduces per block; a one-block kernel reduces the partials in a fixed order.
 //   * grads: the full-resolution gradient of a matched pair / of the softmax goes straight through the adjoint of the bilinear
@@ -39,7 +40,9 @@ __device__ __forceinline__ float interp(const float* p, int w, const LinW& wy, c
 #define MC_QG 2      // queries per workgroup (the GT bits of a pixel are read once for all of them)
 #define MC_MAXI 16   // instances per workgroup (blockIdx.z also walks instance groups of 16)
 #define MC_BAND 48   // full-resolution rows per workgroup
-#define MC_RV(NGM) (2 + 2 * (NGM))   // partial record per (b, l, q, band): [sum p, sum B, sum g.p [NGM], sum g.(A-B) [NGM]]
+#define MC_RV(NGM) (1 + 2 * (NGM))   // partial record per (b, l, q, band): [sum p, sum g.p [NGM], sum (g ? A : B) [NGM]]
+#define MC_QV (1 + 2 * MC_MAXI)      // values per query of a workgroup's reduction: sum p, sum g.p [MC_MAXI], sum (g ? A : B) [MC_MAXI]
+#define MC_NV (MC_QG * MC_QV + MC_MAXI)   // ... and sum g [MC_MAXI]
 
 __global__ __launch_bounds__(256) void mask_cost_partial_kernel(const float* prop, const unsigned char* gt, const int* inst_off,
                                                                 float* part, float* part_g, int* status, int L, int Q, int h, int w,
@@ -51,7 +54,7 @@ __global__ __launch_bounds__(256) void mask_cost_partial_kernel(const float* pro
   const int l = z % L, b = z / L;
   const int n_b = inst_off[b + 1] - inst_off[b];
   if (ig > 0 && ig * MC_MAXI >= n_b) return;          // uniform per workgroup, before any barrier
-  const int ni = min(MC_MAXI, n_b - ig * MC_MAXI);    // may be <= 0 for ig == 0 (sum p / sum B are still produced)
+  const int ni = min(MC_MAXI, n_b - ig * MC_MAXI);    // may be <= 0 for ig == 0 (sum p is still produced)
   const int q0 = qg * MC_QG, nq = min(MC_QG, Q - q0);
   const int hw = h * w;
   const long HW = (long)H * W;
@@ -68,10 +71,10 @@ __global__ __launch_bounds__(256) void mask_cost_partial_kernel(const float* pro
   if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(status, ZH_STATUS_RANGE);
   __syncthreads();
   const bool do_g = (l == 0 && qg == 0);
-  float sp[MC_QG], sb[MC_QG], spg[MC_QG][MC_MAXI], sab[MC_QG][MC_MAXI], sg[MC_MAXI];
+  float sp[MC_QG], spg[MC_QG][MC_MAXI], sab[MC_QG][MC_MAXI], sg[MC_MAXI];
 #pragma unroll
   for (int j = 0; j < MC_QG; ++j) {
-    sp[j] = sb[j] = 0.f;
+    sp[j] = 0.f;
 #pragma unroll
     for (int i = 0; i < MC_MAXI; ++i) spg[j][i] = sab[j][i] = 0.f;
   }
@@ -91,14 +94,13 @@ __global__ __launch_bounds__(256) void mask_cost_partial_kernel(const float* pro
 #pragma unroll
     for (int j = 0; j < MC_QG; ++j) {
       const float p = interp(mc_lds + j * hw, w, wy, wx);
-      const float A = fmaxf(__logf(p), -100.f), Bv = fmaxf(__logf(1.f - p), -100.f), d = A - Bv;
+      const float A = fmaxf(__logf(p), -100.f), Bv = fmaxf(__logf(1.f - p), -100.f);
       sp[j] += p;
-      sb[j] += Bv;
 #pragma unroll
       for (int i = 0; i < MC_MAXI; ++i) {
         const bool on = (m >> i) & 1u;
         spg[j][i] += on ? p : 0.f;
-        sab[j][i] += on ? d : 0.f;
+        sab[j][i] += on ? A : Bv;
       }
     }
     if (do_g) {
@@ -110,42 +112,42 @@ __global__ __launch_bounds__(256) void mask_cost_partial_kernel(const float* pro
   }
   // fixed-order block reduction: wave tree, then the 4 waves in order
   float* red = mc_lds + MC_QG * hw;
-  const int NV = MC_QG * (2 + 2 * MC_MAXI) + MC_MAXI;
+  const int NV = MC_NV;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < MC_QG; ++j) {
-    const float a = wave_sum(sp[j]), c = wave_sum(sb[j]);
-    if (lane == 0) { red[wave * NV + j * (2 + 2 * MC_MAXI)] = a; red[wave * NV + j * (2 + 2 * MC_MAXI) + 1] = c; }
+    const float a = wave_sum(sp[j]);
+    if (lane == 0) red[wave * NV + j * MC_QV] = a;
 #pragma unroll
     for (int i = 0; i < MC_MAXI; ++i) {
       const float e = wave_sum(spg[j][i]), f = wave_sum(sab[j][i]);
-      if (lane == 0) { red[wave * NV + j * (2 + 2 * MC_MAXI) + 2 + i] = e; red[wave * NV + j * (2 + 2 * MC_MAXI) + 2 + MC_MAXI + i] = f; }
+      if (lane == 0) { red[wave * NV + j * MC_QV + 1 + i] = e; red[wave * NV + j * MC_QV + 1 + MC_MAXI + i] = f; }
     }
   }
   if (do_g) {
 #pragma unroll
     for (int i = 0; i < MC_MAXI; ++i) {
       const float e = wave_sum(sg[i]);
-      if (lane == 0) red[wave * NV + MC_QG * (2 + 2 * MC_MAXI) + i] = e;
+      if (lane == 0) red[wave * NV + MC_QG * MC_QV + i] = e;
     }
   }
   __syncthreads();
   const int NGM = NG * MC_MAXI, RV = MC_RV(NGM);
   for (int v = threadIdx.x; v < NV; v += 256) {
     const float s = ((red[v] + red[NV + v]) + red[2 * NV + v]) + red[3 * NV + v];
-    if (v < MC_QG * (2 + 2 * MC_MAXI)) {
-      const int j = v / (2 + 2 * MC_MAXI), r = v - j * (2 + 2 * MC_MAXI);
+    if (v < MC_QG * MC_QV) {
+      const int j = v / MC_QV, r = v - j * MC_QV;
       if (j >= nq) continue;
       float* rec = part + ((((long)b * L + l) * Q + q0 + j) * NB + band) * RV;
-      if (r < 2) {
-        if (ig == 0) rec[r] = s;
+      if (r < 1) {
+        if (ig == 0) rec[0] = s;
       } else {
-        const int i = (r - 2) % MC_MAXI, which = (r - 2) / MC_MAXI;
-        if (i < ni) rec[2 + which * NGM + ig * MC_MAXI + i] = s;
+        const int i = (r - 1) % MC_MAXI, which = (r - 1) / MC_MAXI;
+        if (i < ni) rec[1 + which * NGM + ig * MC_MAXI + i] = s;
       }
     } else if (do_g) {
-      const int i = v - MC_QG * (2 + 2 * MC_MAXI);
+      const int i = v - MC_QG * MC_QV;
       if (i < ni) part_g[((long)b * NB + band) * NGM + ig * MC_MAXI + i] = s;
     }
   }
@@ -187,17 +189,16 @@ __global__ __launch_bounds__(256) void mask_cost_final_kernel(const float* part,
   const int n_b = inst_off[b + 1] - inst_off[b];
   const int rr = (int)(r - (long)L * inst_off[b]);
   const int l = rr / n_b, i = rr - l * n_b;
-  float Sp = 0.f, SB = 0.f, Spg = 0.f, Sab = 0.f, Sg = 0.f;
+  float Sp = 0.f, Spg = 0.f, Sab = 0.f, Sg = 0.f;
   const float* rec = part + (((long)b * L + l) * Q + q) * NB * RV;
   for (int k = 0; k < NB; ++k) {
     Sp += rec[k * RV];
-    SB += rec[k * RV + 1];
-    Spg += rec[k * RV + 2 + i];
-    Sab += rec[k * RV + 2 + NGM + i];
+    Spg += rec[k * RV + 1 + i];
+    Sab += rec[k * RV + 1 + NGM + i];
     Sg += part_g[((long)b * NB + k) * NGM + i];
   }
   const float dice = 1.f - (2.f * Spg + 1.f) / (Sp + Sg + 1.f);
-  const float bce = -(SB + Sab) / (float)HW;
+  const float bce = -Sab / (float)HW;
   costs[t] = wd * dice + wb * bce;
   stat_pg[t] = Spg;
 }
@@ -214,7 +215,7 @@ extern "C" int zh_mask_match_cost(const float* proposals, const unsigned char* g
   ZH_CHECK_ARG(proposals && inst_off && costs && stat_p && stat_pg && stat_g && skip && status && workspace, "zh_mask_match_cost: null pointer");
   ZH_CHECK_ARG(n_max == 0 || gt_u8, "zh_mask_match_cost: null gt_u8");
   ZH_CHECK_ARG(B > 0 && L > 0 && Q > 0 && h > 0 && w > 0 && H > 0 && W > 0 && n_max >= 0, "zh_mask_match_cost: bad shape");
-  const size_t lds = (size_t)(MC_QG * h * w + 4 * (MC_QG * (2 + 2 * MC_MAXI) + MC_MAXI)) * sizeof(float);
+  const size_t lds = (size_t)(MC_QG * h * w + 4 * MC_NV) * sizeof(float);
   ZH_CHECK_ARG(lds <= 65536, "zh_mask_match_cost: proposal plane %dx%d too large for LDS", h, w);
   ZH_CHECK_ARG(workspace_bytes >= zh_mask_match_cost_workspace_size(B, L, Q, H, n_max), "zh_mask_match_cost: workspace too small");
   const int NB = zh_cdiv(H, MC_BAND), NG = zh_cdiv(n_max > 0 ? n_max : 1, MC_MAXI);
