@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 226 /* 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 227 /* 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -79,6 +79,17 @@ int zh_gemm_f16(const void* A, long lda, long strideA, const void* W, long ldw, 
                 const float* bias, const float* residual, long ldr, long strideR, int res_rows,
                 const void* pos_y, const void* pos_x, long ld_pos, int pos_h, int pos_w, int pos_f16,
                 int act, int M, int N, int K, int batch, zh_stream_t stream);
+
+/* The residual update of a HALF-precision stream, x = x + linear(y) as the reference's own fp16 tower computes it (third-party
+ * clip.load leaves the model in fp16 on a GPU, utils/extract_image_embeddings.py:43,72-78; ResidualAttentionBlock.forward,
+ * clip_arch.py:318-321):  C[b][m][n] = f16( f16(sum_k A W + bias[n]) + residual[b][m % res_rows][n] ),  C and residual f16, the sum of
+ * products and both additions in fp32, two roundings to fp16 (the Linear's output, then the sum).  Shapes, strides and alignment as
+ * zh_gemm_f16 with out_f16 = 1; ldr % 4 == 0 and an 8-byte aligned residual (16-byte row stores also need ldr % 8 == 0 and 16-byte
+ * alignment).  residual may alias C. */
+int zh_gemm_f16_res16(const void* A, long lda, long strideA, const void* W, long ldw, long strideW,
+                      void* C, long ldc, long strideC,
+                      const float* bias, const void* residual, long ldr, long strideR, int res_rows,
+                      int M, int N, int K, int batch, zh_stream_t stream);
 
 /* The same contraction at the reference's precision (the reference computes every Linear / einsum in fp32:
  * clip_arch.py:286-292 keeps LayerNorm fp32, zutis.py:55 casts the CLIP weights to fp32).  A and W are split pairs
@@ -147,7 +158,14 @@ int zh_layernorm_f32(const float* x, long in_group_rows, long in_group_stride, l
                      const float* gamma, const float* beta, float eps,
                      float* out_f32, void* out_f16, void* out_f16_plus, float* out_f32_plus,
                      const float* add, int add_rows, int rows, int D, long lo_plane, int* status, zh_stream_t stream);
-/* status (here, zh_sum_layernorm_f32, zh_global_ln_l2; may be NULL): a device word into which ZH_STATUS_NONFINITE (2) is OR-ed when a row's
+/* The same LayerNorm of an fp16 input x (the half-precision residual stream; CLIP's LayerNorm subclass widens an fp16 input to fp32
+ * and back, clip_arch.py:286-292): statistics, affine and every output formed in fp32.  x 16-byte aligned, D % 8 == 0, lo_plane % 8 == 0. */
+int zh_layernorm_f16(const void* x, long in_group_rows, long in_group_stride, long in_offset,
+                     long out_group_rows, long out_group_stride, long out_offset,
+                     const float* gamma, const float* beta, float eps,
+                     float* out_f32, void* out_f16, void* out_f16_plus, float* out_f32_plus,
+                     const float* add, int add_rows, int rows, int D, long lo_plane, int* status, zh_stream_t stream);
+/* status (here, zh_layernorm_f16, zh_sum_layernorm_f32, zh_global_ln_l2; may be NULL): a device word into which ZH_STATUS_NONFINITE (2) is OR-ed when a row's
  * variance is inf / NaN.  The split-pair (f16x3) operands of this library hold |x| < 65504: beyond it hi = inf and every later product is
  * a NaN that reaches the next LayerNorm of the path — checking there costs one compare per row.  The host reads the word once per
  * forward (at its next synchronisation) and raises; bit 0 of the same word is zh_instance_mask_stats' range flag. */
@@ -176,6 +194,12 @@ int zh_sum_layernorm_f32(const float* parts, int n_parts, long part_stride, cons
 int zh_assemble_tokens_ln(const float* patch_emb, const float* class_embedding, const float* pos_embed,
                           const float* gamma, const float* beta, float eps, float* out,
                           int B, int T, int D, zh_stream_t stream);
+
+/* The same with out f16 [B,T,D]: the half-precision residual stream after ln_pre (clip_arch.py:384-397 in the fp16 tower of
+ * utils/extract_image_embeddings.py:43,72-73), rounded once from the fp32 LayerNorm result. */
+int zh_assemble_tokens_ln_f16(const float* patch_emb, const float* class_embedding, const float* pos_embed,
+                              const float* gamma, const float* beta, float eps, void* out,
+                              int B, int T, int D, zh_stream_t stream);
 
 /* x / (||x||_2 + eps) per row: queries (eps = 0) zutis.py:515; averaged tokens (eps = 1e-7) zutis.py:413. */
 int zh_l2norm_rows(const float* x, float* out_f32, void* out_f16, float eps, int rows, int D, long lo_plane, float f16_scale, zh_stream_t stream);

@@ -32,6 +32,7 @@ _SIGS = {
     "zh_dev_set_gemm_overrides": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "zh_dev_set_gemm_persist": (C.c_int, [C.c_int]),
     "zh_gemm_f16": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _vp, _vp, _l, _l, _i, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "zh_gemm_f16_res16": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _vp, _vp, _l, _l, _i, _i, _i, _i, _i, _vp]),
     "zh_gemm_f16x3": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _vp, _l, _l, _l, _i, _f, _vp, _vp, _l, _l, _i, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i,
                            _i, _vp]),
     "zh_attention_f16": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _i, _f, _l, _l, _l, _l, _vp]),
@@ -42,8 +43,10 @@ _SIGS = {
     "zh_eot_rows_f32": (_i, [_vp, _vp, _vp, _l, _i, _i, _vp]),
     "zh_group_mean_l2norm": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "zh_layernorm_f32": (_i, [_vp, _l, _l, _l, _l, _l, _l, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _vp, _vp]),
+    "zh_layernorm_f16": (_i, [_vp, _l, _l, _l, _l, _l, _l, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _vp, _vp]),
     "zh_sum_layernorm_f32": (_i, [_vp, _i, _l, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _l, _l, _l, _l, _i, _vp, _vp, _f, _vp, _vp, _l, _l, _l, _l, _i, _i, _vp, _vp]),
     "zh_assemble_tokens_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
+    "zh_assemble_tokens_ln_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
     "zh_l2norm_rows": (_i, [_vp, _vp, _vp, _f, _i, _i, _l, _f, _vp]),
     "zh_global_ln_l2_workspace_size": (_sz, [_i, _i, _i]),
     "zh_global_ln_l2": (_i, [_vp, _vp, _vp, _f, _f, _i, _i, _i, _vp, _sz, _l, _f, _vp, _vp]),

@@ -49,7 +49,8 @@ struct GemmArgs {
   long planeA, planeW, planeC;   // SPLIT: element offset hi plane -> lo plane of A / W / (OUT == 2) C
   float out_scale;               // SPLIT: accumulators are multiplied by this before the bias (weights packed as W * 2^s)
   const float* bias;
-  const float* R; long ldr, sR; int res_rows;
+  union { const float* R; const half_t* R16; };   // residual: fp32, or (OUT == 3) fp16 — the fp16 residual stream of precision "half"
+  long ldr, sR; int res_rows;
   // separable per-pixel row bias (rows are pixels m = img * pos_hw + y * pos_w + x): pos_y[y][n] + pos_x[x][n] is added to
   // the accumulator before the activation — the tile's accumulators START from it, loaded under the ring's prologue
   const void* pos_y; const void* pos_x; long ld_pos; int pos_hw, pos_w, pos_f16;   // tables fp32, or fp16 (pos_f16)
@@ -115,13 +116,16 @@ constexpr bool gemm_k64_plain(int wm, int wn, int tm, int tn, int stages) {
 // STAGES = depth of the LDS ring: 4 for the big tiles; 8 for the small-tile variants used when a GEMM has fewer tiles than
 // the chip has CUs — those are bound by bytes in flight per CU (3 x 16 KiB per 128x128 block = 24 GB/s per CU at ~2 us of
 // loaded latency), so the ring, not the tile, is what has to grow.
-// OUT: 0 = f32, 1 = f16, 2 = split pair (hi plane at C, lo plane at C + planeC).  SPLIT: operands are split pairs.
+// OUT: 0 = f32, 1 = f16, 2 = split pair (hi plane at C, lo plane at C + planeC), 3 = f16 with an f16 residual (R16): the stored value is
+// f16(f16(acc + bias) + r) — the two roundings of a half-precision `x + linear(y)`, the first one being the fp16 slab OUT = 1 keeps.
+// SPLIT: operands are split pairs.
 template <int WM, int WN, int TM, int TN, int STAGES, int OUT, int ACT, int VEC, int SPLIT>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM * TN) >= 96 ? 2 : 1)) void gemm_f16_kernel(GemmArgs p) {
   constexpr int NW = WM * WN;
   constexpr int NPL = SPLIT ? 2 : 1;        // planes of A
   constexpr int NPLW = SPLIT == 1 ? 2 : 1;  // planes of W (SPLIT = 2: W is exactly its hi plane)
-  constexpr int OUT_F16 = OUT == 1;
+  constexpr int OUT_F16 = OUT == 1 || OUT == 3;
+  constexpr bool RES16 = OUT == 3;
   constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
   // K64 (round 4): split-pair tiles below the big ones on TWO slots stage slices of 64 k (128-B row pieces = whole cache lines) instead
   // of 32: a CU's LDS-DMA stream moves 85 GB/s in 128-B pieces against 52 - 57 in 64-B pieces whatever the ring depth or the number of
@@ -147,7 +151,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
   // in the ring slot the prologue does not use plus the LDS beyond the ring (the kernel takes all 160 KiB), in smaller passes.
   // Same arithmetic per output element: results are bitwise those of one workgroup per tile (the launcher picks the grid).
   // (the fp32-output 256 x 256 form stays one workgroup per tile: with the tile loop around it hipcc spills 36 bytes in its epilogue)
-  constexpr bool PERS = !SPLIT && NW == 8 && STAGES == 4 && VEC == 2 && (OUT == 1 || TN == 3);
+  constexpr bool PERS = !SPLIT && NW == 8 && STAGES == 4 && VEC == 2 && (OUT == 1 || OUT == 3 || TN == 3);
   constexpr int SLAB_OFF = PERS ? (STAGES - 1) * STAGE_HALVES * 2 : 0;                       // bytes: slot STAGES - 1 and what follows
   constexpr int RINGP = K64 ? gemm_k64_ring_pieces(WM, WN, TM, TN, STAGES, SPLIT) : 0;            // circular ring of pieces (K64 tiles too large for three slots)
   constexpr bool FRAC = RINGP != 0;
@@ -809,7 +813,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
   if (PERS) asm volatile("" : "+v"(lane_e));
   const int frow_e = PERS ? (lane_e & 15) : frow, fk_e = PERS ? (lane_e >> 4) : fk;
   const long cb = (long)batch * p.sC;
-  const float* R = p.R ? p.R + (long)batch * p.sR : nullptr;
+  const float* R = (!RES16 && p.R) ? p.R + (long)batch * p.sR : nullptr;
   const float osc = SPLIT ? p.out_scale : 1.0f;
   const bool res_nowrap = p.res_rows >= p.M;               // the residual has its own row for every output row: no modulo
   if (VEC == 2) {
@@ -823,7 +827,10 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
     constexpr int PR0 = PRW < TM * 16 ? PRW : TM * 16;
     constexpr int PR1 = (TM * 16) % PR0 == 0 ? PR0 : (TM * 16 <= 48 ? TM * 16 : 16);      // rows per pass (divides the wave tile)
     // PERS: the slabs share what the next tile's prologue leaves of the LDS — halve the pass until they fit
-    constexpr int PR = !PERS ? PR1 : (NW * PR1 * RS <= SLAB_CAP ? PR1 : (NW * (PR1 / 2) * RS <= SLAB_CAP ? PR1 / 2 : PR1 / 4));
+    constexpr int PRF = !PERS ? PR1 : (NW * PR1 * RS <= SLAB_CAP ? PR1 : (NW * (PR1 / 2) * RS <= SLAB_CAP ? PR1 / 2 : PR1 / 4));
+    // fp16 residual on the 256 x 256 persistent tile: one 16-row sub-tile per pass — the pass's residual chunks (NIT x 4 registers) sit beside
+    // the 128 accumulators, and with 32-row passes the tile loop spilled 36 bytes
+    constexpr int PR = (RES16 && PERS && TN >= 4) ? 16 : PRF;
     static_assert(PR >= 16 && PR % 16 == 0 && (TM * 16) % PR == 0 && NW * PR * RS <= SLAB_CAP, "epilogue slabs do not fit beside the next tile's prologue (a pass is whole 16-row sub-tiles)");
     constexpr int MTP = PR / 16;
     constexpr int CPRW = TN * 16 * ESZ / 16;                // 16-B chunks per row
@@ -927,6 +934,25 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
         // block (in-kernel stamps, profiles/NOTES.md).  Now the pass's residual chunks are requested together, branch-free, before the slab is
         // read, and `m % res_rows` is skipped when the residual has a row of its own for every output row.
         f32x4 rv[NIT];
+        if constexpr (RES16) {
+          // fp16 residual (a chunk is 16 B = 8 halves, the slab's own chunk): the same request, the chunks as raw bits
+          if (p.R16) {
+            const half_t* R16 = p.R16 + (long)batch * p.sR;
+            auto request = [&](auto nowrap) {
+#pragma clang loop unroll(full)
+              for (int it = 0; it < NIT; ++it) {
+                const int c = it * 64 + lane_e;
+                const int row = c / CPRW, ch = c - row * CPRW;
+                const int m = min(m0 + wr * TM * 16 + pass * PR + row, p.M - 1);
+                int n = n0 + wc * TN * 16 + ch * 8;
+                n = n < p.N ? n : 0;
+                rv[it] = *(const f32x4*)(R16 + (long)(decltype(nowrap)::value ? m : m % p.res_rows) * p.ldr + n);
+              }
+            };
+            if (res_nowrap) request(std::true_type{});
+            else request(std::false_type{});
+          }
+        } else
         if (OUT == 0 && R) {
           auto request = [&](auto nowrap) {
 #pragma clang loop unroll(full)
@@ -953,7 +979,16 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
             // f32 output: the slab holds fp32, the residual joins before the store
             if (BIAS_LATE) d += bias_late;
             if (OUT == 0 && R) d += rv[it];
-            if (OUT == 1) *(f32x4*)((half_t*)p.C + cb + (long)m * p.ldc + n) = d;
+            if constexpr (RES16) {
+              if (p.R16) {                                     // f16(g + r): g = the slab's f16(acc + bias), the sum in fp32
+                const half8_t g = __builtin_bit_cast(half8_t, d), r = __builtin_bit_cast(half8_t, rv[it]);
+                half8_t o;
+#pragma clang loop unroll(full)
+                for (int e = 0; e < 8; ++e) o[e] = (half_t)((float)g[e] + (float)r[e]);
+                d = __builtin_bit_cast(f32x4, o);
+              }
+            }
+            if (OUT_F16) *(f32x4*)((half_t*)p.C + cb + (long)m * p.ldc + n) = d;
             else *(f32x4*)((float*)p.C + cb + (long)m * p.ldc + n) = d;
           }
         }
@@ -974,8 +1009,15 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
           if (ACT != ZH_ACT_NONE) {
             v[0] = zh_act(v[0], ACT); v[1] = zh_act(v[1], ACT); v[2] = zh_act(v[2], ACT); v[3] = zh_act(v[3], ACT);
           }
+          if constexpr (RES16) {
+            if (p.R16) {
+              const half4_t g = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+              const half4_t r = *(const half4_t*)(p.R16 + (long)batch * p.sR + (long)(m % p.res_rows) * p.ldr + n);
+              v = (f32x4){(float)g[0] + (float)r[0], (float)g[1] + (float)r[1], (float)g[2] + (float)r[2], (float)g[3] + (float)r[3]};
+            }
+          } else
           if (R) v += *(const f32x4*)(R + (long)(m % p.res_rows) * p.ldr + n);
-          if (OUT == 1) {
+          if (OUT_F16) {
             half4_t h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
             *(half4_t*)((half_t*)p.C + cb + (long)m * p.ldc + n) = h;
           } else if (OUT == 0) {
@@ -990,7 +1032,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
 #pragma clang loop unroll(full)
     for (int mt = 0; mt < TM; ++mt) {
       const int m = m0 + (wr * TM + mt) * 16 + frow_e;
-      const long rrow = R ? (long)(m % p.res_rows) * p.ldr : 0;
+      const long rrow = (RES16 ? p.R16 != nullptr : R != nullptr) ? (long)(m % p.res_rows) * p.ldr : 0;
 #pragma clang loop unroll(full)
       for (int nt = 0; nt < TN; ++nt) {
         const int n = n0 + (wc * TN + nt) * 16 + fk_e * 4;
@@ -1000,9 +1042,12 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) >= 8 ? 2 : ((WM * WN * TM *
             float x = acc[nt][mt][e] * osc;
             if (p.bias) x += p.bias[n + e];
             x = zh_act(x, ACT);
+            if constexpr (RES16) {
+              if (p.R16) x = (float)(half_t)x + (float)p.R16[(long)batch * p.sR + rrow + n + e];
+            } else
             if (R) x += R[rrow + n + e];
             const long ci = cb + (long)m * p.ldc + n + e;
-            if (OUT == 1) ((half_t*)p.C)[ci] = (half_t)x;
+            if (OUT_F16) ((half_t*)p.C)[ci] = (half_t)x;
             else if (OUT == 0) ((float*)p.C)[ci] = x;
             else {
               zh_store_h1((half_t*)p.C + ci, p.planeC, x);
@@ -1036,7 +1081,7 @@ static void launch_one(GemmArgs p, int batch, hipStream_t stream) {
   p.total = (int)nblk;
   // persistent big plain-fp16 tiles (see PERS in the kernel): one workgroup per CU walks the tiles when there is more than one round of
   // them; never with pos tables (their slice is staged through the ring slot the next tile's prologue would use)
-  constexpr bool PERS = !SPLIT && WM * WN == 8 && STAGES == 4 && VEC == 2 && (OUT == 1 || TN == 3);
+  constexpr bool PERS = !SPLIT && WM * WN == 8 && STAGES == 4 && VEC == 2 && (OUT == 1 || OUT == 3 || TN == 3);
   if (PERS) {
     const int cus = gemm_persist_cus();                    // the device's CUs; developer override: 0 = off, n = a grid of n workgroups (multiple of 8)
     if (cus > 0 && !p.pos_y && nblk > (unsigned)cus) nblk = (unsigned)cus;

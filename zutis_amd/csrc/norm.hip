@@ -279,6 +279,130 @@ extern "C" int zh_assemble_tokens_ln(const float* patch_emb, const float* class_
   return ZH_OK;
 }
 
+// ---- the fp16 residual stream (precision "half": CLIP's own storage class for encode_image, utils/extract_image_embeddings.py:43,72-78).
+// Same row addressing, outputs and status word as layernorm_kernel; the row arrives as 16-byte chunks of 8 halves (half the bytes of the
+// fp32 form, which is what this kernel is bound by) and is widened once: statistics, affine and every output are formed in fp32.
+// A lane's chunk j (columns 8 * (lane + 64 j) ..+7) sits in v[2j], v[2j + 1].
+__device__ __forceinline__ bool ln_normalize_h8(LnRow& r, int nv8, int lane, int D, float eps) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j)
+    if (lane + 64 * (j >> 1) < nv8) s += (r.v[j][0] + r.v[j][1]) + (r.v[j][2] + r.v[j][3]);
+  const float mean = wave_sum(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j)
+    if (lane + 64 * (j >> 1) < nv8) {
+      r.v[j] -= mean;
+      q += (r.v[j][0] * r.v[j][0] + r.v[j][1] * r.v[j][1]) + (r.v[j][2] * r.v[j][2] + r.v[j][3] * r.v[j][3]);
+    }
+  const float var = wave_sum(q) / (float)D;
+  const float rstd = rsqrtf(var + eps);
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j) r.v[j] *= rstd;
+  return var < INFINITY;                                    // false for inf and for NaN
+}
+
+__global__ __launch_bounds__(256) void layernorm_h16_kernel(LnArgs p) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= p.rows) return;
+  const int nv8 = p.D >> 3;
+  const long in_row = (r / p.in_group_rows) * p.in_group_stride + p.in_offset + (r % p.in_group_rows);
+  const half8_t* xp = (const half8_t*)((const half_t*)(const void*)p.x + in_row * p.D);
+  half8_t raw[LN_MAXV / 2];
+#pragma unroll
+  for (int j = 0; j < LN_MAXV / 2; ++j)
+    if (lane + 64 * j < nv8) raw[j] = xp[lane + 64 * j];
+  LnRow row;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV / 2; ++j)
+    if (lane + 64 * j < nv8) {
+      row.v[2 * j] = (f32x4){(float)raw[j][0], (float)raw[j][1], (float)raw[j][2], (float)raw[j][3]};
+      row.v[2 * j + 1] = (f32x4){(float)raw[j][4], (float)raw[j][5], (float)raw[j][6], (float)raw[j][7]};
+    }
+  zh_raise_nonfinite(p.status, ln_normalize_h8(row, nv8, lane, p.D, p.eps), lane);
+  const long ob = ((r / p.out_group_rows) * p.out_group_stride + p.out_offset + (r % p.out_group_rows)) * p.D;
+  const long ab = p.add ? (long)(r % p.add_rows) * p.D : 0;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV / 2; ++j) {
+    const int c8 = lane + 64 * j;
+    if (c8 < nv8) {
+      f32x4 y0 = row.v[2 * j], y1 = row.v[2 * j + 1];
+      const int c = 2 * c8;                                 // index of y0 in float4 units; y1 follows
+      if (p.gamma) {
+        y0 = y0 * ((const f32x4*)p.gamma)[c] + ((const f32x4*)p.beta)[c];
+        y1 = y1 * ((const f32x4*)p.gamma)[c + 1] + ((const f32x4*)p.beta)[c + 1];
+      }
+      if (p.out_f32) { ((f32x4*)(p.out_f32 + ob))[c] = y0; ((f32x4*)(p.out_f32 + ob))[c + 1] = y1; }
+      if (p.out_f16) {
+        if (p.lo_plane) zh_store_h8(p.out_f16 + ob + 8 * c8, p.lo_plane, y0, y1);
+        else {                                              // plain fp16: one 16-byte store
+          const half8_t h = {(half_t)y0[0], (half_t)y0[1], (half_t)y0[2], (half_t)y0[3], (half_t)y1[0], (half_t)y1[1], (half_t)y1[2], (half_t)y1[3]};
+          *(half8_t*)(p.out_f16 + ob + 8 * c8) = h;
+        }
+      }
+      if (p.add) {
+        const f32x4 z0 = y0 + ((const f32x4*)(p.add + ab))[c], z1 = y1 + ((const f32x4*)(p.add + ab))[c + 1];
+        if (p.out_f16_plus) { zh_store_h4(p.out_f16_plus + ob + 8 * c8, p.lo_plane, z0); zh_store_h4(p.out_f16_plus + ob + 8 * c8 + 4, p.lo_plane, z1); }
+        if (p.out_f32_plus) { ((f32x4*)(p.out_f32_plus + ob))[c] = z0; ((f32x4*)(p.out_f32_plus + ob))[c + 1] = z1; }
+      }
+    }
+  }
+}
+
+extern "C" int zh_layernorm_f16(const void* x, long in_group_rows, long in_group_stride, long in_offset,
+                                long out_group_rows, long out_group_stride, long out_offset,
+                                const float* gamma, const float* beta, float eps,
+                                float* out_f32, void* out_f16, void* out_f16_plus, float* out_f32_plus,
+                                const float* add, int add_rows, int rows, int D, long lo_plane, int* status, hipStream_t stream) {
+  ZH_CHECK_ARG(x && rows > 0 && ((uintptr_t)x & 15) == 0, "zh_layernorm_f16: bad input (x must be 16-byte aligned)");
+  ZH_CHECK_ARG(lo_plane % 8 == 0, "zh_layernorm_f16: lo_plane must be a multiple of 8 halves");
+  ZH_CHECK_ARG(D % 8 == 0 && D <= 256 * LN_MAXV && D > 0, "zh_layernorm_f16: D=%d must be a multiple of 8 and <= %d", D, 256 * LN_MAXV);
+  ZH_CHECK_ARG((gamma == nullptr) == (beta == nullptr), "zh_layernorm_f16: gamma and beta must both be given or both null");
+  ZH_CHECK_ARG(in_group_rows > 0 && out_group_rows > 0, "zh_layernorm_f16: group_rows must be > 0");
+  ZH_CHECK_ARG(!(out_f16_plus || out_f32_plus) || (add && add_rows > 0), "zh_layernorm_f16: *_plus outputs need add/add_rows");
+  LnArgs p{(const float*)x, in_group_rows, in_group_stride, in_offset, out_group_rows, out_group_stride, out_offset, gamma, beta, out_f32, (half_t*)out_f16,
+           (half_t*)out_f16_plus, add, add_rows, out_f32_plus, rows, D, eps, lo_plane, status};
+  hipLaunchKernelGGL(layernorm_h16_kernel, dim3(zh_cdiv(rows, 4)), dim3(256), 0, stream, p);
+  ZH_CHECK_LAUNCH("zh_layernorm_f16");
+  return ZH_OK;
+}
+
+// token assembly + ln_pre with the fp16 stream as its output: the one rounding of X after ln_pre (fp32 inputs and statistics)
+__global__ __launch_bounds__(256) void assemble_ln_h16_kernel(AsmArgs p) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= (long)p.B * p.T) return;
+  const int nv = p.D >> 2;
+  const int b = (int)(r / p.T), t = (int)(r % p.T);
+  const f32x4* src = t == 0 ? (const f32x4*)p.cls : (const f32x4*)(p.patch + ((long)b * (p.T - 1) + (t - 1)) * p.D);
+  const f32x4* pos = (const f32x4*)(p.pos + (long)t * p.D);
+  LnRow row;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j)
+    if (lane + 64 * j < nv) row.v[j] = src[lane + 64 * j] + pos[lane + 64 * j];
+  if (p.gamma) ln_normalize(row, nv, lane, p.D, p.eps);
+  half_t* out = (half_t*)(void*)p.out + r * p.D;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j) {
+    const int c = lane + 64 * j;
+    if (c < nv) zh_store_h4(out + 4 * c, 0, p.gamma ? row.v[j] * ((const f32x4*)p.gamma)[c] + ((const f32x4*)p.beta)[c] : row.v[j]);
+  }
+}
+
+extern "C" int zh_assemble_tokens_ln_f16(const float* patch_emb, const float* class_embedding, const float* pos_embed,
+                                         const float* gamma, const float* beta, float eps, void* out,
+                                         int B, int T, int D, hipStream_t stream) {
+  ZH_CHECK_ARG(patch_emb && class_embedding && pos_embed && out, "zh_assemble_tokens_ln_f16: null pointer");
+  ZH_CHECK_ARG((gamma == nullptr) == (beta == nullptr), "zh_assemble_tokens_ln_f16: gamma and beta must both be given or both null");
+  ZH_CHECK_ARG(B > 0 && T > 1 && D % 4 == 0 && D <= 256 * LN_MAXV, "zh_assemble_tokens_ln_f16: bad shape B=%d T=%d D=%d", B, T, D);
+  AsmArgs p{patch_emb, class_embedding, pos_embed, gamma, beta, (float*)out, B, T, D, eps};
+  hipLaunchKernelGGL(assemble_ln_h16_kernel, dim3(zh_cdiv((long)B * T, 4)), dim3(256), 0, stream, p);
+  ZH_CHECK_LAUNCH("zh_assemble_tokens_ln_f16");
+  return ZH_OK;
+}
+
 // ---- row L2 normalise: queries / ||queries||  (networks/zutis.py:515, no eps) -> fp16 and/or fp32
 // f16_scale (a power of two; here and in the other producers of unit-norm rows): the fp16 / split-pair copy is stored as y * f16_scale and
 // its consumer multiplies the finished accumulator by 1 / f16_scale (Act.out_scale).  A unit-norm row of 512 - 768 elements has

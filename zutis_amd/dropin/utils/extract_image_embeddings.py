@@ -5,7 +5,12 @@ keeps the reference signature and on-disk pickle format (utils/extract_image_emb
 third-party `clip`'s fp16 `encode_image` (`clip.load` leaves the model in half precision on a GPU, :43,72-76); here the ViT
 tower runs in zutis_amd.engine.ClipImageEncoder.  `precision="exact"` (the default) computes every contraction in the fp32-class
 f16x3 / f16x2 mode (fp16 split pairs, fp32 accumulate / residual / LayerNorm) — MORE precise than the reference's own run;
-`precision="fast"` is the reference's arithmetic class for this path (fp16 MFMA operands in the transformer body, fp32 accumulate).  Weights come from `clip.load` when the package is present, else from `state_dict=`.
+`precision="fast"` is the reference's arithmetic class for this path (fp16 MFMA operands in the transformer body, fp32 accumulate)
+with the residual stream still fp32 — wider than the reference's; `precision="half"` (opt-in) also STORES the residual stream as fp16,
+which is the reference's own storage class for this tower: the stream is rounded once after ln_pre and twice per residual update
+(the Linear's output, then the sum — what an fp16 `x + linear(y)` does), LayerNorm statistics / accumulators / softmax / QuickGELU
+stay fp32.  Every mode returns unit-norm fp32 embeddings.  Weights come from `clip.load` when the package is present, else from
+`state_dict=`.
 Pre-processing (bicubic resize of the shorter side, centre crop, CLIP mean/std; SimpleDataset :90-116) is PIL + NumPy
 on the host — data loading is outside the hot path.
 """

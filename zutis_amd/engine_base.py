@@ -1,7 +1,7 @@
 """ZUTIS forward/predict as a plan over libzutis_hip kernels (MI355X-native; no torch compute ops).
 
 Data layout in HBM (one GPU, B images, T = 1 + h*w encoder tokens, M = 4*h*w decoder memory tokens):
-  X        f32 [B*T, D]        residual stream (fp32 end to end)
+  X        f32 [B*T, D]        residual stream (fp32 end to end; f16 under precision "half", ClipImageEncoder only)
   Y16      f16 [B*T, D]        LayerNorm outputs (GEMM A operands are fp16, accumulate fp32)
   QKV16    f16 [B*T, 3D]       packed q|k|v, consumed in place by flash attention (strided heads)
   H16      f16 [B*T, 4D]       QuickGELU(c_fc) — never stored in fp32
@@ -18,6 +18,10 @@ pairs (hi + lo, 22 bits) and three MFMA products per accumulator (zh_gemm_f16x3,
 `precision=` picks the map: "exact" = x3 everywhere; "fast" (default) = x3 on the contractions whose rounding reaches an
 output directly (ffn1, ffn2, mask einsum, text-space projection, class logits) and f16 in the transformer bodies, which
 tests/test_precision_gpu.py holds to the north-star tolerance on the outlier-channel stress model; "f16" = no x3 at all.
+"half" (opt-in, ClipImageEncoder only) = the sites of "fast" plus the residual stream X STORED as fp16 — the storage class of the
+reference's own encode_image run (clip.load leaves that tower in fp16 on a GPU, utils/extract_image_embeddings.py:43,72-78).  X is
+rounded once after ln_pre and once more per residual update, X <- f16(f16(O W^T + b) + X) (the two roundings of a half-precision
+`x + linear(y)`; both additions in fp32); LayerNorm statistics, accumulators, softmax and QuickGELU stay fp32 in registers.
 
 Reference call sites are cited per step (paths relative to the reference root).
 """
@@ -57,9 +61,20 @@ PRECISIONS = {
 }
 
 
-def resolve_precision(precision) -> frozenset:
-    """"f16" | "fast" | "exact" | an iterable of site names -> the set of sites computed in the x3 mode."""
+HALF = "half"        # the opt-in fp16 residual stream: the x3 sites of "fast" + X stored as fp16 (ClipImageEncoder only)
+
+
+def resolve_precision(precision, allow_half: bool = False) -> frozenset:
+    """"f16" | "fast" | "exact" | an iterable of site names -> the set of sites computed in the x3 mode.
+    "half" names a site set (that of "fast") AND a storage class for the residual stream, so it resolves only for an engine that
+    has the fp16 stream (allow_half: ClipImageEncoder); everywhere else it is refused."""
     if isinstance(precision, str):
+        if precision == HALF:
+            if not allow_half:
+                raise ZutisHipError('precision "half" (fp16 residual stream) exists for ClipImageEncoder only: the reference runs '
+                                    "encode_image in half precision (utils/extract_image_embeddings.py:43,72-78) but keeps ZUTIS, SelfMask "
+                                    "and the text tower in fp32 (networks/zutis.py:55, zutis.py:36)")
+            return PRECISIONS["fast"]
         if precision not in PRECISIONS:
             raise ZutisHipError(f"precision {precision!r} not in {sorted(PRECISIONS)}")
         return PRECISIONS[precision]
@@ -122,9 +137,10 @@ class _EngineBase:
 
     params: Dict[str, torch.Tensor]
 
-    def _init_base(self, precision="exact"):
-        self.x3_sites = resolve_precision(precision)
+    def _init_base(self, precision="exact", allow_half: bool = False):
+        self.x3_sites = resolve_precision(precision, allow_half)
         self.precision = precision if isinstance(precision, str) else "custom"
+        self.half_stream = precision == HALF          # the residual stream X is stored as fp16 (module docstring)
         self._packed_key = None
         self._w: Dict[str, torch.Tensor] = {}
         self._geo: Dict[Tuple[int, int], Dict[str, torch.Tensor]] = {}
@@ -312,7 +328,8 @@ class _EngineBase:
                 w[q + ln2 + ".w"], w[q + ln2 + ".b"] = c32(P[p + ln + ".weight"]), c32(P[p + ln + ".bias"])
 
     def _clip_trunk(self, x: torch.Tensor, pos: torch.Tensor, h: int, w: int):
-        """conv1-as-GEMM, cls concat + pos + ln_pre, all resblocks (clip_arch.py:378-401).  Returns X f32 [B*T, D]."""
+        """conv1-as-GEMM, cls concat + pos + ln_pre, all resblocks (clip_arch.py:378-401).  Returns X [B*T, D]: f32, or f16 under
+        precision "half"."""
         W_, D, p = self._w, self.D, self.patch
         B = x.shape[0]
         T, R = 1 + h * w, B * (1 + h * w)
@@ -320,14 +337,15 @@ class _EngineBase:
         ops.im2col(x, col, p, self.Kc)                                                   # :378 conv1 as GEMM
         pe32 = self._buf("patch_emb", (B * h * w, D), f32)
         self._gemm("conv", col, W_["conv"], pe32)
-        X = self._buf("X", (R, D), f32)
+        X = self._buf("X", (R, D), f16 if self.half_stream else f32)
         ops.assemble_tokens_ln(pe32, W_["encoder.class_embedding"], pos, W_["encoder.ln_pre.weight"],
                                W_["encoder.ln_pre.bias"], 1e-5, X, B, T, D)                # :384-397
         self._vit_blocks(X, B, T, D, self.heads, self.layers, 1e-5, ops.ACT_QUICKGELU)     # :318-321
         return X
 
     def _vit_blocks(self, X, B, T, D, heads, n_layers, eps, act, causal=False):
-        """Pre-LN transformer blocks on the fp32 residual stream X [B*T, D] (in place).
+        """Pre-LN transformer blocks on the residual stream X [B*T, D] (in place): fp32, or fp16 under precision "half" — then every
+        LayerNorm reads fp16 rows and the two residual GEMMs round the updated stream back to fp16 (ops.gemm, fp16 residual).
         clip_arch.py:318-321 (QuickGELU, eps 1e-5) and selfmask/vision_transformer.py:160-170 (erf GELU, eps 1e-6)."""
         W_, R = self._w, B * T
         Fd = P_shape0(W_["enc.0.fc_w"])
@@ -344,6 +362,8 @@ class _EngineBase:
         st = self.status_word()
         s_out, s_proj = self._splitk(R, D, D), self._splitk(R, D, Fd)
         sk = self._x3("out") and self._x3("proj") and (s_out > 1 or s_proj > 1)
+        if X.dtype == f16 and (self._x3("out") or self._x3("proj")):
+            raise ZutisHipError("an fp16 residual stream needs the fp16-operand out / proj GEMMs (precision \"half\")")
         parts = self._buf("sk_parts", (max(s_out, s_proj), R, D), f32) if sk else None
 
         def gemm_parts(site, A, Wt, S):

@@ -16,7 +16,9 @@ from .engine_base import _EngineBase, f16, f32
 class ClipImageEncoder(_EngineBase):
     """CLIP `encode_image` for the index-dataset pipeline (utils/extract_image_embeddings.py:72-73; third-party `clip`,
     restated from the original forward kept in clip_arch.py:413-431,531-532): fixed positional embedding, CLS token ->
-    ln_post -> @proj, then L2 normalisation.  `params` uses the CLIP visual state_dict keys under `prefix`."""
+    ln_post -> @proj, then L2 normalisation.  `params` uses the CLIP visual state_dict keys under `prefix`.
+    precision: "exact" (default) | "fast" | "f16" | site names as for the other engines, or "half" — the sites of "fast" with the
+    residual stream stored as fp16, the storage class of the reference's own run of this tower (clip.load keeps it in fp16 on a GPU)."""
 
     _proj_site = "embed"
 
@@ -27,7 +29,7 @@ class ClipImageEncoder(_EngineBase):
         self.layers = 1 + max(int(k[len(prefix):].split(".")[2]) for k in params if k.startswith(prefix + "transformer.resblocks."))
         self.E = params[prefix + "proj"].shape[1]
         self.grid = int(math.isqrt(params[prefix + "positional_embedding"].shape[0] - 1))
-        self._init_base(precision)
+        self._init_base(precision, allow_half=True)
 
     def _pack(self):
         key = self._version_key()

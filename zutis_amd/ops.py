@@ -112,12 +112,12 @@ def _hp(a):
     return (a.hi, a.plane) if isinstance(a, Act) else (a, 0)
 
 
-def _gemm_bytes(M, N, K, batch, strideA, strideW, op_bytes, out_bytes, has_residual) -> float:
+def _gemm_bytes(M, N, K, batch, strideA, strideW, op_bytes, out_bytes, has_residual, res_bytes: int = 4) -> float:
     """Compulsory (algorithmic) bytes of one GEMM launch: each operand once (a batch-shared operand once), the output once,
-    the fp32 residual once.  op_bytes = 2 for fp16 operands, 4 for split pairs."""
+    the residual once (res_bytes per element: 4 for fp32, 2 for the fp16 stream).  op_bytes = 2 for fp16 operands, 4 for split pairs."""
     a = M * K * op_bytes * (batch if strideA else 1)
     w = N * K * op_bytes * (batch if (strideW or batch == 1) else 1)
-    return float(a + w + M * N * batch * (out_bytes + (4 if has_residual else 0)))
+    return float(a + w + M * N * batch * (out_bytes + (res_bytes if has_residual else 0)))
 
 
 def _pos(pos, N):
@@ -171,7 +171,9 @@ def gemm(A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, bias=None, residua
          act: int = ACT_NONE, *, M=None, N=None, K=None, lda=None, ldw=None, ldc=None, batch: int = 1,
          strideA: int = 0, strideW: int = 0, strideC: int = 0, ldr=None, strideR: int = 0, pos=None):
     """out = act(A @ W^T + bias + pos) + residual[m % res_rows].  A [M,K] f16, W [N,K] f16, out f32|f16 [M,N]; pos: see _pos().
-    Act operands / outputs are read / written through their hi plane (plain fp16)."""
+    Act operands / outputs are read / written through their hi plane (plain fp16).
+    An fp16 residual (the half-precision residual stream) goes with an fp16 `out`, no activation and no pos tables:
+    out = f16(f16(A @ W^T + bias) + residual[m % res_rows]), both additions in fp32 (zh_gemm_f16_res16); it may alias `out`."""
     L = _lib.load()
     for t in (A, W):
         if isinstance(t, Act) and t.out_scale != 1.0:   # a weight packed for the x3 mode is W * 2^s: its hi plane alone is not W
@@ -189,11 +191,19 @@ def gemm(A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, bias=None, residua
     ldc = out.stride(-2) if ldc is None else ldc
     assert A.dtype == f16 and W.dtype == f16 and out.dtype in (f16, f32)
     if residual is not None:
-        assert residual.dtype == f32
+        if residual.dtype == f16 and (out.dtype != f16 or act != ACT_NONE or pos is not None):
+            raise _lib.ZutisHipError("gemm: an fp16 residual needs an fp16 out, no activation and no pos tables")
+        assert residual.dtype in (f16, f32)
         ldr = residual.stride(-2) if ldr is None else ldr
         res_rows = res_rows or M
     if bias is not None:
         assert bias.dtype == f32 and bias.numel() >= N
+    if residual is not None and residual.dtype == f16:
+        args = (_p(A), lda, strideA, _p(W), ldw, strideW, _p(out), ldc, strideC, _p(bias), _p(residual), ldr, strideR, res_rows,
+                M, N, K, batch, _stream())
+        nbytes = _gemm_bytes(M, N, K, batch, strideA, strideW, 2, 2, True, res_bytes=2)
+        _lib.check(_launch("gemm_f16", (2.0 * M * N * K * batch, nbytes, (M, N, K, batch)), lambda: L.zh_gemm_f16_res16(*args)), "zh_gemm_f16_res16")
+        return out_ret
     args = (_p(A), lda, strideA, _p(W), ldw, strideW, _p(out), ldc, strideC, int(out.dtype == f16),
             _p(bias), _p(residual), ldr or 0, strideR, res_rows, *_pos(pos, N), act, M, N, K, batch, _stream())
     nbytes = _gemm_bytes(M, N, K, batch, strideA, strideW, 2, 2 if out.dtype == f16 else 4, residual is not None)
@@ -283,6 +293,12 @@ def layernorm(x, gamma, beta, eps, rows, D, *, out_f32=None, out_f16=None, out_f
     if out_f16 is not None and out_f16_plus is not None and p1 != p2:
         raise _lib.ZutisHipError("layernorm: both fp16 outputs must be split pairs of the same shape, or both plain")
     lo_plane = p1 or p2
+    if x.dtype == f16:                               # the fp16 residual stream: same addressing and outputs, fp32 statistics
+        _lib.check(L.zh_layernorm_f16(_p(x), in_group_rows, in_group_stride, in_offset,
+                                      out_group_rows, out_group_stride, out_offset, _p(gamma), _p(beta), float(eps),
+                                      _p(out_f32), _p(out_f16), _p(out_f16_plus), _p(out_f32_plus), _p(add), add_rows,
+                                      rows, D, lo_plane, _p(status), _stream()), "zh_layernorm_f16")
+        return
     _lib.check(L.zh_layernorm_f32(_p(x), in_group_rows, in_group_stride, in_offset,
                                   out_group_rows, out_group_stride, out_offset, _p(gamma), _p(beta), float(eps),
                                   _p(out_f32), _p(out_f16), _p(out_f16_plus), _p(out_f32_plus), _p(add), add_rows,
@@ -309,7 +325,12 @@ def sum_layernorm(parts, n_parts, rows, D, *, part_stride=None, bias=None, resid
 
 
 def assemble_tokens_ln(patch_emb, cls, pos, gamma, beta, eps, out, B, T, D):
+    """out f32 [B,T,D], or f16 (the half-precision residual stream: rounded once from the fp32 result)."""
     L = _lib.load()
+    if out.dtype == f16:
+        _lib.check(L.zh_assemble_tokens_ln_f16(_p(patch_emb), _p(cls), _p(pos), _p(gamma), _p(beta), float(eps), _p(out),
+                                               B, T, D, _stream()), "zh_assemble_tokens_ln_f16")
+        return
     _lib.check(L.zh_assemble_tokens_ln(_p(patch_emb), _p(cls), _p(pos), _p(gamma), _p(beta), float(eps), _p(out),
                                        B, T, D, _stream()), "zh_assemble_tokens_ln")
 
