@@ -425,7 +425,7 @@ int zh_upsample_ce_bwd(const float* logits_lo, const long long* labels, const fl
 int zh_gemm_f32_strided(const float* A, long sAb, long sAm, long sAk, const float* Bm, long sBb, long sBn, long sBk, float* C,
                         long sCb, long sCm, long sCn, int batch, int M, int N, int K, zh_stream_t stream);
 
-/* Native launch plans (zutis_amd/plan.py): replay n recorded calls of the entry points above (op id + 24 argument words
+/* Native launch plans (zutis_amd/plan.py): replay n recorded calls of the entry points above (op id + 32 argument words
  * each; dispatcher generated from this header) in one C loop; zh_plan_run2 alternates two plans on two streams. */
 int zh_plan_run(const void* cmds, int n, zh_stream_t stream);
 int zh_plan_run2(const void* cmds_a, int na, zh_stream_t stream_a, const void* cmds_b, int nb, zh_stream_t stream_b);

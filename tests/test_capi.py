@@ -20,8 +20,55 @@ def test_library_exports_every_declared_symbol(lib):
     assert not missing, missing
 
 
-def test_every_declared_symbol_has_a_binding():
-    assert not [s for s in _lib.declared_symbols() if s not in _lib._SIGS]
+def test_every_declared_symbol_has_a_binding(lib):
+    """Every `zh_...(` the header shows outside comments is an entry of the parse the bindings are derived from, and the loaded
+    library's function carries argtypes with one item per declared parameter."""
+    import re
+    txt = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER).read(), flags=re.S)
+    seen = sorted(set(re.findall(r"\b(zh_[a-z0-9_]+)\s*\(", txt)))
+    entries = _lib.entries()
+    assert len(seen) >= 18 and not [s for s in seen if s not in entries]
+    assert seen == _lib.declared_symbols()
+    for s in seen:
+        decl = re.search(r"\b%s\s*\(([^)]*)\)\s*;" % s, txt).group(1).strip()
+        n_params = 0 if decl in ("", "void") else decl.count(",") + 1
+        argtypes = getattr(lib, s).argtypes
+        assert argtypes is not None and len(argtypes) == n_params == len(entries[s].params), s
+
+
+def test_header_types_map_to_ctypes(lib):
+    """The C type -> ctypes map, pinned on declarations that between them use every C type of the header."""
+    vp, i, l, f, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
+    want = {
+        "zh_gemm_f16x3": (i, [vp, l, l, l, vp, l, l, l, vp, l, l, l, i, f, vp, vp, l, l, i, vp, vp, l, i, i, i,
+                              i, i, i, i, i, i, vp]),                                  # pointers, long, int, float, stream
+        "zh_topk_rows": (i, [vp, l, i, l, i, vp, ctypes.c_longlong, vp, vp, l, vp]),      # a long long scalar
+        "zh_bilateral_workspace_size": (ctypes.c_size_t, [i, i, d, d, d]),              # size_t return, double
+        "zh_mask_iou_counts": (i, [vp, i, l, vp, vp, vp, ctypes.c_size_t, vp]),         # size_t parameter
+        "zh_last_error": (ctypes.c_char_p, []),                                         # const char* return, (void)
+        "zh_rle_encode_host": (l, [vp, i, i, vp, l]),                                   # long return, char* parameter
+        "zh_plan_run_multi": (i, [vp, vp, vp, i]),                                      # const void* const*, const zh_stream_t*
+    }
+    for name, (res, args) in want.items():
+        e = _lib.entries()[name]
+        assert (e.restype, e.argtypes) == (res, args), name
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    assert _lib.entries()["zh_topk_rows"].params[6] == ("long long", "idx_add")
+
+
+def test_unreadable_header_is_an_error():
+    """Nothing is bound by default: an unknown C type, or a zh_ declaration in a shape the parser does not read, raises."""
+    ok = "int zh_a(const float* x, long n, zh_stream_t stream);\nconst char* zh_b(void);\n"
+    assert list(_lib.parse_declarations(ok)) == ["zh_a", "zh_b"] and _lib.parse_declarations(ok)["zh_a"].plannable
+    with pytest.raises(_lib.ZutisHipError, match="zh_c.*short"):
+        _lib.parse_declarations(ok + "int zh_c(short n, zh_stream_t stream);\n")
+    with pytest.raises(_lib.ZutisHipError, match="zh_c.*float\\*"):
+        _lib.parse_declarations(ok + "float* zh_c(int n);\n")
+    with pytest.raises(_lib.ZutisHipError, match="zh_c"):
+        _lib.parse_declarations(ok + "int zh_c(void (*callback)(int), zh_stream_t stream);\n")
+    with pytest.raises(_lib.ZutisHipError, match="zh_c"):
+        _lib.parse_declarations(ok + "int zh_c(int, zh_stream_t stream);\n")
 
 
 def test_version_arch_and_error_text(lib):
@@ -66,9 +113,9 @@ def test_ops_refuse_cpu_tensors(lib):
         ops.gemm(torch.zeros(8, 64, dtype=torch.float16), torch.zeros(8, 64, dtype=torch.float16), torch.zeros(8, 8))
 
 
-def test_launch_plan_dispatcher_matches_header_and_bindings(tmp_path):
+def test_launch_plan_dispatcher_matches_header_and_bindings(tmp_path, monkeypatch):
     """The native launch-plan dispatcher is generated from include/zutis_hip.h: every plannable entry point (stream last,
-    device-pointer / scalar arguments) must exist in the ctypes table with the same arity, the generated C must call it with
+    device-pointer / scalar arguments) must be bound by ctypes with the same arity, the generated C must call it with
     one argument word per parameter, and the library must report the same op-id -> name mapping (no GPU needed)."""
     import struct
     from zutis_amd import _lib, plan
@@ -76,9 +123,9 @@ def test_launch_plan_dispatcher_matches_header_and_bindings(tmp_path):
     names = [n for n, _ in ops_]
     assert "zh_gemm_f16" in names and "zh_attention_f16" in names and "zh_bilateral_solve" in names
     assert not any(n.startswith("zh_plan_") for n in names) and "zh_denormalize_u8" not in names
+    L = _lib.load(raw=True)
     for name, sig in ops_:
-        res, args = _lib._SIGS[name]
-        assert len(args) == len(sig) <= plan.MAX_ARGS + 1, name
+        assert len(getattr(L, name).argtypes) == len(sig) <= plan.MAX_ARGS + 1, name
         assert sig[-1][0] == "zh_stream_t"
     out = tmp_path / "gen.inc"
     assert plan.generate_dispatch(str(out)) == names
@@ -86,7 +133,6 @@ def test_launch_plan_dispatcher_matches_header_and_bindings(tmp_path):
     for i, (name, sig) in enumerate(ops_):
         line = [ln for ln in txt.splitlines() if ln.strip().startswith(f"case {i}:")][0]
         assert f"return {name}(" in line and line.count("c.a[") == len(sig) - 1
-    L = _lib.load(raw=True)
     for i, name in enumerate(names):
         assert L.zh_plan_op_name(i).decode() == name
     assert L.zh_plan_op_name(len(names)) is None
@@ -94,6 +140,10 @@ def test_launch_plan_dispatcher_matches_header_and_bindings(tmp_path):
     assert plan._word("float", 1.5) == struct.unpack("<I", struct.pack("<f", 1.5))[0]
     assert plan._word("double", -2.0) == struct.unpack("<Q", struct.pack("<d", -2.0))[0]
     assert plan._word("const float*", None) == 0 and plan._word("int", -1) == 0xFFFFFFFFFFFFFFFF
+    # an entry point with more argument words than a plan command holds is refused when the dispatcher is generated
+    monkeypatch.setattr(plan, "MAX_ARGS", max(len(sig) for _, sig in ops_) - 2)
+    with pytest.raises(_lib.ZutisHipError, match="arguments before the stream"):
+        plan.generate_dispatch(str(tmp_path / "too_wide.inc"))
 
 
 def test_precision_site_sets():

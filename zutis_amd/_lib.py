@@ -1,7 +1,9 @@
 """ctypes binding of libzutis_hip.so (include/zutis_hip.h).  Fails loudly: there is no CPU fallback."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import functools
 import os
 import re
 
@@ -10,150 +12,128 @@ LIB_PATH = os.environ.get("ZUTIS_HIP_LIB") or os.path.join(HERE, "libzutis_hip.s
 HEADER = os.path.join(os.path.dirname(HERE), "include", "zutis_hip.h")
 
 _lib = None
-RECORDER = None   # zutis_amd.plan.Recorder while a launch plan is being recorded
 
 
 class ZutisHipError(RuntimeError):
     pass
 
 
-def declared_symbols(header: str = HEADER):
+_CTYPES = {"int": C.c_int, "long": C.c_long, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double,
+           "size_t": C.c_size_t, "zh_stream_t": C.c_void_p}
+_DECL = re.compile(r"^[ \t]*([A-Za-z_][\w \t]*\*?)\s*\b(zh_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", re.M)
+
+# One declaration of include/zutis_hip.h: C return type, [(C type, parameter name)], the ctypes forms of both, and whether a
+# launch plan can replay it.
+Entry = collections.namedtuple("Entry", "ret params restype argtypes plannable")
+
+
+def _ctype(func: str, ctype: str, is_return: bool = False):
+    if "*" in ctype:
+        if not is_return:
+            return C.c_void_p           # device and host pointers alike: callers pass addresses, ctypes arrays, byref() or None
+        if ctype == "const char*":
+            return C.c_char_p
+    elif ctype in _CTYPES:
+        return _CTYPES[ctype]
+    raise ZutisHipError(f"{func}: no ctypes mapping for the C type {ctype!r} (zutis_amd/_lib.py _CTYPES)")
+
+
+def parse_declarations(text: str) -> dict:
+    """{name: Entry} for every zh_* function declared in `text` (the header), in declaration order.  Strict: a type outside
+    _CTYPES, or a `zh_*(` outside comments that is not part of a declaration this parser reads, is an error."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    out = {}
+    for m in _DECL.finditer(text):
+        ret, name = " ".join(m.group(1).split()), m.group(2)
+        params = []
+        for a in (" ".join(a.split()) for a in m.group(3).split(",")):
+            if a in ("", "void"):
+                continue
+            t, _, n = a.rpartition(" ")
+            while n.startswith("*"):
+                t, n = t + "*", n[1:]
+            if not (t and re.fullmatch(r"[A-Za-z_]\w*", n)):
+                raise ZutisHipError(f"{name}: cannot read the parameter {a!r}")
+            params.append((t, n))
+        # plannable = device-pointer / scalar arguments only, stream last (zh_denormalize_u8 takes HOST float[3] pointers)
+        plannable = (ret == "int" and bool(params) and params[-1][0] == "zh_stream_t" and not name.startswith("zh_plan_")
+                     and name != "zh_denormalize_u8")
+        out[name] = Entry(ret, params, _ctype(name, ret, True), [_ctype(name, t) for t, _ in params], plannable)
+    unread = sorted(set(re.findall(r"\b(zh_[a-z0-9_]+)\s*\(", text)) - set(out))
+    if unread:
+        raise ZutisHipError(f"include/zutis_hip.h: declarations the binding parser cannot read: {unread}")
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _header_text() -> str:
+    return open(HEADER).read()
+
+
+@functools.lru_cache(maxsize=None)
+def entries() -> dict:
+    """parse_declarations() of include/zutis_hip.h: what load() binds and zutis_amd/plan.py builds its dispatcher from."""
+    return parse_declarations(_header_text())
+
+
+def declared_symbols():
     """Every function name declared in include/zutis_hip.h."""
-    txt = open(header).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(zh_[a-z0-9_]+)\s*\(", txt)))
-
-
-_vp, _l, _i, _f, _sz, _d = C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_size_t, C.c_double
-_SIGS = {
-    "zh_version": (C.c_int, []),
-    "zh_arch": (C.c_char_p, []),
-    "zh_last_error": (C.c_char_p, []),
-    "zh_dev_set_gemm_overrides": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "zh_dev_set_gemm_persist": (C.c_int, [C.c_int]),
-    "zh_gemm_f16": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _vp, _vp, _l, _l, _i, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "zh_gemm_f16_res16": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _vp, _vp, _l, _l, _i, _i, _i, _i, _i, _vp]),
-    "zh_gemm_f16x3": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _vp, _l, _l, _l, _i, _f, _vp, _vp, _l, _l, _i, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i,
-                           _i, _vp]),
-    "zh_attention_f16": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _i, _f, _l, _l, _l, _l, _vp]),
-    "zh_attention_splitk_workspace_size": (_sz, [_i, _i, _i, _i, _i]),
-    "zh_attention_f16_splitk": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _i, _f, _l, _l, _l, _l, _i, _vp, _sz, _vp]),
-    "zh_attention_causal_f16": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _f, _l, _l, _l, _l, _vp]),
-    "zh_embed_tokens_f32": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _vp]),
-    "zh_eot_rows_f32": (_i, [_vp, _vp, _vp, _l, _i, _i, _vp]),
-    "zh_group_mean_l2norm": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "zh_layernorm_f32": (_i, [_vp, _l, _l, _l, _l, _l, _l, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _vp, _vp]),
-    "zh_layernorm_f16": (_i, [_vp, _l, _l, _l, _l, _l, _l, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _vp, _vp]),
-    "zh_sum_layernorm_f32": (_i, [_vp, _i, _l, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _l, _l, _l, _l, _i, _vp, _vp, _f, _vp, _vp, _l, _l, _l, _l, _i, _i, _vp, _vp]),
-    "zh_assemble_tokens_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
-    "zh_assemble_tokens_ln_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
-    "zh_l2norm_rows": (_i, [_vp, _vp, _vp, _f, _i, _i, _l, _f, _vp]),
-    "zh_global_ln_l2_workspace_size": (_sz, [_i, _i, _i]),
-    "zh_global_ln_l2": (_i, [_vp, _vp, _vp, _f, _f, _i, _i, _i, _vp, _sz, _l, _f, _vp, _vp]),
-    "zh_im2col_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _l, _vp]),
-    "zh_posembed_bicubic": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp]),
-    "zh_select_upsample_mask": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp]),
-    "zh_upsample2x_bilinear_cl": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _l, _i, _vp]),
-    "zh_sine_pe": (_i, [_vp, _i, _i, _i, _f, _vp]),
-    "zh_add_rowperiodic_f16": (_i, [_vp, _vp, _vp, _l, _i, _i, _l, _l, _vp]),
-    "zh_fill_f32": (_i, [_vp, _f, _l, _vp]),
-    "zh_cast_f32_f16": (_i, [_vp, _vp, _i, _vp, _l, _i, _l, _f, _vp]),
-    "zh_upsample_argmax": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
-    "zh_upsample_bilinear_nchw": (_i, [_vp, _vp, _vp, _f, _l, _i, _i, _i, _i, _f, _f, _vp]),
-    "zh_confusion_hist": (_i, [_vp, _vp, _vp, _l, _i, _vp]),
-    "zh_topk_rows": (_i, [_vp, _l, _i, _l, _i, _vp, C.c_longlong, _vp, _vp, _l, _vp]),
-    "zh_mask_runs_workspace_size": (_sz, [_i, _i]),
-    "zh_mask_runs": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "zh_mask_rle_fused_supported": (_i, [_i, _i, _i]),
-    "zh_mask_rle_fused_kept": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp]),
-    "zh_mask_rle_kept": (_i, [_vp, _l, _vp, _vp, _i, _i, _i, _l, _vp, _l, _vp, _vp]),
-    "zh_mask_runs_kept": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
-    "zh_rle_counts_to_string_host": (C.c_long, [_vp, C.c_long, _vp, C.c_long]),
-    "zh_rle_from_transitions_host": (C.c_long, [_vp, C.c_long, _i, _vp, C.c_long, C.c_long, _vp, C.c_long, _vp]),
-    "zh_rle_encode_host": (C.c_long, [_vp, _i, _i, _vp, C.c_long]),
-    "zh_resize_nearest_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),
-    "zh_instance_mask_stats": (_i, [_vp, _l, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "zh_masked_mean_workspace_size": (_sz, [_i, _i, _i, _i]),
-    "zh_masked_mean_tokens": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "zh_instance_classify": (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp]),
-    "zh_denormalize_u8": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
-    "zh_bgrid_coords": (_i, [_vp, _i, _i, _d, _d, _d, _vp, _vp]),
-    "zh_bilateral_workspace_size": (_sz, [_i, _i, _d, _d, _d]),
-    "zh_bilateral_solve": (_i, [_vp, _vp, _vp, _i, _i, _d, _d, _d, _d, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "zh_bilateral_solve_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _d, _d, _d, _d, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "zh_threshold_f64_u8": (_i, [_vp, _d, _vp, _l, _vp]),
-    "zh_plan_op_name": (C.c_char_p, [_i]),
-    "zh_plan_run": (_i, [_vp, _i, _vp]),
-    "zh_plan_run_multi": (_i, [_vp, _vp, _vp, _i]),
-    "zh_plan_run2": (_i, [_vp, _i, _vp, _vp, _i, _vp]),
-    "zh_mask_nms": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "zh_mask_iou_workspace_size": (_sz, [_i, _l]),
-    "zh_mask_iou_counts": (_i, [_vp, _i, _l, _vp, _vp, _vp, _sz, _vp]),
-    "zh_mask_match_cost_workspace_size": (_sz, [_i, _i, _i, _i, _i]),
-    "zh_mask_match_cost": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _sz, _vp]),
-    "zh_mask_match_grad": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp]),
-    "zh_upsample_ce_workspace_size": (_sz, [_i, _i, _i]),
-    "zh_upsample_ce_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _sz, _vp]),
-    "zh_upsample_ce_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
-    "zh_gemm_f32_strided": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _i, _vp]),
-}
-
-
-COUNTER = None    # a dict while launches are being counted (bench.py: kernels per image): entry-point name -> calls
-
-
-class _CountingProxy:
-    """Forwards every call and counts the plannable (= launching) entry points."""
-
-    def __init__(self, lib, counts):
-        self._lib, self._counts = lib, counts
-
-    def __getattr__(self, name):
-        from . import plan
-        fn = getattr(self._lib, name)
-        if name in plan.op_table():
-            def _count(*args):
-                self._counts[name] = self._counts.get(name, 0) + 1
-                return fn(*args)
-            return _count
-        return fn
-
-
-class _RecordingProxy:
-    """Stands in for the CDLL while a plan is recorded: plannable entry points are logged, everything else passes through."""
-
-    def __init__(self, lib, rec):
-        self._lib, self._rec = lib, rec
-
-    def __getattr__(self, name):
-        from . import plan
-        fn = getattr(self._lib, name)
-        if name in plan.op_table():
-            def _log(*args):
-                self._rec.calls.append((name, args))
-                return 0
-            return _log
-        return fn
+    return sorted(entries())
 
 
 def header_abi_version() -> int:
     """ZH_ABI_VERSION of include/zutis_hip.h (the header travels with the package: bindings and library must agree on it)."""
-    import re
-    m = re.search(r"^#define\s+ZH_ABI_VERSION\s+(\d+)", open(HEADER).read(), re.M)
+    m = re.search(r"^#define\s+ZH_ABI_VERSION\s+(\d+)", _header_text(), re.M)
     if not m:
         raise ZutisHipError(f"{HEADER}: ZH_ABI_VERSION not found")
     return int(m.group(1))
 
 
+RECORDER = None   # zutis_amd.plan.Recorder while a launch plan is being recorded
+COUNTER = None    # a dict while launches are being counted (bench.py: kernels per image): entry-point name -> calls
+
+
+def _record(rec, name, fn, *args):
+    rec.calls.append((name, args))
+    return 0
+
+
+def _count(counts, name, fn, *args):
+    counts[name] = counts.get(name, 0) + 1
+    return fn(*args)
+
+
+class _Proxy:
+    """Stands in for the CDLL while a plan is recorded or launches are counted: a plannable (= launching) entry point goes to
+    on_call(sink, name, fn, args), everything else passes through.  One wrapper per name: __getattr__ only runs on a miss."""
+
+    def __init__(self, lib, sink, on_call):
+        self._lib, self._sink, self._on_call = lib, sink, on_call
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name in entries() and entries()[name].plannable:
+            fn = functools.partial(self._on_call, self._sink, name, fn)
+        setattr(self, name, fn)
+        return fn
+
+
+_proxy = None     # the _Proxy of the RECORDER / COUNTER that was active at the last load()
+
+
 def load(raw: bool = False):
     """Load the shared library (building nothing: run `python -m zutis_amd.build` / __graft_entry__.build())."""
-    global _lib
+    global _lib, _proxy
     if _lib is not None:
-        if RECORDER is not None and not raw:
-            return _RecordingProxy(_lib, RECORDER)
-        if COUNTER is not None and not raw:
-            return _CountingProxy(_lib, COUNTER)
-        return _lib
+        if raw:
+            return _lib
+        sink, on_call = (RECORDER, _record) if RECORDER is not None else (COUNTER, _count)
+        if sink is None:
+            _proxy = None               # a finished recorder (and the tensors it keeps alive) is not held on to
+            return _lib
+        if _proxy is None or _proxy._sink is not sink:
+            _proxy = _Proxy(_lib, sink, on_call)
+        return _proxy
     if not os.path.exists(LIB_PATH):
         raise ZutisHipError(
             f"{LIB_PATH} is missing: the HIP extension is REQUIRED (no CPU fallback). "
@@ -165,21 +145,14 @@ def load(raw: bool = False):
     if built != want:       # a stale build: ctypes would pass the new argument lists to the old entry points
         raise ZutisHipError(f"{LIB_PATH} was built for ABI {built} but include/zutis_hip.h declares {want}: "
                             "rebuild it with `python -m zutis_amd.build`.")
-    for name, (res, args) in _SIGS.items():
+    for name, e in entries().items():
         if not hasattr(lib, name):
             continue  # symbol check is test_capi's job; optional groups may be absent in partial builds
         fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
+        fn.restype = e.restype
+        fn.argtypes = e.argtypes
     _lib = lib
     return load(raw)
-
-
-def register(name, restype, argtypes):
-    _SIGS[name] = (restype, argtypes)
-    if _lib is not None and hasattr(_lib, name):
-        fn = getattr(_lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
 
 
 def check(rc: int, what: str = ""):

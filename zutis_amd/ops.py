@@ -22,10 +22,16 @@ f16, f32 = torch.float16, torch.float32
 PROFILER = None
 
 
-def _launch(name, work, fn):
-    if PROFILER is None:
-        return fn()
-    return PROFILER(name, work, fn)
+def _call(entry: str, *args):
+    """Call the C entry point `entry` and raise on a non-zero return code.  Looked up through _lib.load(), so that an active
+    plan recorder or launch counter sees the call."""
+    _lib.check(getattr(_lib.load(), entry)(*args), entry)
+
+
+def _launch(name, work, entry: str, args):
+    """_call(entry, *args), the call itself bracketed by PROFILER as launch `name` doing `work`."""
+    fn = getattr(_lib.load(), entry)
+    _lib.check(fn(*args) if PROFILER is None else PROFILER(name, work, lambda: fn(*args)), entry)
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -51,6 +57,17 @@ def _p(t: Optional[torch.Tensor]):
     if _lib.RECORDER is not None:
         _lib.RECORDER.keepalive.append(t)        # a launch plan owns every tensor whose address it recorded
     return t.data_ptr()
+
+
+def _nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+def _workspace(size_entry: str, device, *dims):
+    """(uint8 tensor of `size_entry`(*dims) bytes on `device`, that size).  A size query launches nothing: it goes to the library
+    itself, not through a recorder or counter."""
+    need = int(getattr(_lib.load(raw=True), size_entry)(*dims))
+    return torch.empty(need, dtype=torch.uint8, device=device), need
 
 
 def _chk(t: torch.Tensor, dtype, name: str):
@@ -138,7 +155,6 @@ def gemm_x3(A: Act, W: Act, out, bias=None, residual=None, res_rows: int = 0, ac
     out = act((A @ W^T) * W.out_scale + bias + pos) + residual[m % res_rows] at the reference's fp32-class precision: A and W
     are split pairs (Act with plane != 0); out is an f32 tensor, an fp16 tensor / plain Act, or a split Act (then the residual is
     added in fp32 before the one rounding, act must be none).  pos: see _pos()."""
-    L = _lib.load()
     if not (isinstance(A, Act) and isinstance(W, Act) and A.plane and (W.plane or W.x2)):
         raise _lib.ZutisHipError("gemm_x3: A must be a split pair, W a split pair or a one-plane split_weight() pack")
     a, w = A.hi, W.hi
@@ -163,7 +179,7 @@ def gemm_x3(A: Act, W: Act, out, bias=None, residual=None, res_rows: int = 0, ac
     if not W.plane:                                  # one-plane weight: 2 bytes per element instead of 4
         nbytes -= N * K * 2.0 * (batch if (strideW or batch == 1) else 1)
     name = "gemm_f16x3" if W.plane else "gemm_f16x2"
-    _lib.check(_launch(name, (2.0 * M * N * K * batch, nbytes, (M, N, K, batch)), lambda: L.zh_gemm_f16x3(*args)), "zh_gemm_f16x3")
+    _launch(name, (2.0 * M * N * K * batch, nbytes, (M, N, K, batch)), "zh_gemm_f16x3", args)
     return out
 
 
@@ -174,7 +190,6 @@ def gemm(A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, bias=None, residua
     Act operands / outputs are read / written through their hi plane (plain fp16).
     An fp16 residual (the half-precision residual stream) goes with an fp16 `out`, no activation and no pos tables:
     out = f16(f16(A @ W^T + bias) + residual[m % res_rows]), both additions in fp32 (zh_gemm_f16_res16); it may alias `out`."""
-    L = _lib.load()
     for t in (A, W):
         if isinstance(t, Act) and t.out_scale != 1.0:   # a weight packed for the x3 mode is W * 2^s: its hi plane alone is not W
             raise _lib.ZutisHipError("gemm: operand packed with out_scale != 1 (split_weight) reached the fp16-operand GEMM")
@@ -202,12 +217,12 @@ def gemm(A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, bias=None, residua
         args = (_p(A), lda, strideA, _p(W), ldw, strideW, _p(out), ldc, strideC, _p(bias), _p(residual), ldr, strideR, res_rows,
                 M, N, K, batch, _stream())
         nbytes = _gemm_bytes(M, N, K, batch, strideA, strideW, 2, 2, True, res_bytes=2)
-        _lib.check(_launch("gemm_f16", (2.0 * M * N * K * batch, nbytes, (M, N, K, batch)), lambda: L.zh_gemm_f16_res16(*args)), "zh_gemm_f16_res16")
+        _launch("gemm_f16", (2.0 * M * N * K * batch, nbytes, (M, N, K, batch)), "zh_gemm_f16_res16", args)
         return out_ret
     args = (_p(A), lda, strideA, _p(W), ldw, strideW, _p(out), ldc, strideC, int(out.dtype == f16),
             _p(bias), _p(residual), ldr or 0, strideR, res_rows, *_pos(pos, N), act, M, N, K, batch, _stream())
     nbytes = _gemm_bytes(M, N, K, batch, strideA, strideW, 2, 2 if out.dtype == f16 else 4, residual is not None)
-    _lib.check(_launch("gemm_f16", (2.0 * M * N * K * batch, nbytes, (M, N, K, batch)), lambda: L.zh_gemm_f16(*args)), "zh_gemm_f16")
+    _launch("gemm_f16", (2.0 * M * N * K * batch, nbytes, (M, N, K, batch)), "zh_gemm_f16", args)
     return out_ret
 
 
@@ -220,7 +235,6 @@ def attention(Q, K, V, O, *, batch, heads, Tq, Tk, head_dim, ldq, ldk, ldv, ldo,
     """x3: Q, K and V are split-pair Acts; scores and P.V get the three-product fp32-class form; a split O is filled as a pair.
     ksplit > 1: the keys are split over ksplit workgroups per (image, head, query block) and merged by a second launch; workspace =
     a uint8 CUDA tensor of attention_splitk_workspace_size() bytes."""
-    L = _lib.load()
     scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
     (Q, pq), (K, pk), (V, pv), (O, po) = _hp(Q), _hp(K), _hp(V), _hp(O)
     if x3 and not (pq and pk and pv):
@@ -233,48 +247,41 @@ def attention(Q, K, V, O, *, batch, heads, Tq, Tk, head_dim, ldq, ldk, ldv, ldo,
             raise _lib.ZutisHipError("causal attention needs Tq == Tk")
         args = (_p(Q), ldq, strideQ, _p(K), ldk, strideK, _p(V), ldv, strideV, _p(O), ldo, strideO,
                 batch, heads, Tq, head_dim, float(scale), pq, pk, pv, po, _stream())
-        _lib.check(_launch(name, 2.0 * batch * heads * Tq * Tk * head_dim, lambda: L.zh_attention_causal_f16(*args)),
-                   "zh_attention_causal_f16")
+        _launch(name, 2.0 * batch * heads * Tq * Tk * head_dim, "zh_attention_causal_f16", args)
         return O
     if ksplit > 1:
         need = attention_splitk_workspace_size(batch, heads, Tq, head_dim, ksplit)
-        if workspace is None or workspace.numel() * workspace.element_size() < need:
+        if workspace is None or _nbytes(workspace) < need:
             raise _lib.ZutisHipError(f"attention(ksplit={ksplit}): workspace of {need} bytes required")
         args = (_p(Q), ldq, strideQ, _p(K), ldk, strideK, _p(V), ldv, strideV, _p(O), ldo, strideO,
                 batch, heads, Tq, Tk, head_dim, float(scale), pq, pk, pv, po, ksplit, _p(workspace),
-                workspace.numel() * workspace.element_size(), _stream())
-        _lib.check(_launch(name, 4.0 * batch * heads * Tq * Tk * head_dim, lambda: L.zh_attention_f16_splitk(*args)),
-                   "zh_attention_f16_splitk")
+                _nbytes(workspace), _stream())
+        _launch(name, 4.0 * batch * heads * Tq * Tk * head_dim, "zh_attention_f16_splitk", args)
         return O
     args = (_p(Q), ldq, strideQ, _p(K), ldk, strideK, _p(V), ldv, strideV, _p(O), ldo, strideO,
             batch, heads, Tq, Tk, head_dim, float(scale), pq, pk, pv, po, _stream())
-    _lib.check(_launch(name, 4.0 * batch * heads * Tq * Tk * head_dim, lambda: L.zh_attention_f16(*args)),
-               "zh_attention_f16")
+    _launch(name, 4.0 * batch * heads * Tq * Tk * head_dim, "zh_attention_f16", args)
     return O
 
 
 def embed_tokens(tokens, table, pos, out):
     """tokens int64 [n,ctx] -> out f32 [n*ctx, D] = table[tokens] + pos (clip_arch.py:535-537)."""
-    L = _lib.load()
     n, ctx = tokens.shape
     _chk(table, f32, "token table"); _chk(pos, f32, "positional embedding"); _chk(out, f32, "embed out")
     if tokens.dtype != torch.int64 or not tokens.is_contiguous():
         raise _lib.ZutisHipError("embed_tokens: tokens must be contiguous int64")
-    _lib.check(L.zh_embed_tokens_f32(_p(tokens), _p(table), _p(pos), _p(out), n, ctx, table.shape[1], table.shape[0], _stream()),
-               "zh_embed_tokens_f32")
+    _call("zh_embed_tokens_f32", _p(tokens), _p(table), _p(pos), _p(out), n, ctx, table.shape[1], table.shape[0], _stream())
 
 
 def eot_rows(tokens, x, out):
-    L = _lib.load()
     n, ctx = tokens.shape
     _chk(x, f32, "eot x"); _chk(out, f32, "eot out")
-    _lib.check(L.zh_eot_rows_f32(_p(tokens), _p(x), _p(out), n, ctx, out.shape[1], _stream()), "zh_eot_rows_f32")
+    _call("zh_eot_rows_f32", _p(tokens), _p(x), _p(out), n, ctx, out.shape[1], _stream())
 
 
 def group_mean_l2norm(x, out, groups, T, E):
-    L = _lib.load()
     _chk(x, f32, "group mean x"); _chk(out, f32, "group mean out")
-    _lib.check(L.zh_group_mean_l2norm(_p(x), _p(out), groups, T, E, _stream()), "zh_group_mean_l2norm")
+    _call("zh_group_mean_l2norm", _p(x), _p(out), groups, T, E, _stream())
 
 
 STATUS_RANGE, STATUS_NONFINITE, STATUS_LABEL = 1, 2, 4     # bits of the status word (zutis_hip.h ZH_STATUS_*)
@@ -284,7 +291,6 @@ UNIT_NORM_SCALE = 1024.0                     # f16_scale of the unit-norm produc
 def layernorm(x, gamma, beta, eps, rows, D, *, out_f32=None, out_f16=None, out_f16_plus=None, out_f32_plus=None,
               add=None, add_rows=0, in_group_rows=None, in_group_stride=None, in_offset=0,
               out_group_rows=None, out_group_stride=None, out_offset=0, status=None):
-    L = _lib.load()
     in_group_rows = rows if in_group_rows is None else in_group_rows
     in_group_stride = in_group_rows if in_group_stride is None else in_group_stride
     out_group_rows = rows if out_group_rows is None else out_group_rows
@@ -293,16 +299,11 @@ def layernorm(x, gamma, beta, eps, rows, D, *, out_f32=None, out_f16=None, out_f
     if out_f16 is not None and out_f16_plus is not None and p1 != p2:
         raise _lib.ZutisHipError("layernorm: both fp16 outputs must be split pairs of the same shape, or both plain")
     lo_plane = p1 or p2
-    if x.dtype == f16:                               # the fp16 residual stream: same addressing and outputs, fp32 statistics
-        _lib.check(L.zh_layernorm_f16(_p(x), in_group_rows, in_group_stride, in_offset,
-                                      out_group_rows, out_group_stride, out_offset, _p(gamma), _p(beta), float(eps),
-                                      _p(out_f32), _p(out_f16), _p(out_f16_plus), _p(out_f32_plus), _p(add), add_rows,
-                                      rows, D, lo_plane, _p(status), _stream()), "zh_layernorm_f16")
-        return
-    _lib.check(L.zh_layernorm_f32(_p(x), in_group_rows, in_group_stride, in_offset,
-                                  out_group_rows, out_group_stride, out_offset, _p(gamma), _p(beta), float(eps),
-                                  _p(out_f32), _p(out_f16), _p(out_f16_plus), _p(out_f32_plus), _p(add), add_rows,
-                                  rows, D, lo_plane, _p(status), _stream()), "zh_layernorm_f32")
+    # an fp16 x is the half-precision residual stream: same addressing and outputs, fp32 statistics
+    _call("zh_layernorm_f16" if x.dtype == f16 else "zh_layernorm_f32", _p(x), in_group_rows, in_group_stride, in_offset,
+          out_group_rows, out_group_stride, out_offset, _p(gamma), _p(beta), float(eps),
+          _p(out_f32), _p(out_f16), _p(out_f16_plus), _p(out_f32_plus), _p(add), add_rows,
+          rows, D, lo_plane, _p(status), _stream())
 
 
 def sum_layernorm(parts, n_parts, rows, D, *, part_stride=None, bias=None, residual=None, out_sum=None, gamma=None, beta=None, eps=1e-5,
@@ -311,28 +312,22 @@ def sum_layernorm(parts, n_parts, rows, D, *, part_stride=None, bias=None, resid
                   status=None):
     """x = sum of the n_parts fp32 planes of `parts` + bias + residual -> out_sum; LN(x) -> out_f32 / out_f16 (row-mapped); LN(LN(x)) with
     gamma2 / beta2 -> out2_* (zh_sum_layernorm_f32).  n_parts = 1 with no bias / residual is a plain (or chained) LayerNorm."""
-    L = _lib.load()
     part_stride = rows * D if part_stride is None else part_stride
     ogr = rows if out_group_rows is None else out_group_rows
     ogs = ogr if out_group_stride is None else out_group_stride
     ogr2 = rows if out2_group_rows is None else out2_group_rows
     ogs2 = ogr2 if out2_group_stride is None else out2_group_stride
     (out_f16, lo1), (out2_f16, lo2) = _hp(out_f16), _hp(out2_f16)
-    _lib.check(L.zh_sum_layernorm_f32(_p(parts), n_parts, part_stride, _p(bias), _p(residual), _p(out_sum), _p(gamma), _p(beta), float(eps),
-                                      _p(out_f32), _p(out_f16), lo1, ogr, ogs, out_offset, int(skip_first_in_group),
-                                      _p(gamma2), _p(beta2), float(eps2), _p(out2_f32), _p(out2_f16), lo2, ogr2, ogs2, out2_offset,
-                                      rows, D, _p(status), _stream()), "zh_sum_layernorm_f32")
+    _call("zh_sum_layernorm_f32", _p(parts), n_parts, part_stride, _p(bias), _p(residual), _p(out_sum), _p(gamma), _p(beta), float(eps),
+          _p(out_f32), _p(out_f16), lo1, ogr, ogs, out_offset, int(skip_first_in_group),
+          _p(gamma2), _p(beta2), float(eps2), _p(out2_f32), _p(out2_f16), lo2, ogr2, ogs2, out2_offset,
+          rows, D, _p(status), _stream())
 
 
 def assemble_tokens_ln(patch_emb, cls, pos, gamma, beta, eps, out, B, T, D):
     """out f32 [B,T,D], or f16 (the half-precision residual stream: rounded once from the fp32 result)."""
-    L = _lib.load()
-    if out.dtype == f16:
-        _lib.check(L.zh_assemble_tokens_ln_f16(_p(patch_emb), _p(cls), _p(pos), _p(gamma), _p(beta), float(eps), _p(out),
-                                               B, T, D, _stream()), "zh_assemble_tokens_ln_f16")
-        return
-    _lib.check(L.zh_assemble_tokens_ln(_p(patch_emb), _p(cls), _p(pos), _p(gamma), _p(beta), float(eps), _p(out),
-                                       B, T, D, _stream()), "zh_assemble_tokens_ln")
+    _call("zh_assemble_tokens_ln_f16" if out.dtype == f16 else "zh_assemble_tokens_ln", _p(patch_emb), _p(cls), _p(pos), _p(gamma), _p(beta),
+          float(eps), _p(out), B, T, D, _stream())
 
 
 def _f16_scale(a) -> float:
@@ -342,10 +337,9 @@ def _f16_scale(a) -> float:
 
 def l2norm_rows(x, rows, D, out_f32=None, out_f16=None, eps=0.0):
     """out_f16 may be an Act with out_scale = 2^-s: the fp16 / split-pair copy is then stored times 2^s (unit-norm rows: UNIT_NORM_SCALE)."""
-    L = _lib.load()
     sc = _f16_scale(out_f16)
     out_f16, lo = _hp(out_f16)
-    _lib.check(L.zh_l2norm_rows(_p(x), _p(out_f32), _p(out_f16), float(eps), rows, D, lo, sc, _stream()), "zh_l2norm_rows")
+    _call("zh_l2norm_rows", _p(x), _p(out_f32), _p(out_f16), float(eps), rows, D, lo, sc, _stream())
 
 
 def global_ln_l2_workspace_size(B, M, Cc) -> int:
@@ -353,59 +347,49 @@ def global_ln_l2_workspace_size(B, M, Cc) -> int:
 
 
 def global_ln_l2(x, B, M, Cc, out_f32=None, out_f16=None, eps=1e-5, l2_eps=1e-7, workspace=None, status=None):
-    L = _lib.load()
     need = global_ln_l2_workspace_size(B, M, Cc)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
+    if workspace is None or _nbytes(workspace) < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
     sc = _f16_scale(out_f16)
     out_f16, lo = _hp(out_f16)
-    _lib.check(L.zh_global_ln_l2(_p(x), _p(out_f32), _p(out_f16), float(eps), float(l2_eps), B, M, Cc, _p(workspace),
-                                 workspace.numel() * workspace.element_size(), lo, sc, _p(status), _stream()), "zh_global_ln_l2")
+    _call("zh_global_ln_l2", _p(x), _p(out_f32), _p(out_f16), float(eps), float(l2_eps), B, M, Cc, _p(workspace),
+          _nbytes(workspace), lo, sc, _p(status), _stream())
 
 
 def im2col(x, out, patch, Kpad, pad_to_patch=False):
-    L = _lib.load()
     B, Cin, H, W = x.shape
     _chk(x, f32, "im2col x")
     out, lo = _hp(out)
-    _lib.check(L.zh_im2col_f16(_p(x), _p(out), B, Cin, H, W, patch, Kpad, int(pad_to_patch), lo, _stream()), "zh_im2col_f16")
+    _call("zh_im2col_f16", _p(x), _p(out), B, Cin, H, W, patch, Kpad, int(pad_to_patch), lo, _stream())
 
 
 def posembed_bicubic(pos, out, grid, h, w, D, scale_h, scale_w, has_cls=True):
-    L = _lib.load()
-    _lib.check(L.zh_posembed_bicubic(_p(pos), _p(out), grid, h, w, D, float(np.float32(scale_h)), float(np.float32(scale_w)),
-                                     int(has_cls), _stream()), "zh_posembed_bicubic")
+    _call("zh_posembed_bicubic", _p(pos), _p(out), grid, h, w, D, float(np.float32(scale_h)), float(np.float32(scale_w)), int(has_cls), _stream())
 
 
 def upsample2x_cl(x, B, h, w, D, out_f32=None, out_f16=None, relu=False):
-    L = _lib.load()
     out_f16, lo = _hp(out_f16)
-    _lib.check(L.zh_upsample2x_bilinear_cl(_p(x), _p(out_f32), _p(out_f16), B, h, w, D, lo, int(relu), _stream()),
-               "zh_upsample2x_bilinear_cl")
+    _call("zh_upsample2x_bilinear_cl", _p(x), _p(out_f32), _p(out_f16), B, h, w, D, lo, int(relu), _stream())
 
 
 def sine_pe(out, h, w, D, temperature=10000.0):
-    L = _lib.load()
-    _lib.check(L.zh_sine_pe(_p(out), h, w, D, float(temperature), _stream()), "zh_sine_pe")
+    _call("zh_sine_pe", _p(out), h, w, D, float(temperature), _stream())
 
 
 def add_rowperiodic_f16(a, add, out, rows, D, add_rows):
-    L = _lib.load()
     (a, la), (out, lo) = _hp(a), _hp(out)
-    _lib.check(L.zh_add_rowperiodic_f16(_p(a), _p(add), _p(out), rows, D, add_rows, la, lo, _stream()), "zh_add_rowperiodic_f16")
+    _call("zh_add_rowperiodic_f16", _p(a), _p(add), _p(out), rows, D, add_rows, la, lo, _stream())
 
 
 def fill_f32(x, value=0.0):
-    L = _lib.load()
     _chk(x, f32, "fill x")
-    _lib.check(L.zh_fill_f32(_p(x), float(value), x.numel(), _stream()), "zh_fill_f32")
+    _call("zh_fill_f32", _p(x), float(value), x.numel(), _stream())
 
 
 def cast_f16(x, out, rows, D, add=None, add_rows=0):
-    L = _lib.load()
     sc = _f16_scale(out)
     out, lo = _hp(out)
-    _lib.check(L.zh_cast_f32_f16(_p(x), _p(add), add_rows, _p(out), rows, D, lo, sc, _stream()), "zh_cast_f32_f16")
+    _call("zh_cast_f32_f16", _p(x), _p(add), add_rows, _p(out), rows, D, lo, sc, _stream())
 
 
 def lin_scale(in_size: int, out_size: int) -> float:
@@ -414,58 +398,46 @@ def lin_scale(in_size: int, out_size: int) -> float:
 
 
 def upsample_argmax(logits_lo, labels, B, n, h, w, H, W):
-    L = _lib.load()
-    _lib.check(L.zh_upsample_argmax(_p(logits_lo), _p(labels), B, n, h, w, H, W, lin_scale(h, H), lin_scale(w, W), _stream()),
-               "zh_upsample_argmax")
+    _call("zh_upsample_argmax", _p(logits_lo), _p(labels), B, n, h, w, H, W, lin_scale(h, H), lin_scale(w, W), _stream())
 
 
 def upsample_bilinear_nchw(x, planes, h, w, H, W, out=None, mask_u8=None, threshold=0.5, scale_h=None, scale_w=None):
     """scale_* default to in/out (size= form); pass 1/scale_factor for the scale_factor form with a cropped output."""
-    L = _lib.load()
     sh = lin_scale(h, H) if scale_h is None else float(np.float32(scale_h))
     sw = lin_scale(w, W) if scale_w is None else float(np.float32(scale_w))
-    _lib.check(L.zh_upsample_bilinear_nchw(_p(x), _p(out), _p(mask_u8), float(threshold), planes, h, w, H, W,
-                                           sh, sw, _stream()), "zh_upsample_bilinear_nchw")
+    _call("zh_upsample_bilinear_nchw", _p(x), _p(out), _p(mask_u8), float(threshold), planes, h, w, H, W, sh, sw, _stream())
 
 
 def confusion_hist(label_true, label_pred, hist, n_class):
-    L = _lib.load()
     _chk(label_true, torch.int64, "label_true")
     _chk(label_pred, torch.int64, "label_pred")
     _chk(hist, torch.int64, "hist")
-    _lib.check(L.zh_confusion_hist(_p(label_true), _p(label_pred), _p(hist), label_true.numel(), n_class, _stream()),
-               "zh_confusion_hist")
+    _call("zh_confusion_hist", _p(label_true), _p(label_pred), _p(hist), label_true.numel(), n_class, _stream())
 
 
 def instance_mask_stats(mask_proposals_last, stride_image, threshold, B, Q, M, sizes, conf, binary, range_flag=None):
     """range_flag: int32 [1] (zeroed by the caller): bit 0 set when a proposal lies outside [0, 1] (zutis.py:385-386)."""
-    L = _lib.load()
-    _lib.check(L.zh_instance_mask_stats(_p(mask_proposals_last), stride_image, float(threshold), B, Q, M, _p(sizes), _p(conf),
-                                        _p(binary), _p(range_flag), _stream()), "zh_instance_mask_stats")
+    _call("zh_instance_mask_stats", _p(mask_proposals_last), stride_image, float(threshold), B, Q, M, _p(sizes), _p(conf),
+          _p(binary), _p(range_flag), _stream())
 
 
 def masked_mean_tokens(tokens, binary, sizes, avg, B, Q, M, E):
-    L = _lib.load()
-    need = int(_lib.load(raw=True).zh_masked_mean_workspace_size(B, Q, M, E))
-    ws = torch.empty(need, dtype=torch.uint8, device=tokens.device)
-    _lib.check(L.zh_masked_mean_tokens(_p(tokens), _p(binary), _p(sizes), _p(avg), B, Q, M, E, _p(ws), need, _stream()), "zh_masked_mean_tokens")
+    ws, need = _workspace("zh_masked_mean_workspace_size", tokens.device, B, Q, M, E)
+    _call("zh_masked_mean_tokens", _p(tokens), _p(binary), _p(sizes), _p(avg), B, Q, M, E, _p(ws), need, _stream())
 
 
 def instance_classify(avg, text, conf, temperature, rows, n, E, category, score):
-    L = _lib.load()
-    _lib.check(L.zh_instance_classify(_p(avg), _p(text), _p(conf), float(temperature), rows, n, E, _p(category), _p(score),
-                                      _stream()), "zh_instance_classify")
+    _call("zh_instance_classify", _p(avg), _p(text), _p(conf), float(temperature), rows, n, E, _p(category), _p(score), _stream())
 
 
 def mask_iou_counts(masks_u8, n, pixels, inter, uni, workspace=None):
     """workspace (optional, >= zh_mask_iou_workspace_size bytes, any dtype): kept by the caller, it holds the masks bit-packed afterwards
     (u64 [n][(pixels + 63) // 64]: the `bits` of mask_rle_fused_kept)."""
-    L = _lib.load()
-    need = L.zh_mask_iou_workspace_size(n, pixels)
+    need = _lib.load(raw=True).zh_mask_iou_workspace_size(n, pixels)
     ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=masks_u8.device)
-    if ws.numel() * ws.element_size() < need:
-        raise _lib.ZutisHipError(f"mask_iou_counts: workspace holds {ws.numel() * ws.element_size()} bytes, {need} needed")
-    _lib.check(L.zh_mask_iou_counts(_p(masks_u8), n, pixels, _p(inter), _p(uni), _p(ws), need, _stream()), "zh_mask_iou_counts")
+    if _nbytes(ws) < need:
+        raise _lib.ZutisHipError(f"mask_iou_counts: workspace holds {_nbytes(ws)} bytes, {need} needed")
+    _call("zh_mask_iou_counts", _p(masks_u8), n, pixels, _p(inter), _p(uni), _p(ws), need, _stream())
 
 
 NMS_TYPES = {"hard": 0, "linear": 1, "gaussian": 2}
@@ -476,7 +448,6 @@ def mask_nms(inter, uni, scores, category_ids, nms_type="hard", nms_threshold=0.
     """Greedy per-category mask NMS on the device (zutis.py:211-299).  inter / uni int32 [B,Q,Q], scores f32 [B,Q], category_ids
     int64 [B,Q] -> (index int32 [B,Q], score f64 [B,Q], category int64 [B,Q], count int32 [B]); the first count[b] entries of
     row b are the kept queries in the reference's emission order."""
-    L = _lib.load()
     B, Q = scores.shape
     _chk(inter, torch.int32, "nms inter"); _chk(uni, torch.int32, "nms union"); _chk(scores, f32, "nms scores")
     _chk(category_ids, torch.int64, "nms categories")
@@ -487,9 +458,9 @@ def mask_nms(inter, uni, scores, category_ids, nms_type="hard", nms_threshold=0.
     sc = torch.empty((B, Q), dtype=torch.float64, device=dev)
     cat = torch.empty((B, Q), dtype=torch.int64, device=dev)
     cnt = torch.empty((B,), dtype=torch.int32, device=dev)
-    _lib.check(L.zh_mask_nms(_p(inter), _p(uni), _p(scores), _p(category_ids), B, Q, NMS_TYPES[nms_type], float(nms_threshold),
-                             float(sigma), float(score_threshold), _p(idx), _p(sc), _p(cat), _p(cnt), _p(packed), _p(range_flag),
-                             None if zero_word is None else _p(zero_word), _stream()), "zh_mask_nms")
+    _call("zh_mask_nms", _p(inter), _p(uni), _p(scores), _p(category_ids), B, Q, NMS_TYPES[nms_type], float(nms_threshold),
+          float(sigma), float(score_threshold), _p(idx), _p(sc), _p(cat), _p(cnt), _p(packed), _p(range_flag),
+          None if zero_word is None else _p(zero_word), _stream())
     return idx, sc, cat, cnt
 
 
@@ -497,26 +468,23 @@ def mask_runs_kept(masks_u8, kept_index, kept_count, max_runs, pos, nr, ba, pack
     """masks u8 [B,Q,H,W]; kept_index int32 [B,Q] / kept_count int32 [B] = zh_mask_nms' device outputs -> pos int32 [B*Q,max_runs], nr
     int32 [B*Q,2], ba int32 [B*Q,5] (row b*Q + j = image b's j-th kept mask; rows past the count are not written).  packed: pos is ONE
     int32 list (any length) that takes the kept masks' transitions back to back, min(#transitions, max_runs) each, as far as it reaches."""
-    L = _lib.load()
     _chk(masks_u8, torch.uint8, "mask_runs_kept masks"); _chk(kept_index, torch.int32, "kept_index"); _chk(kept_count, torch.int32, "kept_count")
     _chk(pos, torch.int32, "mask_runs_kept pos")
     B, Q, H, W = masks_u8.shape
     if not packed and pos.numel() < B * Q * max_runs:
         raise _lib.ZutisHipError(f"mask_runs_kept: pos holds {pos.numel()} ints, the row form needs {B * Q * max_runs}")
-    need = int(_lib.load(raw=True).zh_mask_runs_workspace_size(B * Q, W))
-    ws = torch.empty(need, dtype=torch.uint8, device=masks_u8.device)
-    _lib.check(L.zh_mask_runs_kept(_p(masks_u8), _p(kept_index), _p(kept_count), B, Q, H, W, max_runs, _p(pos), pos.numel() if packed else 0,
-                                   _p(nr), _p(ba), _p(ws), need, _stream()), "zh_mask_runs_kept")
+    ws, need = _workspace("zh_mask_runs_workspace_size", masks_u8.device, B * Q, W)
+    _call("zh_mask_runs_kept", _p(masks_u8), _p(kept_index), _p(kept_count), B, Q, H, W, max_runs, _p(pos), pos.numel() if packed else 0,
+          _p(nr), _p(ba), _p(ws), need, _stream())
 
 
 def mask_rle_kept(pos_packed, nr, kept_count, B, Q, max_runs, HW, out, out_len):
     """COCO RLE strings of the kept masks on the device from mask_runs_kept(packed=True)'s list: out u8 (any length) takes mask b*Q + j's
     string at 5 * off + 16 * rank (see include/zutis_hip.h), out_len int32 [B*Q] its length (-1: the caller encodes that mask itself)."""
-    L = _lib.load()
     _chk(pos_packed, torch.int32, "mask_rle_kept positions"); _chk(nr, torch.int32, "mask_rle_kept nruns"); _chk(kept_count, torch.int32, "kept_count")
     _chk(out, torch.uint8, "mask_rle_kept out"); _chk(out_len, torch.int32, "mask_rle_kept out_len")
-    _lib.check(L.zh_mask_rle_kept(_p(pos_packed), pos_packed.numel(), _p(nr), _p(kept_count), B, Q, max_runs, HW, _p(out), out.numel(), _p(out_len),
-                                  _stream()), "zh_mask_rle_kept")
+    _call("zh_mask_rle_kept", _p(pos_packed), pos_packed.numel(), _p(nr), _p(kept_count), B, Q, max_runs, HW, _p(out), out.numel(), _p(out_len),
+          _stream())
 
 
 def mask_rle_fused_supported(H, W, max_runs) -> bool:
@@ -528,7 +496,6 @@ def mask_rle_fused_kept(masks_u8, kept_index, kept_count, max_runs, out, cursor,
     [B,Q] / kept_count int32 [B] = zh_mask_nms' outputs; out u8 (any length) takes the strings, cursor int32 [1] (zeroed by the caller)
     places them, info int32 [B*Q, 8] = (offset, length or -1, xmin, ymin, xmax, ymax, area, transitions) per kept slot.  bits: the masks
     bit-packed by mask_iou_counts(..., workspace=) — int64 [B, Q, (H*W + 63) // 64] — read instead of the bytes."""
-    L = _lib.load()
     _chk(masks_u8, torch.uint8, "mask_rle_fused_kept masks"); _chk(kept_index, torch.int32, "kept_index"); _chk(kept_count, torch.int32, "kept_count")
     _chk(out, torch.uint8, "mask_rle_fused_kept out"); _chk(cursor, torch.int32, "cursor"); _chk(info, torch.int32, "info")
     B, Q, H, W = masks_u8.shape
@@ -536,30 +503,27 @@ def mask_rle_fused_kept(masks_u8, kept_index, kept_count, max_runs, out, cursor,
         _chk(bits, torch.int64, "mask_rle_fused_kept bits")
         if bits.numel() != B * Q * ((H * W + 63) // 64):
             raise _lib.ZutisHipError(f"mask_rle_fused_kept: bits holds {bits.numel()} words, {B * Q * ((H * W + 63) // 64)} expected")
-    _lib.check(L.zh_mask_rle_fused_kept(_p(masks_u8), None if bits is None else _p(bits), _p(kept_index), _p(kept_count), B, Q, H, W, max_runs,
-                                        _p(out), out.numel(), _p(cursor), _p(info), _stream()), "zh_mask_rle_fused_kept")
+    _call("zh_mask_rle_fused_kept", _p(masks_u8), None if bits is None else _p(bits), _p(kept_index), _p(kept_count), B, Q, H, W, max_runs,
+          _p(out), out.numel(), _p(cursor), _p(info), _stream())
 
 
 # ---------------------------------------------------------------------------------------- bilateral solver (float64)
 def denormalize_u8(x, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """utils/utils.py:261-273 on device: x f32 [3,H,W] -> rgb u8 [H,W,3]."""
     import ctypes as C
-    L = _lib.load()
     _chk(x, f32, "denormalize x")
     _, H, W = x.shape
     out = torch.empty((H, W, 3), dtype=torch.uint8, device=x.device)
     m = (C.c_float * 3)(*[float(np.float32(v)) for v in mean])
     s = (C.c_float * 3)(*[float(np.float32(v)) for v in std])
-    _lib.check(L.zh_denormalize_u8(_p(x), _p(out), H, W, m, s, _stream()), "zh_denormalize_u8")
+    _call("zh_denormalize_u8", _p(x), _p(out), H, W, m, s, _stream())
     return out
 
 
 def bgrid_coords(rgb_u8, sigma_spatial=16, sigma_luma=16, sigma_chroma=8):
-    L = _lib.load()
     H, W, _ = rgb_u8.shape
     out = torch.empty((H * W, 5), dtype=torch.int32, device=rgb_u8.device)
-    _lib.check(L.zh_bgrid_coords(_p(rgb_u8), H, W, float(sigma_spatial), float(sigma_luma), float(sigma_chroma), _p(out), _stream()),
-               "zh_bgrid_coords")
+    _call("zh_bgrid_coords", _p(rgb_u8), H, W, float(sigma_spatial), float(sigma_luma), float(sigma_chroma), _p(out), _stream())
     return out
 
 
@@ -568,14 +532,13 @@ def bilateral_solve(rgb_u8, target, sigma_spatial=16, sigma_luma=16, sigma_chrom
     """rgb u8 [H,W,3] + target u8|f64 [H,W] (device) -> soft f64 [H,W] (device), stats int32 [2] (device)
     [, n, m f64 [H*W] when debug].  A batch ([B,H,W,3] + [B,H,W]) returns [B,H,W], [B,2] (, [B,H*W] x 2): one sequence of
     launches for all B images."""
-    L = _lib.load()
     batched = rgb_u8.dim() == 4
     r4 = rgb_u8 if batched else rgb_u8[None]
     t3 = target if batched else target[None]
     B, H, W, _ = r4.shape
     _chk(r4, torch.uint8, "rgb")
     assert t3.shape == (B, H, W) and t3.is_contiguous() and t3.dtype in (torch.uint8, torch.float64)
-    need = B * L.zh_bilateral_workspace_size(H, W, float(sigma_spatial), float(sigma_luma), float(sigma_chroma))
+    need = B * _lib.load(raw=True).zh_bilateral_workspace_size(H, W, float(sigma_spatial), float(sigma_luma), float(sigma_chroma))
     dev = r4.device
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     out = torch.empty((B, H, W), dtype=torch.float64, device=dev)
@@ -584,9 +547,9 @@ def bilateral_solve(rgb_u8, target, sigma_spatial=16, sigma_luma=16, sigma_chrom
     m = torch.zeros((B, H * W), dtype=torch.float64, device=dev) if debug else None
     t8 = t3 if t3.dtype == torch.uint8 else None
     t64 = t3 if t3.dtype == torch.float64 else None
-    _lib.check(L.zh_bilateral_solve_batch(_p(r4), _p(t8), _p(t64), B, H, W, float(sigma_spatial), float(sigma_luma), float(sigma_chroma),
-                                          float(confidence), float(lam), float(a_diag_min), float(cg_tol), int(cg_maxiter), _p(out),
-                                          _p(stats), _p(n), _p(m), _p(ws), need, _stream()), "zh_bilateral_solve_batch")
+    _call("zh_bilateral_solve_batch", _p(r4), _p(t8), _p(t64), B, H, W, float(sigma_spatial), float(sigma_luma), float(sigma_chroma),
+          float(confidence), float(lam), float(a_diag_min), float(cg_tol), int(cg_maxiter), _p(out),
+          _p(stats), _p(n), _p(m), _p(ws), need, _stream())
     if not batched:
         out, stats = out[0], stats[0]
         n, m = (n[0], m[0]) if debug else (None, None)
@@ -595,27 +558,24 @@ def bilateral_solve(rgb_u8, target, sigma_spatial=16, sigma_luma=16, sigma_chrom
 
 def threshold_f64_u8(x, threshold=0.5):
     """x f64 (device, contiguous) -> u8 {0,1} of the same shape: x > threshold."""
-    L = _lib.load()
     _chk(x, torch.float64, "threshold x")
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    _lib.check(L.zh_threshold_f64_u8(_p(x), float(threshold), _p(out), x.numel(), _stream()), "zh_threshold_f64_u8")
+    _call("zh_threshold_f64_u8", _p(x), float(threshold), _p(out), x.numel(), _stream())
     return out
 
 
 def select_upsample_mask(obj, masks, out_u8, index, B, Q, h, w, H, W, scale_h, scale_w, threshold=0.5):
-    L = _lib.load()
     _chk(obj, f32, "objectness"); _chk(masks, f32, "masks"); _chk(out_u8, torch.uint8, "mask out")
-    _lib.check(L.zh_select_upsample_mask(_p(obj), _p(masks), _p(out_u8), _p(index), B, Q, h, w, H, W, float(scale_h), float(scale_w),
-                                         float(threshold), _stream()), "zh_select_upsample_mask")
+    _call("zh_select_upsample_mask", _p(obj), _p(masks), _p(out_u8), _p(index), B, Q, h, w, H, W, float(scale_h), float(scale_w),
+          float(threshold), _stream())
 
 
 def resize_nearest_u8(x_u8, H, W):
     """F.interpolate(x[None,None], size=(H,W), mode="nearest")[0,0] for a u8 [h,w] mask on the GPU."""
-    L = _lib.load()
     _chk(x_u8, torch.uint8, "resize_nearest x")
     h, w = x_u8.shape
     out = torch.empty((H, W), dtype=torch.uint8, device=x_u8.device)
-    _lib.check(L.zh_resize_nearest_u8(_p(x_u8), _p(out), h, w, H, W, lin_scale(h, H), lin_scale(w, W), _stream()), "zh_resize_nearest_u8")
+    _call("zh_resize_nearest_u8", _p(x_u8), _p(out), h, w, H, W, lin_scale(h, H), lin_scale(w, W), _stream())
     return out
 
 
@@ -623,7 +583,6 @@ def topk_rows(scores, k, N=None, with_values=False, idx_map=None, idx_add=0, out
     """scores f32 [R, ld] on the GPU -> int64 [R,k] indices of the k largest of the first N columns (score desc, column asc).
     Reported index of column i = idx_map[r, i] (int64 [R, ld]) if given, else i + idx_add.  out_idx / out_val may be column
     blocks [R, k] of wider row-major tables (same row stride for both)."""
-    L = _lib.load()
     _chk(scores, f32, "topk scores")
     R, ld = scores.shape
     N = ld if N is None else N
@@ -635,14 +594,12 @@ def topk_rows(scores, k, N=None, with_values=False, idx_map=None, idx_add=0, out
     val = (torch.empty((R, k), dtype=f32, device=scores.device) if out_val is None else out_val) if with_values else None
     if idx.dtype != torch.int64 or idx.stride(1) != 1 or (val is not None and (val.dtype != f32 or val.stride() != idx.stride())):
         raise _lib.ZutisHipError("topk_rows: outputs must be int64 / f32 row-major blocks with equal row strides")
-    _lib.check(L.zh_topk_rows(_p(scores), ld, R, N, k, _p(idx_map), int(idx_add), _p(idx), _p(val), idx.stride(0), _stream()),
-               "zh_topk_rows")
+    _call("zh_topk_rows", _p(scores), ld, R, N, k, _p(idx_map), int(idx_add), _p(idx), _p(val), idx.stride(0), _stream())
     return (idx, val) if with_values else idx
 
 
 def mask_runs(masks_u8, sel, max_runs=8192):
     """masks u8 [n,H,W] (device), sel int32 [m] (device) -> (positions int32 [m,max_runs], nruns int32 [m,2], box_area int32 [m,5])."""
-    L = _lib.load()
     _chk(masks_u8, torch.uint8, "mask_runs masks")
     _chk(sel, torch.int32, "mask_runs sel")
     n, H, W = masks_u8.shape
@@ -650,9 +607,8 @@ def mask_runs(masks_u8, sel, max_runs=8192):
     pos = torch.empty((m, max_runs), dtype=torch.int32, device=masks_u8.device)
     nr = torch.empty((m, 2), dtype=torch.int32, device=masks_u8.device)
     ba = torch.empty((m, 5), dtype=torch.int32, device=masks_u8.device)
-    need = int(_lib.load(raw=True).zh_mask_runs_workspace_size(m, W))
-    ws = torch.empty(need, dtype=torch.uint8, device=masks_u8.device)
-    _lib.check(L.zh_mask_runs(_p(masks_u8), _p(sel), m, H, W, max_runs, _p(pos), _p(nr), _p(ba), _p(ws), need, _stream()), "zh_mask_runs")
+    ws, need = _workspace("zh_mask_runs_workspace_size", masks_u8.device, m, W)
+    _call("zh_mask_runs", _p(masks_u8), _p(sel), m, H, W, max_runs, _p(pos), _p(nr), _p(ba), _p(ws), need, _stream())
     return pos, nr, ba
 
 
@@ -661,21 +617,18 @@ def mask_runs(masks_u8, sel, max_runs=8192):
 def mask_match_cost(proposals, gt_u8, inst_off, n_max, H, W, costs, stat_p, stat_pg, stat_g, skip, status, weight_dice=1.0, weight_bce=1.0):
     """proposals f32 [B, L, Q, h, w]; gt_u8 [n_tot, H, W]; inst_off int32 [B + 1] (device).  Writes costs / stat_pg (image b's [L, n_b, Q]
     at L * inst_off[b] * Q), stat_p [B, L, Q], stat_g [n_tot], skip int32 [B] and ORs STATUS_RANGE into status (see zutis_hip.h)."""
-    L = _lib.load()
     _chk(proposals, f32, "mask_match_cost proposals")
     _chk(gt_u8, torch.uint8, "mask_match_cost gt_u8")
     _chk(inst_off, torch.int32, "mask_match_cost inst_off")
     B, Ly, Q, h, w = proposals.shape
-    need = int(_lib.load(raw=True).zh_mask_match_cost_workspace_size(B, Ly, Q, H, n_max))
-    ws = torch.empty(need, dtype=torch.uint8, device=proposals.device)
-    _lib.check(L.zh_mask_match_cost(_p(proposals), _p(gt_u8) if gt_u8.numel() else None, _p(inst_off), _p(costs), _p(stat_p), _p(stat_pg),
-                                    _p(stat_g), _p(skip), _p(status), B, Ly, Q, h, w, H, W, n_max, float(weight_dice), float(weight_bce),
-                                    lin_scale(h, H), lin_scale(w, W), _p(ws), need, _stream()), "zh_mask_match_cost")
+    ws, need = _workspace("zh_mask_match_cost_workspace_size", proposals.device, B, Ly, Q, H, n_max)
+    _call("zh_mask_match_cost", _p(proposals), _p(gt_u8) if gt_u8.numel() else None, _p(inst_off), _p(costs), _p(stat_p), _p(stat_pg),
+          _p(stat_g), _p(skip), _p(status), B, Ly, Q, h, w, H, W, n_max, float(weight_dice), float(weight_bce),
+          lin_scale(h, H), lin_scale(w, W), _p(ws), need, _stream())
 
 
 def mask_match_grad(proposals, gt_u8, inst_off, pairs, stat_p, stat_pg, stat_g, grad_out, H, W, weight_dice, weight_bce, loss_scale, out=None):
     """pairs int32 [P, 4] = (b, l, q, i local) on the device -> grad f32 [B, L, Q, h, w] (0 outside the matched planes)."""
-    L = _lib.load()
     _chk(proposals, f32, "mask_match_grad proposals")
     _chk(pairs, torch.int32, "mask_match_grad pairs")
     _chk(grad_out, f32, "mask_match_grad grad_out")
@@ -683,45 +636,39 @@ def mask_match_grad(proposals, gt_u8, inst_off, pairs, stat_p, stat_pg, stat_g, 
     out = torch.empty_like(proposals) if out is None else out
     _chk(out, f32, "mask_match_grad out")
     n_pairs = pairs.shape[0]
-    _lib.check(L.zh_mask_match_grad(_p(proposals), _p(gt_u8) if gt_u8.numel() else None, _p(inst_off), _p(pairs) if n_pairs else None,
-                                    n_pairs, _p(stat_p), _p(stat_pg), _p(stat_g), _p(grad_out), _p(out), B, Ly, Q, h, w, H, W,
-                                    float(weight_dice), float(weight_bce), float(loss_scale), lin_scale(h, H), lin_scale(w, W), _stream()),
-               "zh_mask_match_grad")
+    _call("zh_mask_match_grad", _p(proposals), _p(gt_u8) if gt_u8.numel() else None, _p(inst_off), _p(pairs) if n_pairs else None,
+          n_pairs, _p(stat_p), _p(stat_pg), _p(stat_g), _p(grad_out), _p(out), B, Ly, Q, h, w, H, W,
+          float(weight_dice), float(weight_bce), float(loss_scale), lin_scale(h, H), lin_scale(w, W), _stream())
     return out
 
 
 def upsample_ce_fwd(logits_lo, labels, ignore_index, out, status, lse=None):
     """logits_lo f32 [B, n_cat, h, w], labels int64 [B, H, W] -> out f32 [2] = (mean NLL, valid count); lse f32 [B, H, W] returned."""
-    L = _lib.load()
     _chk(logits_lo, f32, "upsample_ce logits_lo")
     _chk(labels, torch.int64, "upsample_ce labels")
     B, n, h, w = logits_lo.shape
     H, W = labels.shape[-2:]
     lse = torch.empty((B, H, W), dtype=f32, device=logits_lo.device) if lse is None else lse
-    need = int(_lib.load(raw=True).zh_upsample_ce_workspace_size(B, H, W))
-    ws = torch.empty(need, dtype=torch.uint8, device=logits_lo.device)
-    _lib.check(L.zh_upsample_ce_fwd(_p(logits_lo), _p(labels), _p(lse), _p(out), _p(status), B, n, h, w, H, W, int(ignore_index),
-                                    lin_scale(h, H), lin_scale(w, W), _p(ws), need, _stream()), "zh_upsample_ce_fwd")
+    ws, need = _workspace("zh_upsample_ce_workspace_size", logits_lo.device, B, H, W)
+    _call("zh_upsample_ce_fwd", _p(logits_lo), _p(labels), _p(lse), _p(out), _p(status), B, n, h, w, H, W, int(ignore_index),
+          lin_scale(h, H), lin_scale(w, W), _p(ws), need, _stream())
     return lse
 
 
 def upsample_ce_bwd(logits_lo, labels, lse, ce_out, grad_out, ignore_index, out=None):
-    L = _lib.load()
     _chk(logits_lo, f32, "upsample_ce_bwd logits_lo")
     _chk(grad_out, f32, "upsample_ce_bwd grad_out")
     B, n, h, w = logits_lo.shape
     H, W = labels.shape[-2:]
     out = torch.empty_like(logits_lo) if out is None else out
-    _lib.check(L.zh_upsample_ce_bwd(_p(logits_lo), _p(labels), _p(lse), _p(ce_out), _p(grad_out), _p(out), B, n, h, w, H, W,
-                                    int(ignore_index), lin_scale(h, H), lin_scale(w, W), _stream()), "zh_upsample_ce_bwd")
+    _call("zh_upsample_ce_bwd", _p(logits_lo), _p(labels), _p(lse), _p(ce_out), _p(grad_out), _p(out), B, n, h, w, H, W,
+          int(ignore_index), lin_scale(h, H), lin_scale(w, W), _stream())
     return out
 
 
 def gemm_f32_strided(A, a_strides, Bm, b_strides, C, c_strides, batch, M, N, K):
     """C[t](m, n) = sum_k A[t](m, k) Bm[t](n, k); *_strides = (batch, row, k) / (batch, m, n) in elements; fp32 tensors."""
-    L = _lib.load()
     for t, nm in ((A, "A"), (Bm, "B"), (C, "C")):
         if t.dtype != f32:
             raise _lib.ZutisHipError(f"gemm_f32_strided {nm}: expected float32, got {t.dtype}")
-    _lib.check(L.zh_gemm_f32_strided(_p(A), *a_strides, _p(Bm), *b_strides, _p(C), *c_strides, batch, M, N, K, _stream()),
-               "zh_gemm_f32_strided")
+    _call("zh_gemm_f32_strided", _p(A), *a_strides, _p(Bm), *b_strides, _p(C), *c_strides, batch, M, N, K, _stream())
