@@ -11,17 +11,18 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libzutis_hip.so")
-# float64 bilateral solver: no FMA contraction (bin edges and bistochastisation are bit-compared with NumPy/SciPy)
-EXTRA_FLAGS = {"bilateral.hip": ["-ffp-contract=off"]}
+# float64 bilateral solver: no FMA contraction (bin edges and bistochastisation are bit-compared with NumPy/SciPy);
+# preprocess.hip: Pillow's resampling coefficients are bit-compared with the host's double arithmetic
+EXTRA_FLAGS = {"bilateral.hip": ["-ffp-contract=off"], "preprocess.hip": ["-ffp-contract=off"]}
 # the MFMA kernels live at the register budget of their occupancy: a spill is a 2-3x slowdown, so it is a build error
-NO_SCRATCH = {"gemm.hip", "gemm_x3.hip", "attention.hip"}
+NO_SCRATCH = {"gemm.hip", "gemm_x3.hip", "attention.hip", "preprocess.hip"}
 MAX_SCRATCH = int(os.environ.get("ZH_BUILD_MAX_SCRATCH", "0"))    # bytes per lane tolerated: the MFMA loops must not spill (developer builds may raise it)
 # waves per SIMD the design of a kernel relies on (source -> mangled-name substring -> minimum), checked against the compiler's
 # remarks; a key that matches no kernel of its source is a build error (a renamed template would otherwise drop its guard)
 MIN_OCCUPANCY = {"attention.hip": {"attn_f16_kernelILi64ELi4ELi1ELi0EE": 3, "attn_f16_kernelILi64ELi4ELi0ELi0EE": 3,
                                    "attn_f16_kernelILi64ELi4ELi1ELi1EE": 2, "attn_f16_kernelILi96ELi4ELi1ELi0EE": 2,
                                    "attn_f16_kernelILi96ELi4ELi0ELi0EE": 2, "attn_f16_kernelILi96ELi4ELi1ELi1EE": 2}}
-SOURCES = ["capi.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "bilateral.hip", "retrieval.hip", "text.hip", "criterion.hip", "plan.hip"]
+SOURCES = ["capi.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "plan.hip"]
 
 
 def _hipcc() -> str:

@@ -11,8 +11,11 @@ which is the reference's own storage class for this tower: the stream is rounded
 (the Linear's output, then the sum — what an fp16 `x + linear(y)` does), LayerNorm statistics / accumulators / softmax / QuickGELU
 stay fp32.  Every mode returns unit-norm fp32 embeddings.  Weights come from `clip.load` when the package is present, else from
 `state_dict=`.
-Pre-processing (bicubic resize of the shorter side, centre crop, CLIP mean/std; SimpleDataset :90-116) is PIL + NumPy
-on the host — data loading is outside the hot path.
+Pre-processing (bicubic resize of the shorter side, centre crop, CLIP mean/std; SimpleDataset :90-116): `n_workers` threads (at most
+16; the reference's DataLoader workers, :64-65) open and decode the files one batch ahead (zutis_amd.preprocess.BatchLoader), the decoded
+bytes cross to the device in one copy per batch, and one kernel (ops.resize_crop_normalize) resizes, crops and normalises them — the
+very bytes of Pillow's resampler and the very fp32 values of `_preprocess`, which stays here as the host statement of the same
+transform (the tests' reference), so the embeddings are bit for bit those of the host path.
 """
 import os
 import pickle as pkl
@@ -22,6 +25,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from zutis_amd import ops, preprocess
 from zutis_amd.engine import ClipImageEncoder
 
 _MEAN = np.array((0.48145466, 0.4578275, 0.40821073), np.float32)
@@ -71,10 +75,14 @@ def extract_image_embeddings(
     enc = ClipImageEncoder(vis, patch, prefix="visual.", precision=precision)
     n_px = patch * enc.grid
     out: Dict[str, torch.Tensor] = {}
-    for i in range(0, len(p_images), batch_size):
-        chunk = p_images[i:i + batch_size]
-        x = torch.from_numpy(np.stack([_preprocess(p, n_px) for p in chunk])).to(device)
-        emb = enc.encode_image(x).cpu()                                 # L2-normalised, fp32 (reference :72-76)
+    lut = torch.from_numpy(preprocess.normalise_table(_MEAN, _STD)).to(device)
+    loader = preprocess.BatchLoader(p_images, n_px, batch_size, n_workers, resize_crop_box)
+    for k, batch in enumerate(loader):
+        i, chunk = k * batch_size, batch.paths
+        packed, desc = preprocess.split_staging(batch.staging.to(device, non_blocking=True), len(chunk))   # one H2D: descriptors + bytes
+        x = ops.resize_crop_normalize(packed, desc, n_px, lut, kmax=batch.kmax)
+        emb = enc.encode_image(x).cpu()                                 # L2-normalised, fp32 (reference :72-76); the copy back is the
+                                                                        # synchronisation after which the loader may reuse the staging buffer
         for p, e in zip(chunk, emb):
             out[os.path.basename(p)] = e.clone()
         if fp is not None and ((i // batch_size) % max(1, (len(p_images) // batch_size) // 20) == 0 or i + batch_size >= len(p_images)):

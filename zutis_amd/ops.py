@@ -507,6 +507,29 @@ def mask_rle_fused_kept(masks_u8, kept_index, kept_count, max_runs, out, cursor,
           _p(out), out.numel(), _p(cursor), _p(info), _stream())
 
 
+# ---------------------------------------------------------------------------------------- CLIP image pre-processing
+RCN_KMAX = 152      # include/zutis_hip.h ZH_RCN_KMAX
+
+
+def resize_crop_normalize(packed, desc, n_px: int, lut, out=None, kmax: Optional[int] = None):
+    """utils/extract_image_embeddings.py:97-103 (Resize BICUBIC, CenterCrop, ToTensor, Normalize) for a ragged batch in one launch,
+    bit-identical to Pillow + NumPy: packed u8 [bytes] (the decoded RGB images back to back at 16-byte-aligned offsets), desc int32
+    [B, 8] = (offset / 16, w, h, nw, nh, left, top, 0) per image, lut f32 [3, 256] (zutis_amd.preprocess.normalise_table) ->
+    f32 [B, 3, n_px, n_px].  kmax: the batch's largest tap count (zutis_amd.preprocess.ksize), which sizes the launch's LDS; None = the
+    largest the kernel serves.  An image whose descriptor does not fit comes back as NaN (include/zutis_hip.h)."""
+    _chk(packed, torch.uint8, "resize_crop_normalize packed"); _chk(desc, torch.int32, "resize_crop_normalize desc"); _chk(lut, f32, "resize_crop_normalize lut")
+    if packed.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 8 or desc.shape[0] == 0 or tuple(lut.shape) != (3, 256):
+        raise _lib.ZutisHipError(f"resize_crop_normalize: packed [bytes], desc [B, 8], lut [3, 256] expected, got {tuple(packed.shape)}, {tuple(desc.shape)}, {tuple(lut.shape)}")
+    B = desc.shape[0]
+    if out is None:
+        out = torch.empty((B, 3, n_px, n_px), dtype=f32, device=packed.device)
+    _chk(out, f32, "resize_crop_normalize out")
+    if tuple(out.shape) != (B, 3, n_px, n_px):
+        raise _lib.ZutisHipError(f"resize_crop_normalize: out {tuple(out.shape)}, expected {(B, 3, n_px, n_px)}")
+    _call("zh_resize_crop_normalize_u8", _p(packed), packed.numel(), _p(desc), B, n_px, RCN_KMAX if kmax is None else int(kmax), _p(lut), _p(out), _stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------- bilateral solver (float64)
 def denormalize_u8(x, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """utils/utils.py:261-273 on device: x f32 [3,H,W] -> rgb u8 [H,W,3]."""

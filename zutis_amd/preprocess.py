@@ -1,0 +1,219 @@
+"""Host side of the device pre-processing of embedding extraction (csrc/preprocess.hip, ops.resize_crop_normalize).
+
+The reference feeds CLIP through SimpleDataset's transform (utils/extract_image_embeddings.py:97-103: Resize BICUBIC, CenterCrop,
+ToTensor, Normalize) under a 16-worker DataLoader (:64-65).  Here the workers are THREADS that only open and decode (Pillow
+releases the GIL while it decodes); the resize, crop and normalisation run in one kernel per batch on the decoded bytes, which
+is also what crosses PCIe (3 bytes per source pixel instead of 12 per output pixel).
+
+  pil_resize_reference  NumPy restatement of Pillow's 8-bit bicubic resampler — the CPU oracle of the tests, not a product path
+  normalise_table       the 3 x 256 fp32 table the kernel looks normalised values up in
+  BatchLoader           paths -> batches of (packed bytes + descriptor rows) in reused staging buffers, decoded one batch ahead
+
+Threads, not processes: no child ever holds the device open, nothing is pickled, a worker's exception is raised by the caller.
+"""
+from __future__ import annotations
+
+import collections
+import math
+from concurrent.futures import ThreadPoolExecutor
+from typing import Callable, List, Sequence
+
+import numpy as np
+import torch
+from PIL import Image
+
+PRECISION_BITS = 32 - 8 - 2     # Pillow's fixed-point coefficients: src/libImaging/Resample.c
+KMAX = 152                      # taps per output pixel the kernel serves (include/zutis_hip.h ZH_RCN_KMAX)
+MAX_WORKERS = 16
+ALIGN = 16                      # byte alignment of an image inside the packed buffer (descriptors hold offset / 16)
+DESC_INTS = 8                   # offset / 16, w, h, nw, nh, left, top, 0
+
+
+def _bicubic(x: float) -> float:
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def ksize(in_size: int, out_size: int) -> int:
+    """Taps per output pixel of Pillow's bicubic resampler for in_size -> out_size (its coefficient row length)."""
+    return int(math.ceil(2.0 * max(in_size / out_size, 1.0))) * 2 + 1
+
+
+def pil_coefficients(in_size: int, out_size: int):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for the bicubic filter: (K int64 [out, ksize], bounds int64 [out, 2] =
+    (first source index, tap count)).  IEEE double, the weights summed in tap order, rounding half away from zero."""
+    scale = filterscale = in_size / out_size
+    if filterscale < 1.0:
+        filterscale = 1.0
+    support = 2.0 * filterscale
+    ks = int(math.ceil(support)) * 2 + 1
+    kk = np.zeros((out_size, ks), np.int64)
+    bounds = np.zeros((out_size, 2), np.int64)
+    ss = 1.0 / filterscale
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        for x, v in enumerate(w):
+            if ww != 0.0:
+                v /= ww
+            kk[xx, x] = int(-0.5 + v * (1 << PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PRECISION_BITS))
+        bounds[xx] = (xmin, xmax)
+    return kk, bounds
+
+
+def _pass(a: np.ndarray, out_size: int) -> np.ndarray:
+    """a u8 [L, in, C] -> u8 [L, out, C]: one resampling pass along axis 1."""
+    kk, bounds = pil_coefficients(a.shape[1], out_size)
+    out = np.empty((a.shape[0], out_size, a.shape[2]), np.uint8)
+    ai = a.astype(np.int64)
+    for xx in range(out_size):
+        xmin, n = bounds[xx]
+        s = (1 << (PRECISION_BITS - 1)) + np.tensordot(ai[:, xmin:xmin + n, :], kk[xx, :n], ([1], [0]))
+        out[:, xx, :] = np.clip(s >> PRECISION_BITS, 0, 255)
+    return out
+
+
+def pil_resize_reference(a_u8: np.ndarray, nw: int, nh: int) -> np.ndarray:
+    """Image.fromarray(a_u8).resize((nw, nh), Image.BICUBIC) for a u8 [h, w, C] array, byte for byte: horizontal pass to a u8
+    intermediate, then vertical; a pass whose size does not change is skipped, as Pillow skips it."""
+    a = np.ascontiguousarray(a_u8)
+    if a.dtype != np.uint8 or a.ndim != 3:
+        raise ValueError("pil_resize_reference: u8 [h, w, C] expected")
+    h, w, _ = a.shape
+    if nw != w:
+        a = _pass(a, nw)
+    if nh != h:
+        a = _pass(a.transpose(1, 0, 2), nh).transpose(1, 0, 2)
+    return np.ascontiguousarray(a)
+
+
+def normalise_table(mean, std) -> np.ndarray:
+    """fp32 [3, 256]: table[c][v] = (float32(v) / 255.0 - mean[c]) / std[c] in NumPy's fp32, the very expression the host
+    pre-processing applies to a cropped image — gathering the table over the bytes gives its result bit for bit."""
+    mean, std = np.asarray(mean, np.float32), np.asarray(std, np.float32)
+    a = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)          # [256, 3] as an H x W x 3 image row would be
+    a = np.asarray(a, np.float32) / 255.0
+    return np.ascontiguousarray(((a - mean) / std).T)
+
+
+def _taps_ok(w: int, h: int, nw: int, nh: int) -> bool:
+    return ksize(w, nw) <= KMAX and ksize(h, nh) <= KMAX and 3 * w * h < 2 ** 31
+
+
+def device_supported(w: int, h: int, n_px: int) -> bool:
+    """Whether the kernel resizes a w x h source itself when its shorter side becomes n_px (Resize's convention): both axes within
+    KMAX taps per output pixel (a shorter side up to ~37 x n_px: 8400 pixels at 224) and the packed image addressable.
+    Anything else the loader resizes on the host."""
+    nw, nh = (n_px, int(n_px * h / w)) if w <= h else (int(n_px * w / h), n_px)
+    return nw > 0 and nh > 0 and _taps_ok(w, h, nw, nh)
+
+
+Batch = collections.namedtuple("Batch", "paths staging packed desc kmax n_host")
+Batch.__doc__ = """One decoded batch.  staging: u8 tensor [32 * B + pixel bytes] (pinned when the loader pins), descriptor rows first —
+one host-to-device copy moves both; packed / desc: its two views (u8 [bytes], int32 [B, 8]), offsets relative to `packed`; kmax: the
+batch's largest tap count; n_host: images that were resized on the host (outside device_supported).  Valid until the loader is advanced."""
+
+
+def split_staging(staging: torch.Tensor, B: int):
+    """(packed, desc) views of a staging tensor (host or device) laid out as BatchLoader lays it out."""
+    return staging[B * DESC_INTS * 4:], staging[:B * DESC_INTS * 4].view(torch.int32).view(B, DESC_INTS)
+
+
+class BatchLoader:
+    """Iterate over `paths` in batches of `batch_size`: a pool of min(n_workers, 16) threads reads the headers, then decodes every
+    image (`Image.open(p).convert("RGB")`) straight into its slice of one of two reused staging buffers; the next batch decodes while
+    the caller works on the current one.  `box(w, h, n_px)` gives ((nw, nh), (left, top)) of the resize and crop.  An image the kernel
+    does not serve (device_supported) is resized and cropped by Pillow in its worker and packed as an n_px x n_px image whose two
+    passes are the identity.  The order of a batch is the order of its paths; a worker's exception (a missing or unreadable file) is
+    raised by the iteration step that needs the batch, at the latest.
+    The caller must be done reading a batch (its host-to-device copy complete) before it advances the loader."""
+
+    def __init__(self, paths: Sequence[str], n_px: int, batch_size: int, n_workers: int, box: Callable, pin=None):
+        if batch_size < 1 or n_px < 1:
+            raise ValueError("BatchLoader: batch_size and n_px must be positive")
+        self.paths, self.n_px, self.batch_size, self.box = list(paths), int(n_px), int(batch_size), box
+        self.n_threads = max(1, min(int(n_workers), MAX_WORKERS))
+        self.pin = torch.cuda.is_available() if pin is None else bool(pin)
+        self._buffers: List[torch.Tensor] = [torch.empty(0, dtype=torch.uint8), torch.empty(0, dtype=torch.uint8)]
+
+    def __len__(self):
+        return (len(self.paths) + self.batch_size - 1) // self.batch_size
+
+    def _staging(self, slot: int, nbytes: int) -> torch.Tensor:
+        """The slot's staging buffer, grown (from the calling thread) when the batch needs more."""
+        if self._buffers[slot].numel() < nbytes:
+            self._buffers[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=self.pin)
+        return self._buffers[slot][:nbytes]
+
+    @staticmethod
+    def _size(path: str):
+        with Image.open(path) as im:            # header only
+            return im.size
+
+    def _decode(self, path: str, dst: np.ndarray, size, host_box):
+        im = Image.open(path).convert("RGB")
+        if im.size != size:
+            raise ValueError(f"{path}: decoded size {im.size} differs from its header's {size}")
+        if host_box is not None:
+            (nw, nh), (left, top) = host_box
+            im = im.resize((nw, nh), Image.BICUBIC).crop((left, top, left + self.n_px, top + self.n_px))
+        np.copyto(dst, np.asarray(im))
+
+    def _submit(self, pool: ThreadPoolExecutor, k: int):
+        """Fix batch k's layout from the headers and start its decodes: (Batch, futures)."""
+        chunk = self.paths[k * self.batch_size:(k + 1) * self.batch_size]
+        sizes = list(pool.map(self._size, chunk))
+        B, n = len(chunk), self.n_px
+        rows = np.zeros((B, DESC_INTS), np.int32)
+        host_boxes, shapes, kmax, off = [], [], 5, 0
+        for i, (w, h) in enumerate(sizes):
+            bx = self.box(w, h, n)
+            (nw, nh), (left, top) = bx
+            if _taps_ok(w, h, nw, nh):
+                host_boxes.append(None)
+            else:
+                host_boxes.append(bx)
+                w = h = nw = nh = n
+                left = top = 0
+            kmax = max(kmax, ksize(w, nw), ksize(h, nh))
+            rows[i] = (off // ALIGN, w, h, nw, nh, left, top, 0)
+            shapes.append((off, h, w))
+            off += -(-3 * w * h // ALIGN) * ALIGN
+        head = B * DESC_INTS * 4
+        staging = self._staging(k % 2, head + off)
+        packed, desc = split_staging(staging, B)
+        desc.numpy()[...] = rows
+        pix = packed.numpy()
+        futures = [pool.submit(self._decode, p, pix[o:o + 3 * w * h].reshape(h, w, 3), size, hb)
+                   for p, (o, h, w), size, hb in zip(chunk, shapes, sizes, host_boxes)]
+        return Batch(chunk, staging, packed, desc, kmax, sum(hb is not None for hb in host_boxes)), futures
+
+    def __iter__(self):
+        n_batches = len(self)
+        if n_batches == 0:
+            return
+        with ThreadPoolExecutor(max_workers=self.n_threads, thread_name_prefix="zutis-decode") as pool:
+            pending = self._submit(pool, 0)
+            try:
+                for k in range(n_batches):
+                    batch, futures = pending
+                    pending = None
+                    for f in futures:
+                        f.result()              # raises what the worker raised
+                    if k + 1 < n_batches:
+                        pending = self._submit(pool, k + 1)
+                    yield batch
+            finally:
+                if pending is not None:
+                    for f in pending[1]:
+                        f.cancel()
