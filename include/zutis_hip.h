@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 228 /* 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 229 /* 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -304,6 +304,17 @@ int zh_mask_iou_counts(const unsigned char* masks, int n, long pixels, int* inte
 #define ZH_RCN_KMAX 152
 int zh_resize_crop_normalize_u8(const unsigned char* packed, long packed_bytes, const int* desc, int B, int n_px, int kmax,
                                 const float* lut, float* out, zh_stream_t stream);
+/* MaskDataset's transform, datasets/index_dataset.py:405-411 — TF.resize(image, image_size, BILINEAR) + to_tensor + normalize — for B
+ * decoded RGB images of different sizes that all resize to ONE out_w x out_h, in one launch and with no crop: the same two-pass
+ * 8-bit resampler with Pillow's filter `filter` (ZH_FILTER_BILINEAR: the triangle 1 - |x| of support 1, taps per output pixel
+ * ceil(max(in / out, 1)) * 2 + 1; ZH_FILTER_BICUBIC: as above), bit-identical to Image.resize((out_w, out_h), filter) followed by
+ * the fp32 (v / 255 - mean) / std.  packed, desc, lut, kmax as for zh_resize_crop_normalize_u8 (kmax >= 3 for bilinear); a pass whose
+ * size does not change has identity coefficients (Pillow skips it).  out f32 [B, 3, out_h, out_w].  A descriptor whose
+ * (nw, nh, left, top) is not (out_w, out_h, 0, 0), or that does not fit as above, gets NaN and is not read. */
+#define ZH_FILTER_BILINEAR 2 /* PIL.Image.BILINEAR */
+#define ZH_FILTER_BICUBIC 3  /* PIL.Image.BICUBIC */
+int zh_resize_normalize_u8(const unsigned char* packed, long packed_bytes, const int* desc, int B, int out_h, int out_w, int filter,
+                           int kmax, const float* lut, float* out, zh_stream_t stream);
 
 /* ---- bilateral solver (SelfMask refinement), utils/bilateral_solver.py:40-195; float64 ---- */
 /* convert_tensor_to_pil_image, utils/utils.py:261-273: fp32 x*std+mean, *255, clip, TRUNCATE.  x f32 [3,H,W] (device)

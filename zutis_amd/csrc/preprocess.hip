@@ -19,6 +19,13 @@
 // LDS = 96 * kmax ints for the coefficient sets, sized per launch by the caller's `kmax` (the largest tap count of the batch:
 // 7 for a 500 x 375 photograph at 336, 149 for an 8192-pixel shorter side at 224), so the common case keeps full occupancy.
 // Bound: bytes — sum 3 w h read + 12 n_px^2 written per image.
+//
+// The same kernel, instantiated on the filter and with a rectangular out_h x out_w output, is MaskDataset's transform
+// (datasets/index_dataset.py:405-411: TF.resize(image, 512, BILINEAR) + to_tensor + normalize) for a batch whose images all
+// resize to ONE shape: Pillow's BILINEAR is the same two-pass code with the triangle filter of support 1 (3 taps per axis when
+// up-scaling).  There a 375 x 500 photograph becomes 512 x 682: 0.56 MB read, 4.2 MB written — store-bound, every wave's store
+// is 64 consecutive floats of one plane row, and the 32 x 64 tile gives 11 x 16 workgroups per image (1408 at eight images, 5.5 per
+// CU) with 3 % of the lanes idle (the last tile column).
 #include "common.h"
 
 #define RCN_TX 64       // output columns per workgroup (= lanes)
@@ -28,25 +35,33 @@
 #define RCN_KMAX 152    // include/zutis_hip.h ZH_RCN_KMAX: 96 * 152 * 4 + 768 bytes of LDS < 64 KiB
 #define RCN_PRECISION_BITS 22
 
-__device__ __forceinline__ double bicubic_filter(double x) {
-  const double a = -0.5;
+#define RCN_BILINEAR 2  // include/zutis_hip.h ZH_FILTER_BILINEAR / ZH_FILTER_BICUBIC
+#define RCN_BICUBIC 3
+
+// Pillow's filter functions (Resample.c: bilinear_filter, bicubic_filter) and their supports
+template <int FILTER>
+__device__ __forceinline__ double rcn_filter(double x) {
   if (x < 0.0) x = -x;
+  if (FILTER == RCN_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
+  const double a = -0.5;
   if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
   if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
   return 0.0;
 }
 
+template <int FILTER>
 __host__ __device__ __forceinline__ int rcn_ksize(int in_size, int out_size) {
   double fs = (double)in_size / (double)out_size;
   if (fs < 1.0) fs = 1.0;
-  return (int)ceil(2.0 * fs) * 2 + 1;
+  return (int)ceil((FILTER == RCN_BILINEAR ? 1.0 : 2.0) * fs) * 2 + 1;
 }
 
 // precompute_coeffs + normalize_coeffs_8bpc for ONE output index xx: taps K[0 .. count) (stride `stride` ints), first source index xmin
+template <int FILTER>
 __device__ void rcn_coeffs(int in_size, int out_size, int xx, int* K, int stride, int& xmin_out, int& count_out) {
   const double scale = (double)in_size / (double)out_size;
   const double fs = scale < 1.0 ? 1.0 : scale;
-  const double support = 2.0 * fs, ss = 1.0 / fs;
+  const double support = (FILTER == RCN_BILINEAR ? 1.0 : 2.0) * fs, ss = 1.0 / fs;
   const double center = (xx + 0.5) * scale;
   int xmin = (int)(center - support + 0.5);
   if (xmin < 0) xmin = 0;
@@ -54,9 +69,9 @@ __device__ void rcn_coeffs(int in_size, int out_size, int xx, int* K, int stride
   if (xmax > in_size) xmax = in_size;
   xmax -= xmin;
   double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) ww += bicubic_filter((x + xmin - center + 0.5) * ss);
+  for (int x = 0; x < xmax; ++x) ww += rcn_filter<FILTER>((x + xmin - center + 0.5) * ss);
   for (int x = 0; x < xmax; ++x) {
-    double k = bicubic_filter((x + xmin - center + 0.5) * ss);
+    double k = rcn_filter<FILTER>((x + xmin - center + 0.5) * ss);
     if (ww != 0.0) k /= ww;
     K[x * stride] = k < 0.0 ? (int)(-0.5 + k * (double)(1 << RCN_PRECISION_BITS)) : (int)(0.5 + k * (double)(1 << RCN_PRECISION_BITS));
   }
@@ -69,10 +84,11 @@ __device__ __forceinline__ int rcn_clip8(int s) {
   return s < 0 ? 0 : (s > 255 ? 255 : s);
 }
 
-// desc row (8 int32): offset / 16, w, h, nw, nh, left, top, 0
+// desc row (8 int32): offset / 16, w, h, nw, nh, left, top, 0; the output is the out_h x out_w window at (left, top) of the resized image
+template <int FILTER>
 __global__ __launch_bounds__(RCN_TX * RCN_WAVES) void resize_crop_normalize_kernel(
-    const unsigned char* __restrict__ packed, long packed_bytes, const int* __restrict__ desc, int n_px, int kmax,
-    const float* __restrict__ lut, float* __restrict__ out, int tiles_x) {
+    const unsigned char* __restrict__ packed, long packed_bytes, const int* __restrict__ desc, int out_h, int out_w, int kmax,
+    const float* __restrict__ lut, float* __restrict__ out, int tiles_x, int whole) {
   extern __shared__ int rcn_lds[];
   int* Kx = rcn_lds;                                // [kmax][RCN_TX]
   int* Ky = Kx + kmax * RCN_TX;                     // [RCN_TY][kmax]
@@ -87,33 +103,35 @@ __global__ __launch_bounds__(RCN_TX * RCN_WAVES) void resize_crop_normalize_kern
   const size_t off = (size_t)(unsigned)d[0] * 16;
   const int w = d[1], h = d[2], nw = d[3], nh = d[4], left = d[5], top = d[6];
   const int ox = tx * RCN_TX + lane;                // this lane's output column
-  float* o = out + (size_t)b * 3 * n_px * n_px;
-  const size_t plane = (size_t)n_px * n_px;
+  const size_t plane = (size_t)out_h * out_w;
+  float* o = out + (size_t)b * 3 * plane;
 
-  // a descriptor this launch cannot serve (outside the packed buffer, crop outside the resized image, more taps than kmax):
+  // a descriptor this launch cannot serve (outside the packed buffer, crop outside the resized image, more taps than kmax; `whole`:
+  // anything but the whole resized image):
   // the image's output is NaN — nothing is read through it
-  bool ok = w > 0 && h > 0 && nw > 0 && nh > 0 && left >= 0 && top >= 0 && (long)left + n_px <= nw && (long)top + n_px <= nh;
+  bool ok = w > 0 && h > 0 && nw > 0 && nh > 0 && left >= 0 && top >= 0 && (long)left + out_w <= nw && (long)top + out_h <= nh;
+  ok = ok && (!whole || (nw == out_w && nh == out_h && left == 0 && top == 0));
   ok = ok && (long)off + 3l * w * h <= packed_bytes;
-  ok = ok && rcn_ksize(w, nw) <= kmax && rcn_ksize(h, nh) <= kmax;
+  ok = ok && rcn_ksize<FILTER>(w, nw) <= kmax && rcn_ksize<FILTER>(h, nh) <= kmax;
   if (!ok) {
-    if (ox < n_px)
+    if (ox < out_w)
       for (int r = 0; r < RCN_RY; ++r) {
         const int oy = ty * RCN_TY + wave * RCN_RY + r;
-        if (oy < n_px)
-          for (int c = 0; c < 3; ++c) o[c * plane + (size_t)oy * n_px + ox] = __builtin_nanf("");
+        if (oy < out_h)
+          for (int c = 0; c < 3; ++c) o[c * plane + (size_t)oy * out_w + ox] = __builtin_nanf("");
       }
     return;
   }
 
   if (tid < RCN_TX) {
     int mn = 0, cnt = 0;
-    if (ox < n_px) rcn_coeffs(w, nw, left + ox, Kx + tid, RCN_TX, mn, cnt);
+    if (ox < out_w) rcn_coeffs<FILTER>(w, nw, left + ox, Kx + tid, RCN_TX, mn, cnt);
     x_min[tid] = mn;
     x_cnt[tid] = cnt;
   } else if (tid < RCN_TX + RCN_TY) {
     const int r = tid - RCN_TX, oy = ty * RCN_TY + r;
     int mn = 0, cnt = 0;
-    if (oy < n_px) rcn_coeffs(h, nh, top + oy, Ky + r * kmax, 1, mn, cnt);
+    if (oy < out_h) rcn_coeffs<FILTER>(h, nh, top + oy, Ky + r * kmax, 1, mn, cnt);
     y_min[r] = mn;
     y_cnt[r] = cnt;
   }
@@ -159,16 +177,25 @@ __global__ __launch_bounds__(RCN_TX * RCN_WAVES) void resize_crop_normalize_kern
     }
   }
 
-  if (ox < n_px) {
+  if (ox < out_w) {
 #pragma unroll
     for (int r = 0; r < RCN_RY; ++r) {
       const int oy = ty * RCN_TY + wave * RCN_RY + r;
-      if (oy < n_px) {
+      if (oy < out_h) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) o[c * plane + (size_t)oy * n_px + ox] = lut[c * 256 + rcn_clip8(acc[r][c])];
+        for (int c = 0; c < 3; ++c) o[c * plane + (size_t)oy * out_w + ox] = lut[c * 256 + rcn_clip8(acc[r][c])];
       }
     }
   }
+}
+
+template <int FILTER>
+static void rcn_launch(const unsigned char* packed, long packed_bytes, const int* desc, int B, int out_h, int out_w, int kmax,
+                       const float* lut, float* out, int whole, hipStream_t stream) {
+  const int tiles_x = zh_cdiv(out_w, RCN_TX), tiles_y = zh_cdiv(out_h, RCN_TY);
+  const size_t lds = ((size_t)(RCN_TX + RCN_TY) * kmax + 2 * (RCN_TX + RCN_TY)) * sizeof(int);
+  hipLaunchKernelGGL(resize_crop_normalize_kernel<FILTER>, dim3(tiles_x * tiles_y, B), dim3(RCN_TX * RCN_WAVES), lds, stream,
+                     packed, packed_bytes, desc, out_h, out_w, kmax, lut, out, tiles_x, whole);
 }
 
 extern "C" int zh_resize_crop_normalize_u8(const unsigned char* packed, long packed_bytes, const int* desc, int B, int n_px, int kmax,
@@ -179,10 +206,24 @@ extern "C" int zh_resize_crop_normalize_u8(const unsigned char* packed, long pac
   ZH_CHECK_ARG(((uintptr_t)packed & 15) == 0, "zh_resize_crop_normalize_u8: packed must be 16-byte aligned");
   ZH_CHECK_ARG(kmax >= 5 && kmax <= RCN_KMAX, "zh_resize_crop_normalize_u8: kmax %d outside [5, %d] (taps per output pixel: resize such an image on the host)",
                kmax, RCN_KMAX);
-  const int tiles_x = zh_cdiv(n_px, RCN_TX), tiles_y = zh_cdiv(n_px, RCN_TY);
-  const size_t lds = ((size_t)(RCN_TX + RCN_TY) * kmax + 2 * (RCN_TX + RCN_TY)) * sizeof(int);
-  hipLaunchKernelGGL(resize_crop_normalize_kernel, dim3(tiles_x * tiles_y, B), dim3(RCN_TX * RCN_WAVES), lds, stream,
-                     packed, packed_bytes, desc, n_px, kmax, lut, out, tiles_x);
+  rcn_launch<RCN_BICUBIC>(packed, packed_bytes, desc, B, n_px, n_px, kmax, lut, out, 0, stream);
   ZH_CHECK_LAUNCH("zh_resize_crop_normalize_u8");
+  return ZH_OK;
+}
+
+// every image of the launch resized to out_w x out_h, no crop: a descriptor whose (nw, nh, left, top) is not (out_w, out_h, 0, 0) gives NaN
+extern "C" int zh_resize_normalize_u8(const unsigned char* packed, long packed_bytes, const int* desc, int B, int out_h, int out_w,
+                                      int filter, int kmax, const float* lut, float* out, hipStream_t stream) {
+  ZH_CHECK_ARG(packed && desc && lut && out, "zh_resize_normalize_u8: null pointer");
+  ZH_CHECK_ARG(B > 0 && B <= 65535 && out_h > 0 && out_h <= 16384 && out_w > 0 && out_w <= 16384 && packed_bytes > 0,
+               "zh_resize_normalize_u8: bad sizes (B=%d out_h=%d out_w=%d packed_bytes=%ld)", B, out_h, out_w, packed_bytes);
+  ZH_CHECK_ARG(((uintptr_t)packed & 15) == 0, "zh_resize_normalize_u8: packed must be 16-byte aligned");
+  ZH_CHECK_ARG(filter == RCN_BILINEAR || filter == RCN_BICUBIC, "zh_resize_normalize_u8: filter %d is neither ZH_FILTER_BILINEAR nor ZH_FILTER_BICUBIC", filter);
+  const int kmin = filter == RCN_BILINEAR ? 3 : 5;
+  ZH_CHECK_ARG(kmax >= kmin && kmax <= RCN_KMAX, "zh_resize_normalize_u8: kmax %d outside [%d, %d] (taps per output pixel: resize such an image on the host)",
+               kmax, kmin, RCN_KMAX);
+  if (filter == RCN_BILINEAR) rcn_launch<RCN_BILINEAR>(packed, packed_bytes, desc, B, out_h, out_w, kmax, lut, out, 1, stream);
+  else rcn_launch<RCN_BICUBIC>(packed, packed_bytes, desc, B, out_h, out_w, kmax, lut, out, 1, stream);
+  ZH_CHECK_LAUNCH("zh_resize_normalize_u8");
   return ZH_OK;
 }

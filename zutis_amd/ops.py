@@ -530,6 +530,30 @@ def resize_crop_normalize(packed, desc, n_px: int, lut, out=None, kmax: Optional
     return out
 
 
+FILTERS = {"bilinear": 2, "bicubic": 3}      # include/zutis_hip.h ZH_FILTER_BILINEAR / ZH_FILTER_BICUBIC (= PIL.Image's values)
+
+
+def resize_normalize(packed, desc, out_h: int, out_w: int, lut, filter: str = "bilinear", out=None, kmax: Optional[int] = None):
+    """datasets/index_dataset.py:405-411 (TF.resize BILINEAR, to_tensor, normalize) for a ragged batch whose images all resize to
+    out_h x out_w, in one launch and with no crop, bit-identical to Pillow + the fp32 normalisation: packed / desc / lut / kmax as for
+    resize_crop_normalize, every desc row (offset / 16, w, h, out_w, out_h, 0, 0, 0) -> f32 [B, 3, out_h, out_w].  `filter`:
+    "bilinear" or "bicubic" (zutis_amd.preprocess.ksize(..., filter) taps per output pixel)."""
+    _chk(packed, torch.uint8, "resize_normalize packed"); _chk(desc, torch.int32, "resize_normalize desc"); _chk(lut, f32, "resize_normalize lut")
+    if packed.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 8 or desc.shape[0] == 0 or tuple(lut.shape) != (3, 256):
+        raise _lib.ZutisHipError(f"resize_normalize: packed [bytes], desc [B, 8], lut [3, 256] expected, got {tuple(packed.shape)}, {tuple(desc.shape)}, {tuple(lut.shape)}")
+    if filter not in FILTERS:
+        raise _lib.ZutisHipError(f"resize_normalize: filter {filter!r} is not one of {sorted(FILTERS)}")
+    B = desc.shape[0]
+    if out is None:
+        out = torch.empty((B, 3, out_h, out_w), dtype=f32, device=packed.device)
+    _chk(out, f32, "resize_normalize out")
+    if tuple(out.shape) != (B, 3, out_h, out_w):
+        raise _lib.ZutisHipError(f"resize_normalize: out {tuple(out.shape)}, expected {(B, 3, out_h, out_w)}")
+    _call("zh_resize_normalize_u8", _p(packed), packed.numel(), _p(desc), B, out_h, out_w, FILTERS[filter], RCN_KMAX if kmax is None else int(kmax),
+          _p(lut), _p(out), _stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------- bilateral solver (float64)
 def denormalize_u8(x, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """utils/utils.py:261-273 on device: x f32 [3,H,W] -> rgb u8 [H,W,3]."""
@@ -593,11 +617,15 @@ def select_upsample_mask(obj, masks, out_u8, index, B, Q, h, w, H, W, scale_h, s
           float(threshold), _stream())
 
 
-def resize_nearest_u8(x_u8, H, W):
-    """F.interpolate(x[None,None], size=(H,W), mode="nearest")[0,0] for a u8 [h,w] mask on the GPU."""
+def resize_nearest_u8(x_u8, H, W, out=None):
+    """F.interpolate(x[None,None], size=(H,W), mode="nearest")[0,0] for a u8 [h,w] mask on the GPU (into `out` u8 [H,W] when given)."""
     _chk(x_u8, torch.uint8, "resize_nearest x")
     h, w = x_u8.shape
-    out = torch.empty((H, W), dtype=torch.uint8, device=x_u8.device)
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.uint8, device=x_u8.device)
+    _chk(out, torch.uint8, "resize_nearest out")
+    if tuple(out.shape) != (H, W):
+        raise _lib.ZutisHipError(f"resize_nearest: out {tuple(out.shape)}, expected {(H, W)}")
     _call("zh_resize_nearest_u8", _p(x_u8), _p(out), h, w, H, W, lin_scale(h, H), lin_scale(w, W), _stream())
     return out
 

@@ -1,13 +1,16 @@
-"""Host side of the device pre-processing of embedding extraction (csrc/preprocess.hip, ops.resize_crop_normalize).
+"""Host side of the device pre-processing of embedding extraction (csrc/preprocess.hip, ops.resize_crop_normalize) and of pseudo-label
+generation from files (ops.resize_normalize).
 
 The reference feeds CLIP through SimpleDataset's transform (utils/extract_image_embeddings.py:97-103: Resize BICUBIC, CenterCrop,
 ToTensor, Normalize) under a 16-worker DataLoader (:64-65).  Here the workers are THREADS that only open and decode (Pillow
 releases the GIL while it decodes); the resize, crop and normalisation run in one kernel per batch on the decoded bytes, which
 is also what crosses PCIe (3 bytes per source pixel instead of 12 per output pixel).
 
-  pil_resize_reference  NumPy restatement of Pillow's 8-bit bicubic resampler — the CPU oracle of the tests, not a product path
+  pil_resize_reference  NumPy restatement of Pillow's 8-bit resampler (bicubic, bilinear) — the CPU oracle of the tests, not a product path
   normalise_table       the 3 x 256 fp32 table the kernel looks normalised values up in
   BatchLoader           paths -> batches of (packed bytes + descriptor rows) in reused staging buffers, decoded one batch ahead
+  ShapeBucketLoader     the same staging for MaskDataset's transform (datasets/index_dataset.py:405-411): batches of ONE resized shape,
+                        gathered from a bounded window of paths ahead, so that the batched SelfMask + solver run batched
 
 Threads, not processes: no child ever holds the device open, nothing is pickled, a worker's exception is raised by the caller.
 """
@@ -39,18 +42,28 @@ def _bicubic(x: float) -> float:
     return 0.0
 
 
-def ksize(in_size: int, out_size: int) -> int:
-    """Taps per output pixel of Pillow's bicubic resampler for in_size -> out_size (its coefficient row length)."""
-    return int(math.ceil(2.0 * max(in_size / out_size, 1.0))) * 2 + 1
+def _bilinear(x: float) -> float:
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
 
 
-def pil_coefficients(in_size: int, out_size: int):
-    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for the bicubic filter: (K int64 [out, ksize], bounds int64 [out, 2] =
+# Pillow's filters (src/libImaging/Resample.c: BICUBIC, BILINEAR): name -> (function, support, PIL.Image constant)
+FILTERS = {"bicubic": (_bicubic, 2.0, Image.BICUBIC), "bilinear": (_bilinear, 1.0, Image.BILINEAR)}
+
+
+def ksize(in_size: int, out_size: int, filter: str = "bicubic") -> int:
+    """Taps per output pixel of Pillow's resampler for in_size -> out_size (its coefficient row length)."""
+    return int(math.ceil(FILTERS[filter][1] * max(in_size / out_size, 1.0))) * 2 + 1
+
+
+def pil_coefficients(in_size: int, out_size: int, filter: str = "bicubic"):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for `filter`: (K int64 [out, ksize], bounds int64 [out, 2] =
     (first source index, tap count)).  IEEE double, the weights summed in tap order, rounding half away from zero."""
+    fn, filter_support, _ = FILTERS[filter]
     scale = filterscale = in_size / out_size
     if filterscale < 1.0:
         filterscale = 1.0
-    support = 2.0 * filterscale
+    support = filter_support * filterscale
     ks = int(math.ceil(support)) * 2 + 1
     kk = np.zeros((out_size, ks), np.int64)
     bounds = np.zeros((out_size, 2), np.int64)
@@ -59,7 +72,7 @@ def pil_coefficients(in_size: int, out_size: int):
         center = (xx + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
         xmax = min(int(center + support + 0.5), in_size) - xmin
-        w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        w = [fn((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for v in w:
             ww += v
@@ -71,9 +84,9 @@ def pil_coefficients(in_size: int, out_size: int):
     return kk, bounds
 
 
-def _pass(a: np.ndarray, out_size: int) -> np.ndarray:
+def _pass(a: np.ndarray, out_size: int, filter: str) -> np.ndarray:
     """a u8 [L, in, C] -> u8 [L, out, C]: one resampling pass along axis 1."""
-    kk, bounds = pil_coefficients(a.shape[1], out_size)
+    kk, bounds = pil_coefficients(a.shape[1], out_size, filter)
     out = np.empty((a.shape[0], out_size, a.shape[2]), np.uint8)
     ai = a.astype(np.int64)
     for xx in range(out_size):
@@ -83,17 +96,17 @@ def _pass(a: np.ndarray, out_size: int) -> np.ndarray:
     return out
 
 
-def pil_resize_reference(a_u8: np.ndarray, nw: int, nh: int) -> np.ndarray:
-    """Image.fromarray(a_u8).resize((nw, nh), Image.BICUBIC) for a u8 [h, w, C] array, byte for byte: horizontal pass to a u8
+def pil_resize_reference(a_u8: np.ndarray, nw: int, nh: int, filter: str = "bicubic") -> np.ndarray:
+    """Image.fromarray(a_u8).resize((nw, nh), Image.BICUBIC | Image.BILINEAR) for a u8 [h, w, C] array, byte for byte: horizontal pass to a u8
     intermediate, then vertical; a pass whose size does not change is skipped, as Pillow skips it."""
     a = np.ascontiguousarray(a_u8)
     if a.dtype != np.uint8 or a.ndim != 3:
         raise ValueError("pil_resize_reference: u8 [h, w, C] expected")
     h, w, _ = a.shape
     if nw != w:
-        a = _pass(a, nw)
+        a = _pass(a, nw, filter)
     if nh != h:
-        a = _pass(a.transpose(1, 0, 2), nh).transpose(1, 0, 2)
+        a = _pass(a.transpose(1, 0, 2), nh, filter).transpose(1, 0, 2)
     return np.ascontiguousarray(a)
 
 
@@ -106,8 +119,8 @@ def normalise_table(mean, std) -> np.ndarray:
     return np.ascontiguousarray(((a - mean) / std).T)
 
 
-def _taps_ok(w: int, h: int, nw: int, nh: int) -> bool:
-    return ksize(w, nw) <= KMAX and ksize(h, nh) <= KMAX and 3 * w * h < 2 ** 31
+def _taps_ok(w: int, h: int, nw: int, nh: int, filter: str = "bicubic") -> bool:
+    return ksize(w, nw, filter) <= KMAX and ksize(h, nh, filter) <= KMAX and 3 * w * h < 2 ** 31
 
 
 def device_supported(w: int, h: int, n_px: int) -> bool:
@@ -144,6 +157,7 @@ class BatchLoader:
         self.paths, self.n_px, self.batch_size, self.box = list(paths), int(n_px), int(batch_size), box
         self.n_threads = max(1, min(int(n_workers), MAX_WORKERS))
         self.pin = torch.cuda.is_available() if pin is None else bool(pin)
+        self.filter = "bicubic"
         self._buffers: List[torch.Tensor] = [torch.empty(0, dtype=torch.uint8), torch.empty(0, dtype=torch.uint8)]
 
     def __len__(self):
@@ -160,43 +174,50 @@ class BatchLoader:
         with Image.open(path) as im:            # header only
             return im.size
 
-    def _decode(self, path: str, dst: np.ndarray, size, host_box):
+    def _decode(self, path: str, dst: np.ndarray, size, host_box, out_wh):
         im = Image.open(path).convert("RGB")
         if im.size != size:
             raise ValueError(f"{path}: decoded size {im.size} differs from its header's {size}")
         if host_box is not None:
             (nw, nh), (left, top) = host_box
-            im = im.resize((nw, nh), Image.BICUBIC).crop((left, top, left + self.n_px, top + self.n_px))
+            im = im.resize((nw, nh), FILTERS[self.filter][2]).crop((left, top, left + out_wh[0], top + out_wh[1]))
         np.copyto(dst, np.asarray(im))
+
+    def _pack(self, pool: ThreadPoolExecutor, slot: int, chunk, sizes, boxes, out_wh):
+        """Lay `chunk` (files of `sizes` = (w, h), resized and cropped as `boxes` = ((nw, nh), (left, top)) say, to out_wh = (w, h) of the
+        kernel's output) out in staging buffer `slot` and start its decodes: (staging, packed, desc, kmax, images resized on the host,
+        futures)."""
+        B, (ow, oh) = len(chunk), out_wh
+        rows = np.zeros((B, DESC_INTS), np.int32)
+        host_boxes, shapes, kmax, off = [], [], ksize(1, 1, self.filter), 0
+        for i, ((w, h), bx) in enumerate(zip(sizes, boxes)):
+            (nw, nh), (left, top) = bx
+            if _taps_ok(w, h, nw, nh, self.filter):
+                host_boxes.append(None)
+            else:
+                host_boxes.append(bx)
+                w, h, nw, nh = ow, oh, ow, oh
+                left = top = 0
+            kmax = max(kmax, ksize(w, nw, self.filter), ksize(h, nh, self.filter))
+            rows[i] = (off // ALIGN, w, h, nw, nh, left, top, 0)
+            shapes.append((off, h, w))
+            off += -(-3 * w * h // ALIGN) * ALIGN
+        head = B * DESC_INTS * 4
+        staging = self._staging(slot, head + off)
+        packed, desc = split_staging(staging, B)
+        desc.numpy()[...] = rows
+        pix = packed.numpy()
+        futures = [pool.submit(self._decode, p, pix[o:o + 3 * w * h].reshape(h, w, 3), size, hb, out_wh)
+                   for p, (o, h, w), size, hb in zip(chunk, shapes, sizes, host_boxes)]
+        return staging, packed, desc, kmax, sum(hb is not None for hb in host_boxes), futures
 
     def _submit(self, pool: ThreadPoolExecutor, k: int):
         """Fix batch k's layout from the headers and start its decodes: (Batch, futures)."""
         chunk = self.paths[k * self.batch_size:(k + 1) * self.batch_size]
         sizes = list(pool.map(self._size, chunk))
-        B, n = len(chunk), self.n_px
-        rows = np.zeros((B, DESC_INTS), np.int32)
-        host_boxes, shapes, kmax, off = [], [], 5, 0
-        for i, (w, h) in enumerate(sizes):
-            bx = self.box(w, h, n)
-            (nw, nh), (left, top) = bx
-            if _taps_ok(w, h, nw, nh):
-                host_boxes.append(None)
-            else:
-                host_boxes.append(bx)
-                w = h = nw = nh = n
-                left = top = 0
-            kmax = max(kmax, ksize(w, nw), ksize(h, nh))
-            rows[i] = (off // ALIGN, w, h, nw, nh, left, top, 0)
-            shapes.append((off, h, w))
-            off += -(-3 * w * h // ALIGN) * ALIGN
-        head = B * DESC_INTS * 4
-        staging = self._staging(k % 2, head + off)
-        packed, desc = split_staging(staging, B)
-        desc.numpy()[...] = rows
-        pix = packed.numpy()
-        futures = [pool.submit(self._decode, p, pix[o:o + 3 * w * h].reshape(h, w, 3), size, hb)
-                   for p, (o, h, w), size, hb in zip(chunk, shapes, sizes, host_boxes)]
-        return Batch(chunk, staging, packed, desc, kmax, sum(hb is not None for hb in host_boxes)), futures
+        n = self.n_px
+        staging, packed, desc, kmax, n_host, futures = self._pack(pool, k % 2, chunk, sizes, [self.box(w, h, n) for w, h in sizes], (n, n))
+        return Batch(chunk, staging, packed, desc, kmax, n_host), futures
 
     def __iter__(self):
         n_batches = len(self)
@@ -212,6 +233,111 @@ class BatchLoader:
                         f.result()              # raises what the worker raised
                     if k + 1 < n_batches:
                         pending = self._submit(pool, k + 1)
+                    yield batch
+            finally:
+                if pending is not None:
+                    for f in pending[1]:
+                        f.cancel()
+
+
+def mask_dataset_size(w: int, h: int, image_size):
+    """(nw, nh) of MaskDataset's `TF.resize(image, size=image_size, interpolation=BILINEAR)` (datasets/index_dataset.py:408-409) for a
+    w x h file: the shorter side becomes image_size, the other int(image_size * long / short); an image whose shorter side already is
+    image_size, and image_size None, stay as they are."""
+    if image_size is None:
+        return w, h
+    s = int(image_size)
+    if (w <= h and w == s) or (h <= w and h == s):
+        return w, h
+    return (s, int(s * h / w)) if w < h else (int(s * w / h), s)
+
+
+def _buckets(shapes, batch_size: int, window: int):
+    open_buckets = {}                                # shape -> indices, in order of each bucket's oldest image (dicts keep insertion order)
+    for i, key in enumerate(shapes):
+        for k in [k for k, idx in open_buckets.items() if idx[0] <= i - window]:
+            yield open_buckets.pop(k)
+        idx = open_buckets.setdefault(key, [])
+        idx.append(i)
+        if len(idx) == batch_size:
+            yield open_buckets.pop(key)
+    yield from open_buckets.values()
+
+
+def bucket_batches(shapes: Sequence, batch_size: int, window: int) -> List[List[int]]:
+    """The grouping of ShapeBucketLoader as a pure function of the images' shape keys in path order: image i joins the open bucket of
+    its shape; a bucket is emitted when it holds batch_size images (full buckets first), when its oldest image lies `window` paths
+    behind the one being read (the window closes on it), or at the end of the list, oldest bucket first.  Lists of indices into
+    `shapes`; every index exactly once; one shape and at most batch_size images per list."""
+    if batch_size < 1 or window < 1:
+        raise ValueError("bucket_batches: batch_size and window must be positive")
+    return list(_buckets(shapes, batch_size, window))
+
+
+ShapeBatch = collections.namedtuple("ShapeBatch", "paths indices sizes_hw out_hw staging packed desc kmax n_host")
+ShapeBatch.__doc__ = """One decoded batch of ONE resized shape.  paths / indices: its files and their positions in the loader's path list;
+sizes_hw: the files' own (H, W); out_hw: the (out_h, out_w) every image of the batch resizes to; the rest as in Batch."""
+
+
+class ShapeBucketLoader(BatchLoader):
+    """BatchLoader's threads and staging for MaskDataset's transform (datasets/index_dataset.py:388-411): every image is resized whole —
+    shorter side to `image_size` (mask_dataset_size), `filter` bilinear — so a batch for ops.resize_normalize must be of one resized
+    shape.  The loader reads the headers of at most `window` paths at a time, groups them with bucket_batches (a deterministic function
+    of the path list, batch_size and window: batches come OUT OF INPUT ORDER and carry their indices) and decodes one batch ahead.
+    An image outside the kernel's envelope (more than KMAX taps per output pixel — a source side over 75 times the target with
+    bilinear's 3-tap support — or 3 w h >= 2^31) is resized by Pillow in its worker and packed as an identity image.  A missing or
+    unreadable file raises in the step that reads its header or needs its batch, at the latest."""
+
+    def __init__(self, paths: Sequence[str], image_size, batch_size: int, n_workers: int, window: int = 512, filter: str = "bilinear", pin=None):
+        if image_size is not None and image_size < 1:
+            raise ValueError("ShapeBucketLoader: image_size must be positive or None")
+        if window < 1 or filter not in FILTERS:
+            raise ValueError(f"ShapeBucketLoader: window must be positive and filter one of {sorted(FILTERS)}")
+        super().__init__(paths, 1, batch_size, n_workers, None, pin)
+        self.image_size, self.window, self.filter = image_size, int(window), filter
+
+    def __len__(self):
+        raise TypeError("ShapeBucketLoader: the number of batches depends on the files' shapes")
+
+    def _groups(self, pool: ThreadPoolExecutor):
+        """bucket_batches over the path list, its shape keys read from the headers `window` paths at a time: yields (indices, the files'
+        (w, h), the resized (nw, nh))."""
+        sizes = {}
+
+        def keys():
+            for start in range(0, len(self.paths), self.window):
+                block = self.paths[start:start + self.window]
+                for i, wh in enumerate(pool.map(self._size, block), start):
+                    sizes[i] = wh
+                for i in range(start, start + len(block)):
+                    yield mask_dataset_size(*sizes[i], self.image_size)
+
+        for idx in _buckets(keys(), self.batch_size, self.window):
+            wh = [sizes.pop(i) for i in idx]
+            yield idx, wh, mask_dataset_size(*wh[0], self.image_size)
+
+    def _start(self, pool: ThreadPoolExecutor, slot: int, group):
+        idx, sizes, (nw, nh) = group
+        chunk = [self.paths[i] for i in idx]
+        staging, packed, desc, kmax, n_host, futures = self._pack(pool, slot, chunk, sizes, [((nw, nh), (0, 0))] * len(idx), (nw, nh))
+        return ShapeBatch(chunk, idx, [(h, w) for w, h in sizes], (nh, nw), staging, packed, desc, kmax, n_host), futures
+
+    def __iter__(self):
+        with ThreadPoolExecutor(max_workers=self.n_threads, thread_name_prefix="zutis-decode") as pool:
+            groups = self._groups(pool)
+            first = next(groups, None)
+            pending = None if first is None else self._start(pool, 0, first)
+            k = 0
+            try:
+                while pending is not None:
+                    batch, futures = pending
+                    pending = None
+                    for f in futures:
+                        f.result()              # raises what the worker raised
+                    k += 1
+                    nxt = next(groups, None)
+                    if nxt is not None:
+                        pending = self._start(pool, k % 2, nxt)
                     yield batch
             finally:
                 if pending is not None:

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import json
 import os
+from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -40,21 +41,28 @@ def pseudo_mask(engine: SelfMaskEngine, image: torch.Tensor, original_size: Opti
     return _device_mask(engine, image, original_size, bilateral_solver).cpu().numpy()
 
 
+def _device_masks_batch(engine: SelfMaskEngine, images: torch.Tensor, bilateral_solver: bool, **norm) -> torch.Tensor:
+    """The device steps of pseudo_masks_batch up to the threshold: images f32 [B,3,H,W] -> u8 {0,1} [B,H,W], on the current stream.
+    norm: mean= / std= the images were normalised with, when they are not ops.denormalize_u8's defaults."""
+    B = images.shape[0]
+    out = engine.forward(images.contiguous(), inference=True)
+    dts = out["dts"]                                                       # u8 [B,H,W]
+    if bilateral_solver:
+        rgb = torch.stack([ops.denormalize_u8(images[b].contiguous(), **norm) for b in range(B)])
+        soft, _ = ops.bilateral_solve(rgb, dts.contiguous())
+        dts = ops.threshold_f64_u8(soft, 0.5)
+    return dts
+
+
 @torch.no_grad()
 def pseudo_masks_batch(engine: SelfMaskEngine, images: torch.Tensor, original_sizes: Optional[Sequence[Tuple[int, int]]] = None,
                        bilateral_solver: bool = True) -> List[torch.Tensor]:
     """B images of ONE size in one pass (the reference loops batch 1, index_dataset.py:189-204): images f32 [B,3,H,W] on the
     GPU -> list of B uint8 {0,1} masks on the GPU.  SelfMask runs batched; the bilateral solver's ~110 launches are shared by
     the whole batch (zh_bilateral_solve_batch, blockIdx.y = image) — for one image it is launch/latency-bound."""
-    B = images.shape[0]
-    out = engine.forward(images.contiguous(), inference=True)
-    dts = out["dts"]                                                       # u8 [B,H,W]
-    if bilateral_solver:
-        rgb = torch.stack([ops.denormalize_u8(images[b].contiguous()) for b in range(B)])
-        soft, _ = ops.bilateral_solve(rgb, dts.contiguous())
-        dts = ops.threshold_f64_u8(soft, 0.5)
+    dts = _device_masks_batch(engine, images, bilateral_solver)
     masks = []
-    for b in range(B):
+    for b in range(images.shape[0]):
         dt = dts[b]
         if original_sizes is not None and tuple(original_sizes[b]) != tuple(dt.shape):
             dt = ops.resize_nearest_u8(dt.contiguous(), int(original_sizes[b][0]), int(original_sizes[b][1]))
@@ -70,7 +78,7 @@ def save_rle_json(mask: np.ndarray, path: str) -> Dict:
     with open(path, "w") as f:
         json.dump({"size": r["size"], "counts": r["counts"].decode("ascii")}, f)
     back = json.load(open(path))
-    assert (rle.decode(back) == mask).sum() == mask.size
+    assert (rle.decode_np(back) == mask).sum() == mask.size
     return r
 
 
@@ -134,6 +142,100 @@ def generate_pseudo_masks(engine: SelfMaskEngine, images: Sequence[torch.Tensor]
     return list(out_paths)
 
 
+# ------------------------------------------------------------------------------------- files in, JSON out
+MAX_THREADS = 16        # decoders + writers
+
+
+class _Slot:
+    """One of the two sets of buffers a batch's masks travel through: a device buffer the masks are resized into, its pinned host twin,
+    the event behind the copy between them, and the writer tasks that still read the host side."""
+
+    def __init__(self, device):
+        self.device, self.dev, self.host = device, None, None
+        self.event = torch.cuda.Event()
+        self.tasks = []
+
+    def reserve(self, nbytes: int):
+        if self.dev is None or self.dev.numel() < nbytes:
+            self.dev = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, device=self.device)
+            self.host = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=True)
+
+    def drain(self):
+        """Wait for the writers of the batch that used this slot; raises what a writer raised."""
+        tasks, self.tasks = self.tasks, []
+        for t in tasks:
+            t.result()
+
+
+def _write_masks(event, host: np.ndarray, items):
+    """A writer task: once the batch's copy has landed, index_dataset.py:219-224 for some of its masks.  items: (offset, (H, W), path)."""
+    event.synchronize()
+    for off, (h, w), path in items:
+        save_rle_json(host[off:off + h * w].reshape(h, w), path)
+
+
+@torch.no_grad()
+def generate_pseudo_masks_from_files(engine: SelfMaskEngine, p_images: Sequence[str], out_paths: Sequence[str], *, image_size: Optional[int] = 512,
+                                     mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), bilateral_solver: bool = True,
+                                     batch_size: int = 8, n_workers: int = 16, window: int = 512) -> List[str]:
+    """IndexDataset.generate_pseudo_masks (datasets/index_dataset.py:177-226) from a list of image files to the RLE JSON files
+    `out_paths`, MaskDataset's transform (:405-411) included.  Threads decode into pinned staging one batch ahead
+    (preprocess.ShapeBucketLoader: batches of ONE resized shape out of a window of `window` paths, so SelfMask and the solver run
+    batched on a corpus of mixed shapes); per batch one host-to-device copy of the decoded bytes, ops.resize_normalize (Pillow's
+    BILINEAR + the normalisation, bit for bit), the device steps of pseudo_masks_batch, every mask resized to its file's own size into
+    one device buffer, one copy to pinned memory behind an event; RLE encoding, the JSON write and its read-back check run on writer
+    threads while the next batch is on the GPU.  n_workers (at most 16) is split between decoders and writers (a quarter, at least one).
+    Each file is what save_rle_json writes; returns out_paths (input order).  A missing or unreadable image and a writer's exception
+    are raised here.  The grouping is preprocess.bucket_batches of the files' resized shapes."""
+    from . import preprocess
+    p_images, out_paths = list(p_images), list(out_paths)
+    if len(p_images) != len(out_paths):
+        raise ValueError("generate_pseudo_masks_from_files: one output path per image")
+    if not p_images:
+        return out_paths
+    dev = engine._device()
+    n_threads = max(2, min(int(n_workers), MAX_THREADS))
+    n_writers = max(1, n_threads // 4)
+    lut = torch.from_numpy(preprocess.normalise_table(mean, std)).to(dev)
+    loader = preprocess.ShapeBucketLoader(p_images, image_size, batch_size, n_threads - n_writers, window=window, filter="bilinear")
+    slots = [_Slot(dev), _Slot(dev)]
+    copied = torch.cuda.Event()
+    with ThreadPoolExecutor(max_workers=n_writers, thread_name_prefix="zutis-rle") as writers, torch.cuda.device(dev):
+        try:
+            for k, batch in enumerate(loader):
+                B, (oh, ow) = len(batch.paths), batch.out_hw
+                staged = batch.staging.to(dev, non_blocking=True)                      # descriptors + decoded bytes: one H2D
+                copied.record()
+                packed, desc = preprocess.split_staging(staged, B)
+                x = ops.resize_normalize(packed, desc, oh, ow, lut, filter="bilinear", kmax=batch.kmax)
+                dts = _device_masks_batch(engine, x, bilateral_solver, mean=mean, std=std)
+                slot = slots[k % 2]
+                slot.drain()                                                            # the writers of batch k - 2 are done with its host buffer
+                offs = np.concatenate(([0], np.cumsum([h * w for h, w in batch.sizes_hw]))).tolist()
+                slot.reserve(offs[-1])
+                for b, (h, w) in enumerate(batch.sizes_hw):                             # index_dataset.py:214-215
+                    dst = slot.dev[offs[b]:offs[b + 1]].view(h, w)
+                    if (h, w) == (oh, ow):
+                        dst.copy_(dts[b])
+                    else:
+                        ops.resize_nearest_u8(dts[b], h, w, out=dst)
+                slot.host[:offs[-1]].copy_(slot.dev[:offs[-1]], non_blocking=True)     # one D2H
+                slot.event.record()
+                host = slot.host.numpy()
+                items = [(offs[b], batch.sizes_hw[b], out_paths[i]) for b, i in enumerate(batch.indices)]
+                per = -(-B // n_writers)
+                slot.tasks = [writers.submit(_write_masks, slot.event, host, items[j:j + per]) for j in range(0, B, per)]
+                copied.synchronize()                                                    # the loader may now decode into this staging buffer again
+            for slot in slots:
+                slot.drain()
+        finally:
+            torch.cuda.synchronize(dev)                                                 # nothing in flight on the pinned buffers when they go
+            for slot in slots:
+                for t in slot.tasks:
+                    t.cancel()
+    return out_paths
+
+
 # ------------------------------------------------------------------------------------- the dataset method's own signature
 def _image_size_hw(p_image: str) -> Tuple[int, int]:
     """(H, W) of the image file — `W, H = Image.open(p_image).size` (index_dataset.py:214)."""
@@ -145,7 +247,7 @@ def _image_size_hw(p_image: str) -> Tuple[int, int]:
 
 @torch.no_grad()
 def dataset_generate_pseudo_masks(self, p_images: List[str], dir_dataset: str, n_workers: int = 4, bilateral_solver: bool = True, *,
-                                  batch_size: int = 8, network=None, mask_dataset_cls=None, image_size_fn=None) -> None:
+                                  batch_size: int = 8, network=None, mask_dataset_cls=None, image_size_fn=None, loader: str = "dataset") -> None:
     """`IndexDataset.generate_pseudo_masks(self, p_images, dir_dataset, n_workers, bilateral_solver)` (datasets/index_dataset.py:177-226;
     the same method exists in datasets/imagenet.py and datasets/pass.py) over the batched device path.  Bind it in place of the
     reference's method — `IndexDataset.generate_pseudo_masks = zutis_amd.pseudo_masks.dataset_generate_pseudo_masks` — and the
@@ -156,7 +258,9 @@ def dataset_generate_pseudo_masks(self, p_images: List[str], dir_dataset: str, n
     The loader is the dataset module's own `MaskDataset` (same resize / normalisation); the network is the `selfmask` of
     `utils.utils.get_network` (the overlay's drop-in SelfMask when it is installed) unless `network=` is given.  The keyword-only
     arguments are not in the reference's signature: `batch_size` (images of one shape solved together; 1 = the reference's loop),
-    and the injection points the tests use."""
+    the injection points the tests use, and `loader`: "dataset" (the default: the DataLoader over MaskDataset, groups of consecutive
+    images of one shape) or "threads" (generate_pseudo_masks_from_files with image_size / mean / std of a MaskDataset instance and
+    n_workers decoding and writing threads: shape-bucketed batches, the resize on the device)."""
     import sys
     from torch.utils.data import DataLoader
     if network is None:
@@ -168,8 +272,17 @@ def dataset_generate_pseudo_masks(self, p_images: List[str], dir_dataset: str, n
     if not isinstance(engine, SelfMaskEngine):
         raise TypeError("dataset_generate_pseudo_masks needs the MI355X drop-in SelfMask (networks/selfmask/selfmask.py of the overlay) "
                         "or a SelfMaskEngine: there is no torch / CPU fallback")
+    if loader not in ("dataset", "threads"):
+        raise ValueError(f"dataset_generate_pseudo_masks: loader {loader!r} is neither 'dataset' nor 'threads'")
     if mask_dataset_cls is None:
         mask_dataset_cls = getattr(sys.modules[type(self).__module__], "MaskDataset")
+    if loader == "threads":
+        ds = mask_dataset_cls(p_images=p_images)
+        generate_pseudo_masks_from_files(engine, p_images, [self._convert_p_image_to_p_pseudo_mask(p_image=p) for p in p_images],
+                                         image_size=ds.image_size, mean=ds.mean, std=ds.std, bilateral_solver=bilateral_solver,
+                                         batch_size=batch_size, n_workers=n_workers)
+        print(f"Pseudo-masks are saved in {dir_dataset}.")          # :226
+        return
     size_of = image_size_fn or _image_size_hw
     loader = DataLoader(dataset=mask_dataset_cls(p_images=p_images), batch_size=1, num_workers=n_workers, pin_memory=True)   # :187-188
 

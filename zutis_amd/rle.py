@@ -100,6 +100,29 @@ def decode(rle: Dict) -> np.ndarray:
     return flat.reshape((h, w), order="F")
 
 
+def decode_np(rle: Dict) -> np.ndarray:
+    """decode() in NumPy, for the read-back check of the pseudo-label writers (pseudo_masks.save_rle_json), where the per-character Python
+    loop of decode() was the longest step of the tail: the characters of a value are its 5-bit groups (bit 0x20 = more follow, bit 0x10
+    of the last = sign), values from the fourth on are deltas against the value two places back, i.e. running sums over the odd and over
+    the even places.  decode() stays as the readable restatement it is checked against (tests/test_pseudo_files_cpu.py)."""
+    h, w = rle["size"]
+    s = rle["counts"]
+    c = np.frombuffer(s.encode("ascii") if isinstance(s, str) else bytes(s), np.uint8).astype(np.int64) - 48
+    flat = np.zeros(h * w, np.uint8)
+    if c.size:
+        ends = np.flatnonzero((c & 0x20) == 0)
+        starts = np.concatenate(([0], ends[:-1] + 1))
+        nchar = ends - starts + 1
+        part = (c & 0x1F) << (5 * (np.arange(c.size) - np.repeat(starts, nchar)))
+        cnts = np.add.reduceat(part, starts)
+        cnts = np.where((c[ends] & 0x10) != 0, cnts | np.left_shift(np.int64(-1), 5 * nchar), cnts)
+        cnts[1::2] = np.cumsum(cnts[1::2])
+        cnts[2::2] = np.cumsum(cnts[2::2])
+        runs = np.repeat((np.arange(cnts.size) & 1).astype(np.uint8), cnts)[:h * w]
+        flat[:runs.size] = runs
+    return flat.reshape((h, w), order="F")
+
+
 def mask_to_box(mask: np.ndarray) -> List[float]:
     """torchvision.ops.masks_to_boxes for one mask: [xmin, ymin, xmax, ymax] of the non-zero pixels (float32 values)."""
     rows = np.flatnonzero(mask.any(axis=1))
