@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 229 /* 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 230 /* 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -469,6 +469,38 @@ long zh_rle_counts_to_string_host(const long long* counts, long n, char* out, lo
  * -1 when cap is too small.  Replaces pycocotools.mask.encode per kept mask (networks/zutis.py:290,448). */
 long zh_rle_from_transitions_host(const int* positions, long stride, int packed, const int* nruns, long n, long HW, char* out, long cap,
                                   long long* offsets);
+
+/* One training sample of IndexDataset.__getitem__ on the device — datasets/index_dataset.py:301-385: random_scale / random_crop /
+ * random_hflip (datasets/augmentations/geometric_transforms.py), ColorJitter + RandomGrayscale + GaussianBlur
+ * (datasets/base_dataset.py:62-78), to_tensor + normalize, copy_paste (datasets/augmentations/copy_paste.py) — for a batch of B
+ * samples made of N sub-images, every random draw taken from a recipe (zutis_amd/synth.py).  Bit-identical to Pillow / torch on the
+ * host except the blur.  Between the stages a sub-image is u8 [C, C, 4] = (R, G, B, mask byte in {0, 1, ignore_index}).
+ * packed / packed_bytes: as for zh_resize_crop_normalize_u8, the u8 [h, w] masks packed next to the images.
+ * desc int32 [N, 32] per sub-image: image offset / 16, w, h, scaled nw, nh, mask offset / 16, pad left, pad top, crop left, crop top,
+ *   flip, label id, flags (1 jitter, 2 grey, 4 blur, 8 padded), op order (four 2-bit codes, first op lowest: 0 brightness, 1 contrast,
+ *   2 saturation, 3 hue), hue shift (the u8 added to H), brightness / contrast / saturation factors (fp32 bits), the ATen nearest
+ *   scales float(h) / float(nh), float(w) / float(nw) (fp32 bits), the paste draws u_top, u_left (float64 bits, two slots each), 0.
+ * work int32 [N, 12], 8-byte aligned, initialised by the caller to (0 x 8, C, -1, C, -1): four u64 sums (the scaled image's R, G, B:
+ *   its mean is the pad fill; the grey sum behind the contrast mean) and the object's box ymin, ymax, xmin, xmax.
+ * zh_synth_geometry_u8: Pillow BILINEAR at (nw, nh) (the resampler of zh_resize_normalize_u8, kmax as there, >= 3), ATen nearest
+ *   for the mask, pad (image: the integer channel mean of the scaled image; mask: ignore_index), crop C x C, flip -> out_rgbm, box -> work.
+ *   fill_w x fill_h: the largest scaled extent among the PADDED sub-images (0: none is padded, the sums are not computed).  A descriptor
+ *   the launch cannot serve (bytes outside packed, more taps than kmax) gives an all-ignore crop and is not read through. */
+int zh_synth_geometry_u8(const unsigned char* packed, long packed_bytes, const int* desc, int N, int C, int ignore_index, int kmax,
+                         int fill_w, int fill_h, int* work, unsigned char* out_rgbm, zh_stream_t stream);
+/* ColorJitter's ops in desc's order (ImageEnhance blends; the hue shift through Pillow's RGB <-> HSV) and RandomGrayscale, in place;
+ * the contrast mean is reduced over the image as it stands when contrast is reached (work). */
+int zh_synth_photometric_u8(unsigned char* rgbm, const int* desc, int N, int C, int* work, zh_stream_t stream);
+/* Separable Gaussian, BORDER_REFLECT_101, of the sub-images whose flags say blur: rgbm -> out_rgbm (the others are not written).
+ * weights f32 [N, ksize], normalised; ksize odd, radius at most 48.  fp32 sums rounded to nearest: within one level of the exact value. */
+int zh_synth_blur_u8(const unsigned char* rgbm, const int* desc, const float* weights, int N, int C, int ksize, unsigned char* out_rgbm,
+                     zh_stream_t stream);
+/* copy_paste per output pixel + normalisation.  samples int32 [B, 4]: first sub-image, n (at most 64), first one-hot row, 0.  A sub-image
+ * is read from rgbm_blurred when its flags say blur, else from rgbm.  lut f32 [3, 256] as for zh_resize_crop_normalize_u8.
+ * -> image f32 [B, 3, C, C], semantic int64 [B, C, C], onehot u8 (bool) [sum n, C, C]. */
+int zh_synth_compose(const unsigned char* rgbm, const unsigned char* rgbm_blurred, const int* desc, const int* samples, const int* work,
+                     const float* lut, int N, int B, int C, int ignore_index, float* image, long long* semantic, unsigned char* onehot,
+                     zh_stream_t stream);
 
 /* HOST helper (no GPU): COCO RLE string of one u8 [H,W] mask = pycocotools.mask.encode(np.asfortranarray(m))["counts"]
  * (zutis.py:290,448; datasets/index_dataset.py:219).  Returns the length, -1 if cap is too small. */

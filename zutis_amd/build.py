@@ -13,16 +13,17 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libzutis_hip.so")
 # float64 bilateral solver: no FMA contraction (bin edges and bistochastisation are bit-compared with NumPy/SciPy);
 # preprocess.hip: Pillow's resampling coefficients are bit-compared with the host's double arithmetic
-EXTRA_FLAGS = {"bilateral.hip": ["-ffp-contract=off"], "preprocess.hip": ["-ffp-contract=off"]}
+EXTRA_FLAGS = {"bilateral.hip": ["-ffp-contract=off"], "preprocess.hip": ["-ffp-contract=off"],
+               "synth.hip": ["-ffp-contract=off"]}   # synth.hip: Pillow's blend and HSV arithmetic, one IEEE operation at a time
 # the MFMA kernels live at the register budget of their occupancy: a spill is a 2-3x slowdown, so it is a build error
-NO_SCRATCH = {"gemm.hip", "gemm_x3.hip", "attention.hip", "preprocess.hip"}
+NO_SCRATCH = {"gemm.hip", "gemm_x3.hip", "attention.hip", "preprocess.hip", "synth.hip"}
 MAX_SCRATCH = int(os.environ.get("ZH_BUILD_MAX_SCRATCH", "0"))    # bytes per lane tolerated: the MFMA loops must not spill (developer builds may raise it)
 # waves per SIMD the design of a kernel relies on (source -> mangled-name substring -> minimum), checked against the compiler's
 # remarks; a key that matches no kernel of its source is a build error (a renamed template would otherwise drop its guard)
 MIN_OCCUPANCY = {"attention.hip": {"attn_f16_kernelILi64ELi4ELi1ELi0EE": 3, "attn_f16_kernelILi64ELi4ELi0ELi0EE": 3,
                                    "attn_f16_kernelILi64ELi4ELi1ELi1EE": 2, "attn_f16_kernelILi96ELi4ELi1ELi0EE": 2,
                                    "attn_f16_kernelILi96ELi4ELi0ELi0EE": 2, "attn_f16_kernelILi96ELi4ELi1ELi1EE": 2}}
-SOURCES = ["capi.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "plan.hip"]
+SOURCES = ["capi.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "synth.hip", "plan.hip"]
 
 
 def _hipcc() -> str:
@@ -41,7 +42,7 @@ def needs_build() -> bool:
         return True
     t = os.path.getmtime(LIB)
     deps = sources() + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_kernel.h"), os.path.join(CSRC, "gemm_skinny.h"),
-                        os.path.join(os.path.dirname(HERE), "include", "zutis_hip.h")]
+                        os.path.join(CSRC, "rcn.h"), os.path.join(os.path.dirname(HERE), "include", "zutis_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -60,6 +61,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if os.path.basename(src).startswith("gemm"):
             deps.append(os.path.join(CSRC, "gemm_kernel.h"))
             deps.append(os.path.join(CSRC, "gemm_skinny.h"))
+        if os.path.basename(src) in ("preprocess.hip", "synth.hip"):
+            deps.append(os.path.join(CSRC, "rcn.h"))
         if os.path.basename(src) in ("plan.hip", "capi.hip"):       # the dispatcher generated from the header / ZH_ABI_VERSION
             deps.append(os.path.join(os.path.dirname(HERE), "include", "zutis_hip.h"))
         if not force and os.path.exists(obj) and all(os.path.getmtime(obj) > os.path.getmtime(d) for d in deps):

@@ -9,6 +9,7 @@
 // expression, looked up here — no floating-point pixel arithmetic on the device at all.
 //
 // MI355X design.  One launch per batch; one workgroup (4 waves) per (image, tile of 32 output rows x 64 output columns).
+// (steps 1 and 2 are rcn_tile_u8 of rcn.h, which csrc/synth.hip runs as well)
 //   1. 64 threads compute the tile's column coefficient sets, 32 its row sets, into LDS as int32 ([tap][column] / [row][tap]).
 //   2. A lane owns one output column (all three channels), a wave 8 output rows.  The wave streams over the source rows its
 //      8 rows tap: per source row the lane forms the horizontal pass's u8 pixel from global memory (the source of a typical
@@ -27,62 +28,7 @@
 // is 64 consecutive floats of one plane row, and the 32 x 64 tile gives 11 x 16 workgroups per image (1408 at eight images, 5.5 per
 // CU) with 3 % of the lanes idle (the last tile column).
 #include "common.h"
-
-#define RCN_TX 64       // output columns per workgroup (= lanes)
-#define RCN_WAVES 4
-#define RCN_RY 8        // output rows per wave
-#define RCN_TY (RCN_WAVES * RCN_RY)
-#define RCN_KMAX 152    // include/zutis_hip.h ZH_RCN_KMAX: 96 * 152 * 4 + 768 bytes of LDS < 64 KiB
-#define RCN_PRECISION_BITS 22
-
-#define RCN_BILINEAR 2  // include/zutis_hip.h ZH_FILTER_BILINEAR / ZH_FILTER_BICUBIC
-#define RCN_BICUBIC 3
-
-// Pillow's filter functions (Resample.c: bilinear_filter, bicubic_filter) and their supports
-template <int FILTER>
-__device__ __forceinline__ double rcn_filter(double x) {
-  if (x < 0.0) x = -x;
-  if (FILTER == RCN_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
-  const double a = -0.5;
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-  return 0.0;
-}
-
-template <int FILTER>
-__host__ __device__ __forceinline__ int rcn_ksize(int in_size, int out_size) {
-  double fs = (double)in_size / (double)out_size;
-  if (fs < 1.0) fs = 1.0;
-  return (int)ceil((FILTER == RCN_BILINEAR ? 1.0 : 2.0) * fs) * 2 + 1;
-}
-
-// precompute_coeffs + normalize_coeffs_8bpc for ONE output index xx: taps K[0 .. count) (stride `stride` ints), first source index xmin
-template <int FILTER>
-__device__ void rcn_coeffs(int in_size, int out_size, int xx, int* K, int stride, int& xmin_out, int& count_out) {
-  const double scale = (double)in_size / (double)out_size;
-  const double fs = scale < 1.0 ? 1.0 : scale;
-  const double support = (FILTER == RCN_BILINEAR ? 1.0 : 2.0) * fs, ss = 1.0 / fs;
-  const double center = (xx + 0.5) * scale;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) ww += rcn_filter<FILTER>((x + xmin - center + 0.5) * ss);
-  for (int x = 0; x < xmax; ++x) {
-    double k = rcn_filter<FILTER>((x + xmin - center + 0.5) * ss);
-    if (ww != 0.0) k /= ww;
-    K[x * stride] = k < 0.0 ? (int)(-0.5 + k * (double)(1 << RCN_PRECISION_BITS)) : (int)(0.5 + k * (double)(1 << RCN_PRECISION_BITS));
-  }
-  xmin_out = xmin;
-  count_out = xmax;
-}
-
-__device__ __forceinline__ int rcn_clip8(int s) {
-  s >>= RCN_PRECISION_BITS;                         // arithmetic shift, as Pillow's clip8
-  return s < 0 ? 0 : (s > 255 ? 255 : s);
-}
+#include "rcn.h"
 
 // desc row (8 int32): offset / 16, w, h, nw, nh, left, top, 0; the output is the out_h x out_w window at (left, top) of the resized image
 template <int FILTER>
@@ -90,14 +36,7 @@ __global__ __launch_bounds__(RCN_TX * RCN_WAVES) void resize_crop_normalize_kern
     const unsigned char* __restrict__ packed, long packed_bytes, const int* __restrict__ desc, int out_h, int out_w, int kmax,
     const float* __restrict__ lut, float* __restrict__ out, int tiles_x, int whole) {
   extern __shared__ int rcn_lds[];
-  int* Kx = rcn_lds;                                // [kmax][RCN_TX]
-  int* Ky = Kx + kmax * RCN_TX;                     // [RCN_TY][kmax]
-  int* x_min = Ky + RCN_TY * kmax;                  // [RCN_TX]
-  int* x_cnt = x_min + RCN_TX;                      // [RCN_TX]
-  int* y_min = x_cnt + RCN_TX;                      // [RCN_TY]
-  int* y_cnt = y_min + RCN_TY;                      // [RCN_TY]
-
-  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
   const int* d = desc + (size_t)b * 8;
   const size_t off = (size_t)(unsigned)d[0] * 16;
@@ -123,59 +62,8 @@ __global__ __launch_bounds__(RCN_TX * RCN_WAVES) void resize_crop_normalize_kern
     return;
   }
 
-  if (tid < RCN_TX) {
-    int mn = 0, cnt = 0;
-    if (ox < out_w) rcn_coeffs<FILTER>(w, nw, left + ox, Kx + tid, RCN_TX, mn, cnt);
-    x_min[tid] = mn;
-    x_cnt[tid] = cnt;
-  } else if (tid < RCN_TX + RCN_TY) {
-    const int r = tid - RCN_TX, oy = ty * RCN_TY + r;
-    int mn = 0, cnt = 0;
-    if (oy < out_h) rcn_coeffs<FILTER>(h, nh, top + oy, Ky + r * kmax, 1, mn, cnt);
-    y_min[r] = mn;
-    y_cnt[r] = cnt;
-  }
-  __syncthreads();
-
-  const int xmin = x_min[lane], xcnt = x_cnt[lane];
-  int ymin[RCN_RY], ycnt[RCN_RY];
-  int ylo = 0x7fffffff, yhi = 0;
-#pragma unroll
-  for (int r = 0; r < RCN_RY; ++r) {
-    ymin[r] = y_min[wave * RCN_RY + r];
-    ycnt[r] = y_cnt[wave * RCN_RY + r];
-    if (ycnt[r] > 0) {
-      ylo = min(ylo, ymin[r]);
-      yhi = max(yhi, ymin[r] + ycnt[r]);
-    }
-  }
-  int acc[RCN_RY][3];
-#pragma unroll
-  for (int r = 0; r < RCN_RY; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 1 << (RCN_PRECISION_BITS - 1);
-
-  const unsigned char* src = packed + off;
-  const int* ky = Ky + wave * RCN_RY * kmax;
-  for (int y = ylo; y < yhi; ++y) {                 // wave-uniform bounds
-    const unsigned char* p = src + ((size_t)y * w + xmin) * 3;
-    int s0 = 1 << (RCN_PRECISION_BITS - 1), s1 = s0, s2 = s0;
-    for (int t = 0; t < xcnt; ++t) {
-      const int k = Kx[t * RCN_TX + lane];
-      s0 += (int)p[3 * t] * k;
-      s1 += (int)p[3 * t + 1] * k;
-      s2 += (int)p[3 * t + 2] * k;
-    }
-    const int h0 = rcn_clip8(s0), h1 = rcn_clip8(s1), h2 = rcn_clip8(s2);      // the u8 intermediate of the horizontal pass
-#pragma unroll
-    for (int r = 0; r < RCN_RY; ++r) {
-      const int t = y - ymin[r];
-      if ((unsigned)t < (unsigned)ycnt[r]) {
-        const int k = ky[r * kmax + t];
-        acc[r][0] += h0 * k;
-        acc[r][1] += h1 * k;
-        acc[r][2] += h2 * k;
-      }
-    }
-  }
+  int px[RCN_RY][3];       // the tile's bytes: rcn.h
+  rcn_tile_u8<FILTER>(packed + off, w, h, nw, nh, ox < out_w ? left + ox : -1, top + ty * RCN_TY, out_h - ty * RCN_TY, kmax, rcn_lds, px);
 
   if (ox < out_w) {
 #pragma unroll
@@ -183,7 +71,7 @@ __global__ __launch_bounds__(RCN_TX * RCN_WAVES) void resize_crop_normalize_kern
       const int oy = ty * RCN_TY + wave * RCN_RY + r;
       if (oy < out_h) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) o[c * plane + (size_t)oy * out_w + ox] = lut[c * 256 + rcn_clip8(acc[r][c])];
+        for (int c = 0; c < 3; ++c) o[c * plane + (size_t)oy * out_w + ox] = lut[c * 256 + px[r][c]];
       }
     }
   }

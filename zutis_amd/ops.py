@@ -554,6 +554,78 @@ def resize_normalize(packed, desc, out_h: int, out_w: int, lut, filter: str = "b
     return out
 
 
+# ---------------------------------------------------------------------------------------- training samples (csrc/synth.hip)
+def _synth_chk(desc, name):
+    _chk(desc, torch.int32, f"{name} desc")
+    if desc.dim() != 2 or desc.shape[1] != 32 or desc.shape[0] == 0:
+        raise _lib.ZutisHipError(f"{name}: desc int32 [N, 32] expected, got {tuple(desc.shape)}")
+    return desc.shape[0]
+
+
+def synth_geometry(packed, desc, crop_size: int, ignore_index: int, kmax: int, fill_wh, work, out=None):
+    """random_scale + random_crop + random_hflip of N sub-images (zutis_amd.synth): packed u8 [bytes], desc int32 [N, 32], work int32
+    [N, 12] (initialised as include/zutis_hip.h says; receives the fill sums and the objects' boxes) -> u8 [N, C, C, 4] = (R, G, B, mask)."""
+    N = _synth_chk(desc, "synth_geometry")
+    _chk(packed, torch.uint8, "synth_geometry packed"); _chk(work, torch.int32, "synth_geometry work")
+    if packed.dim() != 1 or tuple(work.shape) != (N, 12):
+        raise _lib.ZutisHipError(f"synth_geometry: packed [bytes], work [N, 12] expected, got {tuple(packed.shape)}, {tuple(work.shape)}")
+    C = int(crop_size)
+    if out is None:
+        out = torch.empty((N, C, C, 4), dtype=torch.uint8, device=packed.device)
+    _chk(out, torch.uint8, "synth_geometry out")
+    if tuple(out.shape) != (N, C, C, 4):
+        raise _lib.ZutisHipError(f"synth_geometry: out {tuple(out.shape)}, expected {(N, C, C, 4)}")
+    _call("zh_synth_geometry_u8", _p(packed), packed.numel(), _p(desc), N, C, int(ignore_index), int(kmax), int(fill_wh[0]), int(fill_wh[1]),
+          _p(work), _p(out), _stream())
+    return out
+
+
+def synth_photometric(rgbm, desc, work):
+    """ColorJitter in desc's order + RandomGrayscale on u8 [N, C, C, 4], in place."""
+    N = _synth_chk(desc, "synth_photometric")
+    _chk(rgbm, torch.uint8, "synth_photometric rgbm"); _chk(work, torch.int32, "synth_photometric work")
+    if rgbm.dim() != 4 or rgbm.shape[0] != N or rgbm.shape[1] != rgbm.shape[2] or rgbm.shape[3] != 4 or tuple(work.shape) != (N, 12):
+        raise _lib.ZutisHipError(f"synth_photometric: rgbm [N, C, C, 4], work [N, 12] expected, got {tuple(rgbm.shape)}, {tuple(work.shape)}")
+    _call("zh_synth_photometric_u8", _p(rgbm), _p(desc), N, rgbm.shape[1], _p(work), _stream())
+    return rgbm
+
+
+def synth_blur(rgbm, desc, weights, out=None):
+    """The separable Gaussian (weights f32 [N, ksize]) of the sub-images whose desc flags say blur -> a second u8 [N, C, C, 4]; the
+    rows of the other sub-images are NOT written."""
+    N = _synth_chk(desc, "synth_blur")
+    _chk(rgbm, torch.uint8, "synth_blur rgbm"); _chk(weights, f32, "synth_blur weights")
+    if rgbm.dim() != 4 or rgbm.shape[0] != N or rgbm.shape[1] != rgbm.shape[2] or rgbm.shape[3] != 4 or weights.dim() != 2 or weights.shape[0] != N:
+        raise _lib.ZutisHipError(f"synth_blur: rgbm [N, C, C, 4], weights [N, ksize] expected, got {tuple(rgbm.shape)}, {tuple(weights.shape)}")
+    if out is None:
+        out = torch.empty_like(rgbm)
+    _chk(out, torch.uint8, "synth_blur out")
+    if out.shape != rgbm.shape:
+        raise _lib.ZutisHipError(f"synth_blur: out {tuple(out.shape)}, expected {tuple(rgbm.shape)}")
+    _call("zh_synth_blur_u8", _p(rgbm), _p(desc), _p(weights), N, rgbm.shape[1], weights.shape[1], _p(out), _stream())
+    return out
+
+
+def synth_compose(rgbm, blurred, desc, samples, work, lut, ignore_index: int):
+    """copy_paste per output pixel + normalisation: samples int32 [B, 4] = (first sub-image, n, first one-hot row, 0) ->
+    (image f32 [B, 3, C, C], semantic int64 [B, C, C], one-hot bool [sum n, C, C])."""
+    N = _synth_chk(desc, "synth_compose")
+    for t, name in ((rgbm, "rgbm"), (blurred, "blurred")):
+        _chk(t, torch.uint8, f"synth_compose {name}")
+        if t.dim() != 4 or t.shape[0] != N or t.shape[1] != t.shape[2] or t.shape[3] != 4 or t.shape != rgbm.shape:
+            raise _lib.ZutisHipError(f"synth_compose: {name} [N, C, C, 4] expected, got {tuple(t.shape)}")
+    _chk(samples, torch.int32, "synth_compose samples"); _chk(work, torch.int32, "synth_compose work"); _chk(lut, f32, "synth_compose lut")
+    if samples.dim() != 2 or samples.shape[1] != 4 or samples.shape[0] == 0 or tuple(work.shape) != (N, 12) or tuple(lut.shape) != (3, 256):
+        raise _lib.ZutisHipError(f"synth_compose: samples [B, 4], work [N, 12], lut [3, 256] expected, got {tuple(samples.shape)}, {tuple(work.shape)}, {tuple(lut.shape)}")
+    B, C = samples.shape[0], rgbm.shape[1]
+    image = torch.empty((B, 3, C, C), dtype=f32, device=rgbm.device)
+    semantic = torch.empty((B, C, C), dtype=torch.int64, device=rgbm.device)
+    onehot = torch.empty((N, C, C), dtype=torch.bool, device=rgbm.device)
+    _call("zh_synth_compose", _p(rgbm), _p(blurred), _p(desc), _p(samples), _p(work), _p(lut), N, B, C, int(ignore_index), _p(image), _p(semantic),
+          _p(onehot), _stream())
+    return image, semantic, onehot
+
+
 # ---------------------------------------------------------------------------------------- bilateral solver (float64)
 def denormalize_u8(x, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """utils/utils.py:261-273 on device: x f32 [3,H,W] -> rgb u8 [H,W,3]."""
