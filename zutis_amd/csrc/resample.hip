@@ -275,9 +275,55 @@ extern "C" int zh_cast_f32_f16(const float* x, const float* add, int add_rows, v
 
 // (bilinear index/weight: lin_weights, common.h)
 
+// ---- what the three upsample + arg-max kernels do with a pixel's label once it is known (compile-time epilogue).  Every lane of a wave
+//      that is still running calls it, `valid` = the lane owns the pixel `pix` (index into [B,H,W]): the scoring form talks to its wave.
+struct UaStore {                        // zh_upsample_argmax: the int64 label map
+  long long* labels;
+  __device__ __forceinline__ void operator()(bool valid, long pix, int label) const {
+    if (valid) labels[pix] = label;
+  }
+};
+#define ZH_GT_U8 0
+#define ZH_GT_RG16 1
+// zh_upsample_argmax_score: RunningScore._fast_hist (utils/running_score.py:11-16) on the label while it is in a register.
+// hist[n * gt + label] += 1 for gt < n.  Equal keys are merged inside the wave before memory is touched: the first pending lane's
+// key is broadcast, a ballot counts the lanes that hold it, that lane adds the count with ONE 64-bit atomic, and the loop goes on
+// with the lanes that are left — a natural image has a few distinct (gt, label) pairs per wave, so it runs a few times.  Integer
+// adds: exact and order-independent.  The loop's control flow is wave-uniform (the pending set is a ballot); it is bounded, so that a
+// ground truth of per-pixel noise costs what one atomic per pixel costs and no more.
+#define UA_MERGE_ROUNDS 8               // distinct keys a wave merges before its remaining lanes go to memory one by one
+struct UaScore {
+  const unsigned char* gt;
+  unsigned long long* hist;
+  long long* labels;                    // may be NULL
+  int n, rg16;
+  __device__ __forceinline__ void operator()(bool valid, long pix, int label) const {
+    int key = -1;
+    if (valid) {
+      if (labels) labels[pix] = label;
+      const int g = rg16 ? (int)gt[3 * pix] + 256 * (int)gt[3 * pix + 1] : (int)gt[pix];   // datasets/imagenet_s.py:93; B is ignored
+      if (g < n) key = g * n + label;                                                      // n <= 46340: fits; 255 / 1000 are dropped
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(key >= 0);
+    for (int round = 0; todo; ++round) {
+      if (round == UA_MERGE_ROUNDS) {   // many distinct pairs in this wave (noise, not an annotation): the lanes left add their own 1
+        if ((todo >> lane) & 1) atomicAdd(&hist[key], 1ull);
+        break;
+      }
+      const int leader = __ffsll((long long)todo) - 1;
+      const int k = __shfl(key, leader);
+      const unsigned long long same = __ballot(key == k);
+      if (lane == leader) atomicAdd(&hist[k], (unsigned long long)__popcll(same));
+      todo &= ~same;
+    }
+  }
+};
+
 // ---- fused bilinear upsample + argmax over classes (networks/zutis.py:366-372), never materialising
 //      [B,n,H,W].  logits [B,n,h,w] fp32 (NCHW, low-res) -> labels int64 [B,H,W]; first index on ties.
-__global__ __launch_bounds__(256) void upsample_argmax_kernel(const float* lo, long long* labels, int B, int n, int h, int w,
+template <class Epi>
+__global__ __launch_bounds__(256) void upsample_argmax_kernel(const float* lo, const Epi epi, int B, int n, int h, int w,
                                                               int H, int W, float scale_h, float scale_w) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   const long total = (long)B * H * W;
@@ -297,7 +343,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(const float* lo, l
     // torch.argmax: first maximal index; NaN is treated as maximal (propagates)
     if (c == 0 || v > best || (v != v && best == best)) { best = v; besti = c; }
   }
-  labels[idx] = besti;
+  epi(true, idx, besti);               // lanes past the last pixel have left: they are in no ballot
 }
 
 // LDS two-phase variant: a block owns a 32 x 32 output tile (each thread 4 pixels of one column) and walks the classes in
@@ -310,7 +356,8 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(const float* lo, l
 #define UA_TW 32
 #define UA_CH 32
 #define UA_PX (UA_TH * UA_TW / 256)
-__global__ __launch_bounds__(256) void upsample_argmax_lds_kernel(const float* lo, long long* labels, int n, int h, int w,
+template <class Epi>
+__global__ __launch_bounds__(256) void upsample_argmax_lds_kernel(const float* lo, const Epi epi, int n, int h, int w,
                                                                   int H, int W, float scale_h, float scale_w, int tiles_x, int tiles_y,
                                                                   int wr_max, int wc_max) {
   extern __shared__ __attribute__((aligned(16))) float ua_lds[];
@@ -392,7 +439,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_lds_kernel(const float* l
 #pragma unroll
   for (int i = 0; i < UA_PX; ++i) {
     const int oy = oy0 + tyl + (256 / UA_TW) * i;
-    if (oy < H && ox0 + txl < W) labels[((long)b * H + oy) * W + ox0 + txl] = besti[i];
+    epi(oy < H && ox0 + txl < W, ((long)b * H + oy) * W + ox0 + txl, besti[i]);   // a partial tile's spare lanes: valid = false
   }
 }
 
@@ -423,7 +470,8 @@ __device__ __forceinline__ float ua_max3(float a, float b, float c) {
   asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
 }
-__global__ __launch_bounds__(256) void upsample_argmax_pk_kernel(const float* lo, long long* labels, int n, int h, int w,
+template <class Epi>
+__global__ __launch_bounds__(256) void upsample_argmax_pk_kernel(const float* lo, const Epi epi, int n, int h, int w,
                                                                  int H, int W, float scale_h, float scale_w, int tiles_x, int tiles_y,
                                                                  int wr_max, int wc_max) {
   extern __shared__ __attribute__((aligned(16))) float ua_lds[];
@@ -546,13 +594,13 @@ __global__ __launch_bounds__(256) void upsample_argmax_pk_kernel(const float* lo
 #pragma unroll
   for (int i = 0; i < UA_PX; ++i) {
     const int oy = oy0 + tyl + (256 / UA_TW) * i;
-    if (oy < H && ox0 + txl < W) labels[((long)b * H + oy) * W + ox0 + txl] = besti[i];
+    epi(oy < H && ox0 + txl < W, ((long)b * H + oy) * W + ox0 + txl, besti[i]);   // a partial tile's spare lanes: valid = false
   }
 }
 
-extern "C" int zh_upsample_argmax(const float* logits_lo, long long* labels, int B, int n, int h, int w, int H, int W,
-                                  float scale_h, float scale_w, hipStream_t stream) {
-  ZH_CHECK_ARG(logits_lo && labels && B > 0 && n > 0 && h > 0 && w > 0 && H > 0 && W > 0, "zh_upsample_argmax: bad arguments");
+template <class Epi>
+static void ua_launch(const Epi epi, const float* logits_lo, int B, int n, int h, int w, int H, int W, float scale_h, float scale_w,
+                      hipStream_t stream) {
   // worst-case low-res window of a 32 x 32 output tile: ceil(extent * scale) + 2 rows / cols (identity sizes: extent)
   const int wr = (h == H ? UA_TH : (int)(UA_TH * scale_h) + 3), wc = (w == W ? UA_TW : (int)(UA_TW * scale_w) + 3);
   const size_t lds = (size_t)UA_CH * wr * (wc + UA_TW) * sizeof(float);
@@ -560,16 +608,34 @@ extern "C" int zh_upsample_argmax(const float* logits_lo, long long* labels, int
   const size_t lds_pk = (size_t)UA_CHP * wr * (wc + UA_TW) * sizeof(float);
   if (wr * wc <= 64 && lds_pk <= 48 * 1024 && tiles < (1L << 31)) {   // a window of <= 64 low-res pixels (upsampling by >= ~6x at 32 x 32 tiles)
     const int tiles_y = zh_cdiv(H, UA_TH), tiles_x = zh_cdiv(W, UA_TW);
-    hipLaunchKernelGGL(upsample_argmax_pk_kernel, dim3((unsigned)tiles), dim3(256), lds_pk, stream, logits_lo, labels,
+    hipLaunchKernelGGL((upsample_argmax_pk_kernel<Epi>), dim3((unsigned)tiles), dim3(256), lds_pk, stream, logits_lo, epi,
                        n, h, w, H, W, scale_h, scale_w, tiles_x, tiles_y, wr, wc);
   } else if (lds <= 48 * 1024 && tiles < (1L << 31)) {    // upsampling by >= ~2.5x; otherwise the direct kernel
     const int tiles_y = zh_cdiv(H, UA_TH), tiles_x = zh_cdiv(W, UA_TW);
-    hipLaunchKernelGGL(upsample_argmax_lds_kernel, dim3((unsigned)tiles), dim3(256), lds, stream, logits_lo, labels,
+    hipLaunchKernelGGL((upsample_argmax_lds_kernel<Epi>), dim3((unsigned)tiles), dim3(256), lds, stream, logits_lo, epi,
                        n, h, w, H, W, scale_h, scale_w, tiles_x, tiles_y, wr, wc);
   } else {
-    hipLaunchKernelGGL(upsample_argmax_kernel, dim3(zh_cdiv((long)B * H * W, 256)), dim3(256), 0, stream, logits_lo, labels, B, n, h, w, H, W, scale_h, scale_w);
+    hipLaunchKernelGGL((upsample_argmax_kernel<Epi>), dim3(zh_cdiv((long)B * H * W, 256)), dim3(256), 0, stream, logits_lo, epi, B, n, h, w, H, W, scale_h, scale_w);
   }
+}
+
+extern "C" int zh_upsample_argmax(const float* logits_lo, long long* labels, int B, int n, int h, int w, int H, int W,
+                                  float scale_h, float scale_w, hipStream_t stream) {
+  ZH_CHECK_ARG(logits_lo && labels && B > 0 && n > 0 && h > 0 && w > 0 && H > 0 && W > 0, "zh_upsample_argmax: bad arguments");
+  ua_launch(UaStore{labels}, logits_lo, B, n, h, w, H, W, scale_h, scale_w, stream);
   ZH_CHECK_LAUNCH("zh_upsample_argmax");
+  return ZH_OK;
+}
+
+// ---- the same launch with the confusion-matrix histogram as its epilogue (zutis.py:366-372 + utils/running_score.py:11-16): the
+//      label map is written only when the caller asks for it, the ground truth is read as the bytes of its PNG.
+extern "C" int zh_upsample_argmax_score(const float* logits_lo, const unsigned char* gt, int gt_format, long long* hist_accum,
+                                        long long* labels, int B, int n, int h, int w, int H, int W, float scale_h, float scale_w,
+                                        hipStream_t stream) {
+  ZH_CHECK_ARG(logits_lo && gt && hist_accum && B > 0 && n > 0 && n <= 46340 && h > 0 && w > 0 && H > 0 && W > 0 &&
+               (gt_format == ZH_GT_U8 || gt_format == ZH_GT_RG16), "zh_upsample_argmax_score: bad arguments");
+  ua_launch(UaScore{gt, (unsigned long long*)hist_accum, labels, n, gt_format == ZH_GT_RG16}, logits_lo, B, n, h, w, H, W, scale_h, scale_w, stream);
+  ZH_CHECK_LAUNCH("zh_upsample_argmax_score");
   return ZH_OK;
 }
 

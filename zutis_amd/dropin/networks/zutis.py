@@ -467,6 +467,14 @@ class ZUTIS(nn.Module):
             predictions.append(prediction)
         return predictions
 
+    @torch.no_grad()
+    def score_semantic(self, dict_outputs: dict, gt_dev: torch.Tensor, metric_meter, size: Optional[Tuple[int, int]] = None,
+                       gt_format: str = "u8") -> None:
+        """metric_meter.update(gt, self.predict(dict_outputs, "semantic", size=size)) with the confusion matrix counted by the arg-max
+        kernel itself (zutis.py:355-372 + utils/running_score.py:11-16): no label map, no copy to the host.  gt_dev: u8 on the
+        device, [B,H,W] or ([B,H,W,3], gt_format "rg16"); metric_meter: the drop-in RunningScore."""
+        metric_meter.update_device(self, dict_outputs, gt_dev, gt_format=gt_format, size=size)
+
     @staticmethod
     def non_maximum_suppression_indices(binary_masks, scores, category_ids, nms_type="hard", nms_threshold=0.3,
                                         sigma=0.5, threshold=0.001, iou=None):

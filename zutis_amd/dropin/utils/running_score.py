@@ -25,6 +25,20 @@ class RunningScore(object):
         for lt, lp in zip(label_trues, label_preds):
             _ops.confusion_hist(self._dev(lt).reshape(-1), self._dev(lp).reshape(-1), self._hist, self.n_classes)
 
+    def update_device(self, engine_or_network, dict_outputs, gt_dev, gt_format="u8", size=None):
+        """update(gt, network.predict(dict_outputs, "semantic", size=size)) without the label map: the arg-max kernel adds its
+        labels' confusion counts to this meter's histogram (zh_upsample_argmax_score).  gt_dev: u8 on the device, [B,H,W] ("u8") or
+        [B,H,W,3] ("rg16": R + 256 G, datasets/imagenet_s.py:93); engine_or_network: the drop-in ZUTIS or its ZutisEngine (the
+        engine needs dict_outputs["text_embeddings"] or the module's own)."""
+        net = engine_or_network
+        if hasattr(net, "_get_engine"):
+            eng, text = net._get_engine(), net.text_embeddings
+        else:
+            eng, text = net, dict_outputs["text_embeddings"]
+        if text.shape[0] != self.n_classes:
+            raise ValueError(f"update_device: {text.shape[0]} text embeddings, the meter has {self.n_classes} classes")
+        eng.score_semantic(dict_outputs["patch_tokens"], text, gt_dev, self._hist, gt_format=gt_format, size=size)
+
     def get_scores(self):
         hist = self.confusion_matrix
         with np.errstate(divide="ignore", invalid="ignore"):

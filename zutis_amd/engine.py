@@ -327,6 +327,16 @@ class ZutisEngine(_EngineBase):
         ops.upsample_argmax(lo, labels, B, n, h, w, H, Wd)
         return labels
 
+    def score_semantic(self, patch_tokens: torch.Tensor, text: torch.Tensor, gt: torch.Tensor, hist: torch.Tensor, gt_format: str = "u8",
+                       size: Optional[Tuple[int, int]] = None, labels: Optional[torch.Tensor] = None) -> None:
+        """predict_semantic + RunningScore.update in one launch (zutis.py:355-372 + utils/running_score.py:11-16): hist int64 [n * n] on
+        the device += the confusion counts of the arg-max labels against gt (u8 [B,H,W], or [B,H,W,3] with gt_format "rg16"), at
+        `size` (the low-res grid when None).  No label map is made unless `labels` (int64 [B,H,W]) is given."""
+        lo = self.semantic_logits_lowres(patch_tokens, text)
+        B, n, h, w = lo.shape
+        H, Wd = (h, w) if size is None else (int(size[0]), int(size[1]))
+        ops.upsample_argmax_score(lo, gt, hist, B, n, h, w, H, Wd, gt_format=gt_format, labels=labels)
+
     # ------------------------------------------------------------------ predict (instance)
     def instance_candidates(self, mask_proposals_last: torch.Tensor, patch_tokens: torch.Tensor, text: torch.Tensor,
                             threshold: float = 0.5, temperature: float = 5.0, size: Optional[Tuple[int, int]] = None,

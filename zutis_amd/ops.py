@@ -401,6 +401,28 @@ def upsample_argmax(logits_lo, labels, B, n, h, w, H, W):
     _call("zh_upsample_argmax", _p(logits_lo), _p(labels), B, n, h, w, H, W, lin_scale(h, H), lin_scale(w, W), _stream())
 
 
+GT_FORMATS = {"u8": 0, "rg16": 1}       # include/zutis_hip.h ZH_GT_*
+
+
+def upsample_argmax_score(logits_lo, gt, hist, B, n, h, w, H, W, gt_format: str = "u8", labels=None):
+    """upsample_argmax with RunningScore._fast_hist fused in (zutis.py:366-372 + utils/running_score.py:11-16): hist int64 [n * n] +=
+    bincount(n * gt + label) over the pixels with gt < n.  gt u8 [B,H,W] ("u8") or [B,H,W,3] ("rg16": R + 256 G, imagenet_s.py:93);
+    labels: None (no label map is made) or int64 [B,H,W]."""
+    _chk(logits_lo, f32, "upsample_argmax_score logits"); _chk(gt, torch.uint8, "upsample_argmax_score gt"); _chk(hist, torch.int64, "upsample_argmax_score hist")
+    if gt_format not in GT_FORMATS:
+        raise _lib.ZutisHipError(f"upsample_argmax_score: gt_format {gt_format!r} is not one of {sorted(GT_FORMATS)}")
+    want = (B, H, W) if gt_format == "u8" else (B, H, W, 3)
+    if tuple(logits_lo.shape) != (B, n, h, w) or tuple(gt.shape) != want or hist.numel() != n * n:
+        raise _lib.ZutisHipError(f"upsample_argmax_score: logits {(B, n, h, w)}, gt {want}, hist [{n * n}] expected, got "
+                                 f"{tuple(logits_lo.shape)}, {tuple(gt.shape)}, {tuple(hist.shape)}")
+    if labels is not None:
+        _chk(labels, torch.int64, "upsample_argmax_score labels")
+        if tuple(labels.shape) != (B, H, W):
+            raise _lib.ZutisHipError(f"upsample_argmax_score: labels {tuple(labels.shape)}, expected {(B, H, W)}")
+    _call("zh_upsample_argmax_score", _p(logits_lo), _p(gt), GT_FORMATS[gt_format], _p(hist), _p(labels), B, n, h, w, H, W,
+          lin_scale(h, H), lin_scale(w, W), _stream())
+
+
 def upsample_bilinear_nchw(x, planes, h, w, H, W, out=None, mask_u8=None, threshold=0.5, scale_h=None, scale_w=None):
     """scale_* default to in/out (size= form); pass 1/scale_factor for the scale_factor form with a cropped output."""
     sh = lin_scale(h, H) if scale_h is None else float(np.float32(scale_h))

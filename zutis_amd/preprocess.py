@@ -12,6 +12,8 @@ is also what crosses PCIe (3 bytes per source pixel instead of 12 per output pix
   ShapeBucketLoader     the same staging for MaskDataset's transform (datasets/index_dataset.py:405-411): batches of ONE resized shape,
                         gathered from a bounded window of paths ahead, so that the batched SelfMask + solver run batched
 
+  EvalBatchLoader       ShapeBucketLoader for evaluation: every image travels with its ground-truth PNG (one staging buffer, one copy)
+
 Threads, not processes: no child ever holds the device open, nothing is pickled, a worker's exception is raised by the caller.
 """
 from __future__ import annotations
@@ -183,10 +185,10 @@ class BatchLoader:
             im = im.resize((nw, nh), FILTERS[self.filter][2]).crop((left, top, left + out_wh[0], top + out_wh[1]))
         np.copyto(dst, np.asarray(im))
 
-    def _pack(self, pool: ThreadPoolExecutor, slot: int, chunk, sizes, boxes, out_wh):
+    def _pack(self, pool: ThreadPoolExecutor, slot: int, chunk, sizes, boxes, out_wh, extra: int = 0):
         """Lay `chunk` (files of `sizes` = (w, h), resized and cropped as `boxes` = ((nw, nh), (left, top)) say, to out_wh = (w, h) of the
         kernel's output) out in staging buffer `slot` and start its decodes: (staging, packed, desc, kmax, images resized on the host,
-        futures)."""
+        futures).  extra: bytes the staging buffer holds behind the packed images (packed stops in front of them)."""
         B, (ow, oh) = len(chunk), out_wh
         rows = np.zeros((B, DESC_INTS), np.int32)
         host_boxes, shapes, kmax, off = [], [], ksize(1, 1, self.filter), 0
@@ -203,8 +205,8 @@ class BatchLoader:
             shapes.append((off, h, w))
             off += -(-3 * w * h // ALIGN) * ALIGN
         head = B * DESC_INTS * 4
-        staging = self._staging(slot, head + off)
-        packed, desc = split_staging(staging, B)
+        staging = self._staging(slot, head + off + extra)
+        packed, desc = split_staging(staging[:head + off], B)
         desc.numpy()[...] = rows
         pix = packed.numpy()
         futures = [pool.submit(self._decode, p, pix[o:o + 3 * w * h].reshape(h, w, 3), size, hb, out_wh)
@@ -250,6 +252,18 @@ def mask_dataset_size(w: int, h: int, image_size):
     if (w <= h and w == s) or (h <= w and h == s):
         return w, h
     return (s, int(s * h / w)) if w < h else (int(s * w / h), s)
+
+
+def longer_edge_size(w: int, h: int, max_size):
+    """(nw, nh) of ImageNetSDataset's `resize(image, size=max_size, edge="longer", interpolation="bilinear")` (datasets/imagenet_s.py:71-76)
+    for a w x h file: an image whose longer edge exceeds max_size gets that edge capped and the other one int(float(a) / b * max_size)
+    (geometric_transforms.compute_size: the quotient first, truncated); any other image, and max_size None, stay as they are."""
+    if max_size is None or max(w, h) <= int(max_size):
+        return w, h
+    s = int(max_size)
+    if w > h:
+        return s, int(float(h) / w * s)
+    return int(float(w) / h * s), s
 
 
 def _buckets(shapes, batch_size: int, window: int):
@@ -343,3 +357,85 @@ class ShapeBucketLoader(BatchLoader):
                 if pending is not None:
                     for f in pending[1]:
                         f.cancel()
+
+
+GT_MODES = {"u8": ("L", "P"), "rg16": ("RGB",)}      # Pillow modes np.array() turns into u8 [H, W] / u8 [H, W, 3]
+GT_CHANNELS = {"u8": 1, "rg16": 3}
+
+EvalBatch = collections.namedtuple("EvalBatch", "paths gt_paths indices size_hw out_hw staging packed_bytes gt kmax n_host")
+EvalBatch.__doc__ = """One decoded evaluation batch: images of ONE file size that resize to ONE shape, with their ground truth.  paths /
+gt_paths / indices: the files and their positions in the loader's lists; size_hw: the (H, W) every file of the batch has; out_hw: what
+the images resize to; staging: u8 [32 * B + packed_bytes + ground-truth bytes] — descriptor rows, the packed images, then gt, the host
+view u8 [B, H, W] ("u8") or [B, H, W, 3] ("rg16") of its tail; kmax, n_host as in Batch."""
+
+
+def split_eval_staging(staging: torch.Tensor, B: int, packed_bytes: int, gt_shape):
+    """(packed, desc, gt) views of an EvalBatch's staging tensor (host or device)."""
+    head = B * DESC_INTS * 4 + packed_bytes
+    packed, desc = split_staging(staging[:head], B)
+    return packed, desc, staging[head:].view(gt_shape)
+
+
+def eval_bucket_key(w: int, h: int, gw: int, gh: int, max_size):
+    """The key EvalBatchLoader groups by: (the image's resized (nw, nh), the ground truth's (gw, gh)) — one launch of the resize and one of
+    the scoring kernel serve a batch, so both shapes are shared."""
+    return longer_edge_size(w, h, max_size), (gw, gh)
+
+
+class EvalBatchLoader(ShapeBucketLoader):
+    """ShapeBucketLoader for the validation datasets: image i is scored against the ground-truth PNG gt_paths[i] at the file's own size
+    (trainer.py:322-325), so a batch shares the image file size as well as the resized shape (eval_bucket_key), and the ground truth is
+    decoded by the same threads into the tail of the same staging buffer.  max_size: None (the image goes in as it is: coco2017.py,
+    coco20k.py) or the cap of the longer edge (longer_edge_size, imagenet_s.py:71-76), Pillow BILINEAR.  gt_format "u8": an 8-bit
+    grey or palette PNG, the byte is the label; "rg16": an RGB PNG, label R + 256 G (imagenet_s.py:93).  A ground-truth file of
+    another mode, or of another size than its image, raises ValueError naming the file."""
+
+    def __init__(self, paths: Sequence[str], gt_paths: Sequence[str], max_size, batch_size: int, n_workers: int, window: int = 512,
+                 gt_format: str = "u8", pin=None):
+        if gt_format not in GT_MODES:
+            raise ValueError(f"EvalBatchLoader: gt_format {gt_format!r} is not one of {sorted(GT_MODES)}")
+        if len(paths) != len(gt_paths):
+            raise ValueError("EvalBatchLoader: one ground-truth file per image")
+        super().__init__(paths, max_size, batch_size, n_workers, window=window, filter="bilinear", pin=pin)
+        self.gt_paths, self.max_size, self.gt_format = list(gt_paths), max_size, gt_format
+
+    def _gt_size(self, path: str):
+        with Image.open(path) as im:            # header only
+            if im.mode not in GT_MODES[self.gt_format]:
+                raise ValueError(f"{path}: ground truth of mode {im.mode!r}, gt_format {self.gt_format!r} needs one of {GT_MODES[self.gt_format]}")
+            return im.size
+
+    def _decode_gt(self, path: str, dst: np.ndarray):
+        with Image.open(path) as im:
+            a = np.asarray(im)
+        if a.dtype != np.uint8 or a.shape != dst.shape:
+            raise ValueError(f"{path}: ground truth decodes to {a.dtype} {a.shape}, expected uint8 {dst.shape}")
+        np.copyto(dst, a)
+
+    def _groups(self, pool: ThreadPoolExecutor):
+        sizes = {}
+
+        def keys():
+            for start in range(0, len(self.paths), self.window):
+                block = self.paths[start:start + self.window]
+                gts = list(pool.map(self._gt_size, self.gt_paths[start:start + self.window]))
+                for i, wh in enumerate(pool.map(self._size, block), start):
+                    if gts[i - start] != wh:
+                        raise ValueError(f"{self.gt_paths[i]}: ground truth of size {gts[i - start]}, its image {self.paths[i]} is {wh}")
+                    sizes[i] = wh
+                for i in range(start, start + len(block)):
+                    yield eval_bucket_key(*sizes[i], *sizes[i], self.max_size)
+
+        for idx in _buckets(keys(), self.batch_size, self.window):
+            wh = [sizes.pop(i) for i in idx]
+            yield idx, wh, longer_edge_size(*wh[0], self.max_size)
+
+    def _start(self, pool: ThreadPoolExecutor, slot: int, group):
+        idx, sizes, (nw, nh) = group
+        B, (w, h), ch = len(idx), sizes[0], GT_CHANNELS[self.gt_format]
+        chunk, gts = [self.paths[i] for i in idx], [self.gt_paths[i] for i in idx]
+        staging, packed, desc, kmax, n_host, futures = self._pack(pool, slot, chunk, sizes, [((nw, nh), (0, 0))] * B, (nw, nh), extra=B * h * w * ch)
+        gt = staging[B * DESC_INTS * 4 + packed.numel():].view((B, h, w) if ch == 1 else (B, h, w, ch))
+        gt_np = gt.numpy()
+        futures += [pool.submit(self._decode_gt, p, gt_np[b]) for b, p in enumerate(gts)]
+        return EvalBatch(chunk, gts, idx, (h, w), (nh, nw), staging, packed.numel(), gt, kmax, n_host), futures
