@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 231 /* 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 232 /* 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -462,6 +462,31 @@ int zh_upsample_ce_bwd(const float* logits_lo, const long long* labels, const fl
  * einsum("nc,bchw->bnhw") of criterion.py:88-90 and its transpose for the token gradient.  fp32, fixed k order. */
 int zh_gemm_f32_strided(const float* A, long sAb, long sAm, long sAk, const float* Bm, long sBb, long sBn, long sBk, float* C,
                         long sCb, long sCm, long sCn, int batch, int M, int N, int K, zh_stream_t stream);
+
+/* The criterion's assignment on the device: scipy.optimize.linear_sum_assignment(cost_matrix) of criterion.py:133 for every (image,
+ * layer) of one call, and the matched costs summed into the mask loss of criterion.py:145,150.  costs / inst_off / skip: exactly what
+ * zh_mask_match_cost wrote and read (image b's [L, n_b, Q] float32 block at L * inst_off[b] * Q); n_max = max instances of an image,
+ * n_tot = inst_off[B].  One wavefront per problem runs scipy's rectangular shortest-augmenting-path solve (Crouse / Jonker-Volgenant)
+ * in float64 with scipy's scan order and tie rule, transposed when n_b > Q: the matches are scipy's, ties included.
+ * Outputs: pairs int32 [n_pairs, 4] = (b, l, q, i) in (b, l, i) order (the tensor zh_mask_match_grad reads; 16-byte aligned, room for
+ * sum_b L * min(n_b, Q) rows), *n_pairs, *mask_loss = f32(float64 sum of the matched costs in that order / B).  An image with
+ * skip[b] != 0 or no instance gives no pairs.  A problem with a non-finite cost gives no pairs and ORs ZH_STATUS_NONFINITE into
+ * *status — unlike scipy, which accepts +inf entries, every cost must be finite (zh_mask_match_cost cannot produce a non-finite cost
+ * without having set ZH_STATUS_RANGE).  Limit: max(n_max, Q) <= zh_linear_assignment_max_dim() = 1024 (32 bytes of LDS state per
+ * column, 16 per row: 48 KB at the cap), ZH_ERR_ARG above it.  workspace >= zh_linear_assignment_workspace_size. */
+int zh_linear_assignment_max_dim(void);
+size_t zh_linear_assignment_workspace_size(int B, int L, int n_tot);
+int zh_linear_assignment(const float* costs, const int* inst_off, const int* skip, int B, int L, int Q, int n_max, int n_tot,
+                         int* pairs, int* n_pairs, float* mask_loss, int* status, void* workspace, size_t workspace_bytes,
+                         zh_stream_t stream);
+/* The ragged ground truth of a criterion call (criterion.py:97-118: one [n_b, H, W] tensor per image) -> gt_u8 [n_tot, H, W]
+ * (non-zero -> 1) and inst_off int32 [B + 1] on the device, in one launch per 32 images.  src / counts: HOST arrays [B] of the
+ * images' DEVICE source pointers and instance counts — they travel as kernel arguments, so nothing is copied to the device and the
+ * entry cannot be part of a launch plan; elem_size 1 (bool, uint8) or 8 (int64); HW = H * W.  An image whose source pointer IS its
+ * place in gt_u8 is left as it is (masks that already lie packed in one allocation: only inst_off is written); any other overlap of a
+ * source with gt_u8 is undefined.  gt_u8 may be NULL when every count is 0. */
+int zh_pack_masks_u8(const void* const* src, const int* counts, int B, int elem_size, long HW, unsigned char* gt_u8, int* inst_off,
+                     zh_stream_t stream);
 
 /* Native launch plans (zutis_amd/plan.py): replay n recorded calls of the entry points above (op id + 32 argument words
  * each; dispatcher generated from this header) in one C loop; zh_plan_run2 alternates two plans on two streams. */

@@ -55,9 +55,10 @@ def parse_declarations(text: str) -> dict:
             if not (t and re.fullmatch(r"[A-Za-z_]\w*", n)):
                 raise ZutisHipError(f"{name}: cannot read the parameter {a!r}")
             params.append((t, n))
-        # plannable = device-pointer / scalar arguments only, stream last (zh_denormalize_u8 takes HOST float[3] pointers)
+        # plannable = device-pointer / scalar arguments only, stream last (zh_denormalize_u8 takes HOST float[3] pointers,
+        # zh_pack_masks_u8 HOST pointer / count tables)
         plannable = (ret == "int" and bool(params) and params[-1][0] == "zh_stream_t" and not name.startswith("zh_plan_")
-                     and name != "zh_denormalize_u8")
+                     and name not in ("zh_denormalize_u8", "zh_pack_masks_u8"))
         out[name] = Entry(ret, params, _ctype(name, ret, True), [_ctype(name, t) for t, _ in params], plannable)
     unread = sorted(set(re.findall(r"\b(zh_[a-z0-9_]+)\s*\(", text)) - set(out))
     if unread:

@@ -23,7 +23,7 @@ MAX_SCRATCH = int(os.environ.get("ZH_BUILD_MAX_SCRATCH", "0"))    # bytes per la
 MIN_OCCUPANCY = {"attention.hip": {"attn_f16_kernelILi64ELi4ELi1ELi0EE": 3, "attn_f16_kernelILi64ELi4ELi0ELi0EE": 3,
                                    "attn_f16_kernelILi64ELi4ELi1ELi1EE": 2, "attn_f16_kernelILi96ELi4ELi1ELi0EE": 2,
                                    "attn_f16_kernelILi96ELi4ELi0ELi0EE": 2, "attn_f16_kernelILi96ELi4ELi1ELi1EE": 2}}
-SOURCES = ["capi.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "synth.hip", "plan.hip"]
+SOURCES = ["capi.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "assign.hip", "synth.hip", "plan.hip"]
 
 
 def _hipcc() -> str:

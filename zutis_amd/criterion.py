@@ -13,6 +13,11 @@ backward.  Here (csrc/criterion.hip):
   * backward: zh_mask_match_grad / zh_upsample_ce_bwd push the full-resolution gradients through the adjoint of the bilinear
     upsample into the low-res inputs (never writing them at full resolution), then the transposed GEMM gives d tokens.
 
+HipCriterion(..., assignment="device") keeps the step on the device between those two groups of kernels (csrc/assign.hip): ground
+truth that is already on the GPU is packed there (zh_pack_masks_u8, or not at all when it lies packed already), zh_linear_assignment
+solves every (image, layer) exactly as scipy does and writes the pairs and the mask loss where the backward reads them, and the host
+does ONE small device -> host copy (status word, CE mean and count, mask loss, pair count, pairs) and no host -> device copy.
+
 The text embeddings are constants of the criterion (the frozen CLIP text features of the reference): no gradient flows into them.
 There is no CPU fallback: CPU tensors raise ZutisHipError.
 """
@@ -93,8 +98,10 @@ def _check_batch(props, gts, tokens, te, sem):
                   f"{tuple(sem.shape) if isinstance(sem, torch.Tensor) else type(sem).__name__}")
 
 
-def _pack_gt(gts, dev):
-    """The ragged GT list -> ONE host buffer [inst_off int32 (B + 1, padded to 16 bytes) | masks u8 [n_tot, H, W]], copied once."""
+def _pack_gt(gts, dev, on_device=False):
+    """The ragged GT list -> ONE host buffer [inst_off int32 (B + 1, padded to 16 bytes) | masks u8 [n_tot, H, W]], copied once.
+    on_device (assignment="device"): when every GT tensor is on `dev` already, nothing goes to the host — ops.pack_masks_u8 packs
+    them there (bool views of one allocation in order, as zutis_amd.synth delivers them, are used where they lie)."""
     B = len(gts)
     for g in gts:
         assert len(g.shape) == 3, f"Invalid ground truth instance masks shape: {len(g.shape)} != 3"
@@ -105,6 +112,12 @@ def _pack_gt(gts, dev):
     counts = [int(g.shape[0]) for g in gts]
     off = np.zeros(B + 1, dtype=np.int32)
     off[1:] = np.cumsum(counts)
+    if on_device and all(isinstance(g, torch.Tensor) and g.device == dev for g in gts):
+        src = [g.detach() for g in gts]
+        if not (all(g.dtype in (torch.bool, torch.uint8) for g in src) or all(g.dtype == torch.int64 for g in src)):
+            src = [g != 0 for g in src]                         # any other dtype: compared on the device
+        gt_u8, inst_off, _ = ops.pack_masks_u8(src, H, W)
+        return inst_off, gt_u8, off, H, W
     head = (4 * (B + 1) + 15) // 16 * 16
     buf = torch.zeros(head + int(off[-1]) * H * W, dtype=torch.uint8)
     buf[:4 * (B + 1)] = torch.from_numpy(off.view(np.uint8))
@@ -124,16 +137,38 @@ class HipCriterion:
             weight_mask_loss: float = 1.0,
             weight_dice_loss: float = 1.0,
             weight_bce_loss: float = 1.0,
-            ignore_index: int = 255
+            ignore_index: int = 255,
+            *,
+            assignment: str = "host"
     ):
+        """assignment (keyword-only, after the reference's arguments): "host" solves the assignments with scipy on the host, as the
+        reference does.  "device" solves them on the GPU (zh_linear_assignment: scipy's algorithm, scan order and tie rule in
+        float64 — the same matches, ties included), packs ground truth that is already on the GPU there, and makes one small
+        device -> host copy per call and no host -> device copy.  In device mode `last_costs` stays empty (use host mode to look
+        at the costs), a non-finite cost raises ValueError (scipy would accept +inf entries; the cost kernel cannot produce one
+        without the range assert firing first), and a call with more than ops.ASSIGN_MAX_DIM (1024) queries or instances of one
+        image — the solver's LDS state — is solved on the host as in "host" mode.  Bool ground-truth views of one allocation are
+        read where they lie, forward and backward: like the proposals, they must not be overwritten between the two."""
+        self.assignment = assignment
         self.text_embeddings: torch.Tensor = text_embeddings  # n_categories x n_dims
         self.weight_ce_loss: float = weight_ce_loss
         self.weight_mask_loss: float = weight_mask_loss
         self.weight_dice_loss: float = weight_dice_loss
         self.weight_bce_loss: float = weight_bce_loss
         self.ignore_index: int = ignore_index
-        self.last_costs: Dict = {}          # (image, layer) -> float32 [n_i, Q] cost matrix of the last call (tests / inspection)
+        self.last_costs: Dict = {}          # (image, layer) -> float32 [n_i, Q] cost matrix of the last call (tests / inspection; host mode)
         self.last_matches: Dict = {}        # (image, layer) -> (instance indices, query indices)
+
+    @property
+    def assignment(self) -> str:
+        """"host" or "device" (see __init__); may be set between calls."""
+        return self._assignment
+
+    @assignment.setter
+    def assignment(self, value: str):
+        if value not in ("host", "device"):
+            raise ValueError(f"HipCriterion: assignment must be 'host' or 'device', got {value!r}")
+        self._assignment = value
 
     def __call__(
             self,
@@ -156,16 +191,26 @@ class HipCriterion:
         p5 = props.detach().to(torch.float32)
         p5 = (p5.unsqueeze(1) if props.dim() == 4 else p5).contiguous()
         _, L, Q, h, w = p5.shape
-        inst_off, gt_u8, off, H, W = _pack_gt(list(gts), dev)
+        n_inst = max((int(g.shape[0]) for g in gts if len(g.shape)), default=0)
+        on_device = self.assignment == "device" and max(n_inst, Q) <= ops.ASSIGN_MAX_DIM     # above the cap: the host solve
+        inst_off, gt_u8, off, H, W = _pack_gt(list(gts), dev, on_device)
         n_tot, n_max = int(off[-1]), int(np.diff(off).max()) if B else 0
         labels = sem.to(dev).to(torch.int64).contiguous()
         if tuple(labels.shape) != (B, H, W):
             raise _lib.ZutisHipError(f"HipCriterion: semantic masks must be [{B}, {H}, {W}], got {tuple(labels.shape)}")
 
-        # ONE readback buffer: [status, -, ce mean, ce count, skip [B], costs [L * n_tot * Q]]
-        rb = torch.zeros(4 + B + L * n_tot * Q, dtype=torch.int32, device=dev)
-        status, ce_out, skip = rb[0:1], rb[2:4].view(torch.float32), rb[4:4 + B]
-        costs = rb[4 + B:].view(torch.float32)
+        if on_device:
+            # ONE readback buffer: [status, n_pairs, ce mean, ce count, mask loss, -, -, -, pairs [cap, 4]]; skip and costs stay on the device
+            cap = ops.assignment_pairs_capacity(B, L, Q, n_max, n_tot)
+            rb = torch.zeros(8 + 4 * cap, dtype=torch.int32, device=dev)
+            status, ce_out = rb[0:1], rb[2:4].view(torch.float32)
+            skip = torch.empty(B, dtype=torch.int32, device=dev)
+            costs = torch.empty(max(1, L * n_tot * Q), dtype=torch.float32, device=dev)
+        else:
+            # ONE readback buffer: [status, -, ce mean, ce count, skip [B], costs [L * n_tot * Q]]
+            rb = torch.zeros(4 + B + L * n_tot * Q, dtype=torch.int32, device=dev)
+            status, ce_out, skip = rb[0:1], rb[2:4].view(torch.float32), rb[4:4 + B]
+            costs = rb[4 + B:].view(torch.float32)
 
         # CE: low-res logits [B, n_cat, h2, w2] = te . tok, then upsample -> LSE -> NLL
         te = self.text_embeddings.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -184,6 +229,8 @@ class HipCriterion:
         ops.mask_match_cost(p5, gt_u8, inst_off, n_max, H, W, costs, stat_p, stat_pg, stat_g, skip, status,
                             self.weight_dice_loss, self.weight_bce_loss)
 
+        if on_device:                                           # the assignments of every (image, layer): one call, no host trip
+            ops.linear_assignment_batched(costs, inst_off, skip, B, L, Q, n_max, n_tot, rb[8:], rb[1:2], rb[4:5].view(torch.float32), status)
         host = rb.cpu().numpy()                                 # the one device -> host copy (synchronises)
         word = int(host[0])
         if word & ops.STATUS_RANGE:                             # the reference's asserts, criterion.py:71-72 (error path only)
@@ -193,6 +240,24 @@ class HipCriterion:
         if word & ops.STATUS_LABEL:
             raise ValueError(f"HipCriterion: a semantic label is neither in [0, {n_cat}) nor ignore_index={self.ignore_index}")
         ce_value = float(host[2:4].view(np.float32)[0])
+        meta_m = {"H": H, "W": W, "wd": self.weight_dice_loss, "wb": self.weight_bce_loss, "loss_scale": 1.0 / B,
+                  "shape": props.shape, "dtype": props.dtype}
+        if on_device:
+            if word & ops.STATUS_NONFINITE:
+                raise ValueError("HipCriterion: a matching cost is not finite (assignment='device' needs finite costs)")
+            n_pairs = int(host[1])
+            pairs_h = host[8:8 + 4 * n_pairs].reshape(-1, 4)
+            mask_value = host[4:5].view(np.float32)[0]
+            self.last_costs, self.last_matches = {}, {}
+            instance_indices = query_indices = None
+            # the pairs are in (b, l, i) order: one run per matched (image, layer)
+            cuts = np.flatnonzero(np.any(pairs_h[1:, :2] != pairs_h[:-1, :2], axis=1)) + 1 if n_pairs else np.zeros(0, dtype=np.int64)
+            for run in np.split(pairs_h, cuts) if n_pairs else []:
+                instance_indices, query_indices = run[:, 3].astype(np.int64), run[:, 2].astype(np.int64)
+                self.last_matches[(int(run[0, 0]), int(run[0, 1]))] = (instance_indices, query_indices)
+            mask_loss = _MaskTerm.apply(props, p5, gt_u8, inst_off, rb[8:8 + 4 * n_pairs].view(-1, 4), stat_p, stat_pg, stat_g,
+                                        rb[4:5].view(torch.float32)[0], meta_m)
+            return self._finish(mask_loss, tokens, lo, te, labels, lse, ce_out, ce_value, mask_value, instance_indices, query_indices)
         skip_h = host[4:4 + B]
         cost_h = host[4 + B:].view(np.float32)
 
@@ -219,10 +284,11 @@ class HipCriterion:
         hb[0] = mask_value.view(np.int32)
         hb[4:] = pairs
         db = torch.from_numpy(hb).to(dev)                       # the one host -> device copy
-        meta_m = {"H": H, "W": W, "wd": self.weight_dice_loss, "wb": self.weight_bce_loss, "loss_scale": 1.0 / B,
-                  "shape": props.shape, "dtype": props.dtype}
         mask_loss = _MaskTerm.apply(props, p5, gt_u8, inst_off, db[4:].view(-1, 4), stat_p, stat_pg, stat_g,
                                     db[0:1].view(torch.float32)[0], meta_m)
+        return self._finish(mask_loss, tokens, lo, te, labels, lse, ce_out, ce_value, mask_value, instance_indices, query_indices)
+
+    def _finish(self, mask_loss, tokens, lo, te, labels, lse, ce_out, ce_value, mask_value, instance_indices, query_indices):
         ce_loss = _CETerm.apply(tokens, lo, te, labels, lse, ce_out, {"ignore_index": self.ignore_index, "dtype": tokens.dtype})
         loss = self.weight_mask_loss * mask_loss + self.weight_ce_loss * ce_loss
         return {

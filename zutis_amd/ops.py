@@ -787,6 +787,86 @@ def mask_match_grad(proposals, gt_u8, inst_off, pairs, stat_p, stat_pg, stat_g, 
     return out
 
 
+ASSIGN_MAX_DIM = 1024     # zh_linear_assignment_max_dim(): cap on max(instances of an image, queries), from the solver's LDS state
+
+
+def assignment_pairs_capacity(B, L, Q, n_max, n_tot) -> int:
+    """Rows of the pairs buffer linear_assignment_batched asks for: a bound on sum_b L * min(n_b, Q) from the shape arguments alone."""
+    return L * min(n_tot, B * min(n_max, Q))
+
+
+def linear_assignment_batched(costs, inst_off, skip, B, L, Q, n_max, n_tot, pairs, n_pairs, mask_loss, status):
+    """scipy.optimize.linear_sum_assignment for every (image, layer) of the costs zh_mask_match_cost wrote, in one call: pairs int32
+    [assignment_pairs_capacity(), 4] = (b, l, q, i) in (b, l, i) order, n_pairs int32 [1], mask_loss f32 [1] = matched costs / B, and
+    STATUS_NONFINITE OR-ed into status for a problem with a non-finite cost (which gives no pairs; scipy would accept +inf).
+    max(n_max, Q) > ASSIGN_MAX_DIM is the library's argument error (see zutis_hip.h)."""
+    _chk(costs, f32, "linear_assignment costs")
+    _chk(inst_off, torch.int32, "linear_assignment inst_off")
+    _chk(skip, torch.int32, "linear_assignment skip")
+    _chk(pairs, torch.int32, "linear_assignment pairs")
+    if (costs.numel() < L * n_tot * Q or pairs.numel() < 4 * assignment_pairs_capacity(B, L, Q, n_max, n_tot) or inst_off.numel() < B + 1
+            or skip.numel() < B):
+        raise _lib.ZutisHipError("linear_assignment: a buffer is smaller than its shape arguments say")
+    ws, need = _workspace("zh_linear_assignment_workspace_size", costs.device, B, L, n_tot)
+    _call("zh_linear_assignment", _p(costs) if n_tot else None, _p(inst_off), _p(skip), B, L, Q, n_max, n_tot,
+          _p(pairs) if n_tot else None, _p(n_pairs), _p(mask_loss), _p(status), _p(ws), need, _stream())
+
+
+def linear_assignment(cost: torch.Tensor):
+    """(rows, cols) int64 arrays = scipy.optimize.linear_sum_assignment(cost) for ONE float32 [n, Q] matrix on the GPU, solved by
+    the device kernel.  Every entry must be finite (ValueError otherwise; scipy would accept +inf)."""
+    if cost.dim() != 2:
+        raise _lib.ZutisHipError(f"linear_assignment: expected a [n, Q] matrix, got {tuple(cost.shape)}")
+    _chk(cost, f32, "linear_assignment cost")
+    n, Q = (int(d) for d in cost.shape)
+    if n == 0 or Q == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    dev = cost.device
+    inst_off = torch.tensor([0, n], dtype=torch.int32, device=dev)
+    out = torch.zeros(4 + 4 * min(n, Q), dtype=torch.int32, device=dev)      # [status, n_pairs, loss, skip | pairs]
+    linear_assignment_batched(cost.reshape(-1), inst_off, out[3:4], 1, 1, Q, n, n, out[4:], out[1:2], out[2:3].view(f32), out[0:1])
+    h = out.cpu().numpy()
+    if h[0] & STATUS_NONFINITE:
+        raise ValueError("linear_assignment: the cost matrix has a non-finite entry")
+    pr = h[4:4 + 4 * int(h[1])].reshape(-1, 4).astype(np.int64)
+    return pr[:, 3].copy(), pr[:, 2].copy()
+
+
+def pack_masks_u8(srcs, H: int, W: int):
+    """[bool | uint8 | int64 [n_b, H, W] GPU tensors] -> (gt_u8 [n_tot, H, W] with non-zero -> 1, inst_off int32 [B + 1] on the
+    device, counts): one zh_pack_masks_u8 launch per 32 images, nothing copied from or to the host (the pointers and counts are
+    kernel arguments).  Bool sources (bytes 0 / 1 already) that lie back to back in one allocation, in order, are not copied:
+    gt_u8 is then a view of that allocation and only inst_off is written."""
+    import ctypes
+    if _lib.RECORDER is not None:
+        raise _lib.ZutisHipError("pack_masks_u8 takes host tables: it cannot be recorded into a launch plan")
+    B = len(srcs)
+    sizes = {g.element_size() for g in srcs if g.shape[0]}
+    if any(g.dtype not in (torch.bool, torch.uint8, torch.int64) for g in srcs) or len(sizes) > 1:
+        raise _lib.ZutisHipError("pack_masks_u8: the sources must be all bool / uint8 or all int64")
+    es = sizes.pop() if sizes else 1
+    srcs = [g.contiguous() for g in srcs]
+    counts = [int(g.shape[0]) for g in srcs]
+    n_tot, HW = sum(counts), H * W
+    dev = srcs[0].device
+    live = [g for g in srcs if g.shape[0]]
+    gt_u8 = None
+    if live and all(g.dtype == torch.bool for g in live):
+        base, first, at = live[0].data_ptr(), live[0], 0
+        for g in live:
+            if g.data_ptr() != base + at or g.untyped_storage().data_ptr() != first.untyped_storage().data_ptr():
+                break
+            at += g.shape[0] * HW
+        else:
+            gt_u8 = torch.empty(0, dtype=torch.uint8, device=dev).set_(first.untyped_storage(), first.storage_offset(), (n_tot, H, W))
+    if gt_u8 is None:
+        gt_u8 = torch.empty((n_tot, H, W), dtype=torch.uint8, device=dev)
+    inst_off = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    ptrs = (ctypes.c_void_p * B)(*[_p(g) if g.shape[0] else None for g in srcs])
+    _call("zh_pack_masks_u8", ptrs, (ctypes.c_int * B)(*counts), B, es, HW, _p(gt_u8) if n_tot else None, _p(inst_off), _stream())
+    return gt_u8, inst_off, counts
+
+
 def upsample_ce_fwd(logits_lo, labels, ignore_index, out, status, lse=None):
     """logits_lo f32 [B, n_cat, h, w], labels int64 [B, H, W] -> out f32 [2] = (mean NLL, valid count); lse f32 [B, H, W] returned."""
     _chk(logits_lo, f32, "upsample_ce logits_lo")
