@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 232 /* 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 233 /* 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -261,6 +261,18 @@ int zh_upsample_argmax(const float* logits_lo, long long* labels, int B, int n, 
 int zh_upsample_argmax_score(const float* logits_lo, const unsigned char* gt, int gt_format, long long* hist_accum,
                              long long* labels, int B, int n, int h, int w, int H, int W, float scale_h, float scale_w,
                              zh_stream_t stream);
+
+/* zh_upsample_argmax with the label leaving as the bytes of the file it becomes: zutis.py:366-372 in the two formats
+ * zh_upsample_argmax_score reads — datasets/imagenet_s.py:93 read backwards.  The label of a pixel is exactly zh_upsample_argmax's.
+ * labels_out u8, or NULL: ZH_GT_U8 [B,H,W], the byte is the label (n <= 256); ZH_GT_RG16 [B,H,W,3] interleaved, R = label & 255,
+ * G = label >> 8, B = 0 (n <= 65536).  overlay_out u8 [B,H,W,3], or NULL (not both): the colour picture over the decoded image,
+ * out[p][c] = (img[p][c] * (256 - alpha) + palette[label][c] * alpha + 128) >> 8 in integers, alpha in 0..256 (256: the pure palette
+ * colour, 0: the image).  palette u8 [n,3].  img is image b of a staging buffer as zh_resize_normalize_u8 takes it: HWC u8 at
+ * packed + 16 * desc[8 b], of size W x H — desc int32 [B, 8] rows (offset / 16, w, h, ...).  packed and desc are NOT checked here
+ * (every row's (w, h) must be (W, H) and lie inside packed: the caller's duty); they are read only with an overlay. */
+int zh_upsample_argmax_bytes(const float* logits_lo, unsigned char* labels_out, int label_format, unsigned char* overlay_out,
+                             const unsigned char* packed, const int* desc, const unsigned char* palette, int alpha,
+                             int B, int n, int h, int w, int H, int W, float scale_h, float scale_w, zh_stream_t stream);
 
 /* F.interpolate(x, size, bilinear) on `planes` NCHW planes (return_logits zutis.py:368-371; masks zutis.py:422-423);
  * optional mask_u8 = value > threshold. */

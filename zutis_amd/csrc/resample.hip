@@ -276,10 +276,11 @@ extern "C" int zh_cast_f32_f16(const float* x, const float* add, int add_rows, v
 // (bilinear index/weight: lin_weights, common.h)
 
 // ---- what the three upsample + arg-max kernels do with a pixel's label once it is known (compile-time epilogue).  Every lane of a wave
-//      that is still running calls it, `valid` = the lane owns the pixel `pix` (index into [B,H,W]): the scoring form talks to its wave.
+//      that is still running calls it, `valid` = the lane owns the pixel `pix` (index into [B,H,W]) of image `b`: the scoring form talks to its wave.
 struct UaStore {                        // zh_upsample_argmax: the int64 label map
+  static constexpr int kLdsWaves = 1;   // waves per SIMD asked of upsample_argmax_lds_kernel (1: the compiler's own choice, 6)
   long long* labels;
-  __device__ __forceinline__ void operator()(bool valid, long pix, int label) const {
+  __device__ __forceinline__ void operator()(bool valid, int b, long pix, int label) const {
     if (valid) labels[pix] = label;
   }
 };
@@ -293,11 +294,12 @@ struct UaStore {                        // zh_upsample_argmax: the int64 label m
 // ground truth of per-pixel noise costs what one atomic per pixel costs and no more.
 #define UA_MERGE_ROUNDS 8               // distinct keys a wave merges before its remaining lanes go to memory one by one
 struct UaScore {
+  static constexpr int kLdsWaves = 1;
   const unsigned char* gt;
   unsigned long long* hist;
   long long* labels;                    // may be NULL
   int n, rg16;
-  __device__ __forceinline__ void operator()(bool valid, long pix, int label) const {
+  __device__ __forceinline__ void operator()(bool valid, int b, long pix, int label) const {
     int key = -1;
     if (valid) {
       if (labels) labels[pix] = label;
@@ -316,6 +318,39 @@ struct UaScore {
       const unsigned long long same = __ballot(key == k);
       if (lane == leader) atomicAdd(&hist[k], (unsigned long long)__popcll(same));
       todo &= ~same;
+    }
+  }
+};
+
+// zh_upsample_argmax_bytes: the label as the bytes of the PNG it becomes (the two formats UaScore READS as ground truth), and / or the
+// colour picture blended over the decoded image where the batch's staging buffer already holds it (desc rows of 8 int32: offset / 16,
+// w, h, ...; HWC u8 at the file's own size = the output's).  One lane = one pixel; a wave's lanes own consecutive x, so its byte stores
+// land in one (u8) or three (RGB) consecutive runs of a row.  Integer arithmetic only, no LDS, no atomics.
+struct UaBytes {
+  static constexpr int kLdsWaves = 6;   // with the overlay's image read the allocator settles on 88 VGPRs (5 waves) unless told: 73, as UaStore
+  unsigned char* labels;                // may be NULL: u8 [B,H,W] (ZH_GT_U8) or [B,H,W,3] = (label & 255, label >> 8, 0) (ZH_GT_RG16)
+  unsigned char* overlay;               // may be NULL: u8 [B,H,W,3]
+  const unsigned char* packed;
+  const int* desc;
+  const unsigned char* palette;         // u8 [n,3]
+  long HW;
+  int rg16, alpha;
+  __device__ __forceinline__ void operator()(bool valid, int b, long pix, int label) const {
+    if (!valid) return;
+    if (labels) {
+      if (rg16) {
+        unsigned char* o = labels + 3 * pix;
+        o[0] = (unsigned char)(label & 255); o[1] = (unsigned char)(label >> 8); o[2] = 0;   // datasets/imagenet_s.py:93 read backwards
+      } else {
+        labels[pix] = (unsigned char)label;
+      }
+    }
+    if (overlay) {
+      const unsigned char* img = packed + (long)desc[8 * b] * 16 + 3 * (pix - b * HW);   // b is block-uniform in the tile kernels: a scalar load
+      const unsigned char* pal = palette + 3 * label;
+      unsigned char* o = overlay + 3 * pix;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c] = (unsigned char)(((int)img[c] * (256 - alpha) + (int)pal[c] * alpha + 128) >> 8);
     }
   }
 };
@@ -343,7 +378,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(const float* lo, c
     // torch.argmax: first maximal index; NaN is treated as maximal (propagates)
     if (c == 0 || v > best || (v != v && best == best)) { best = v; besti = c; }
   }
-  epi(true, idx, besti);               // lanes past the last pixel have left: they are in no ballot
+  epi(true, b, idx, besti);               // lanes past the last pixel have left: they are in no ballot
 }
 
 // LDS two-phase variant: a block owns a 32 x 32 output tile (each thread 4 pixels of one column) and walks the classes in
@@ -357,7 +392,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(const float* lo, c
 #define UA_CH 32
 #define UA_PX (UA_TH * UA_TW / 256)
 template <class Epi>
-__global__ __launch_bounds__(256) void upsample_argmax_lds_kernel(const float* lo, const Epi epi, int n, int h, int w,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Epi::kLdsWaves))) void upsample_argmax_lds_kernel(const float* lo, const Epi epi, int n, int h, int w,
                                                                   int H, int W, float scale_h, float scale_w, int tiles_x, int tiles_y,
                                                                   int wr_max, int wc_max) {
   extern __shared__ __attribute__((aligned(16))) float ua_lds[];
@@ -439,7 +474,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_lds_kernel(const float* l
 #pragma unroll
   for (int i = 0; i < UA_PX; ++i) {
     const int oy = oy0 + tyl + (256 / UA_TW) * i;
-    epi(oy < H && ox0 + txl < W, ((long)b * H + oy) * W + ox0 + txl, besti[i]);   // a partial tile's spare lanes: valid = false
+    epi(oy < H && ox0 + txl < W, b, ((long)b * H + oy) * W + ox0 + txl, besti[i]);   // a partial tile's spare lanes: valid = false
   }
 }
 
@@ -594,7 +629,7 @@ __global__ __launch_bounds__(256) void upsample_argmax_pk_kernel(const float* lo
 #pragma unroll
   for (int i = 0; i < UA_PX; ++i) {
     const int oy = oy0 + tyl + (256 / UA_TW) * i;
-    epi(oy < H && ox0 + txl < W, ((long)b * H + oy) * W + ox0 + txl, besti[i]);   // a partial tile's spare lanes: valid = false
+    epi(oy < H && ox0 + txl < W, b, ((long)b * H + oy) * W + ox0 + txl, besti[i]);   // a partial tile's spare lanes: valid = false
   }
 }
 
@@ -636,6 +671,22 @@ extern "C" int zh_upsample_argmax_score(const float* logits_lo, const unsigned c
                (gt_format == ZH_GT_U8 || gt_format == ZH_GT_RG16), "zh_upsample_argmax_score: bad arguments");
   ua_launch(UaScore{gt, (unsigned long long*)hist_accum, labels, n, gt_format == ZH_GT_RG16}, logits_lo, B, n, h, w, H, W, scale_h, scale_w, stream);
   ZH_CHECK_LAUNCH("zh_upsample_argmax_score");
+  return ZH_OK;
+}
+
+// ---- the same launch with the label leaving as file bytes (zutis.py:366-372 written as datasets/imagenet_s.py:93 reads it) and an
+//      optional colour overlay on the decoded image; see UaBytes.  packed / desc are trusted: the binding checks them.
+extern "C" int zh_upsample_argmax_bytes(const float* logits_lo, unsigned char* labels_out, int label_format, unsigned char* overlay_out,
+                                        const unsigned char* packed, const int* desc, const unsigned char* palette, int alpha,
+                                        int B, int n, int h, int w, int H, int W, float scale_h, float scale_w, hipStream_t stream) {
+  ZH_CHECK_ARG(logits_lo && (labels_out || overlay_out) && B > 0 && n > 0 && h > 0 && w > 0 && H > 0 && W > 0 &&
+               (label_format == ZH_GT_U8 || label_format == ZH_GT_RG16), "zh_upsample_argmax_bytes: bad arguments");
+  ZH_CHECK_ARG(n <= (label_format == ZH_GT_U8 ? 256 : 65536), "zh_upsample_argmax_bytes: n exceeds the label format (u8: 256, rg16: 65536)");
+  ZH_CHECK_ARG(!overlay_out || (packed && desc && palette && alpha >= 0 && alpha <= 256),
+               "zh_upsample_argmax_bytes: an overlay needs packed, desc, palette and alpha in 0..256");
+  ua_launch(UaBytes{labels_out, overlay_out, packed, desc, palette, (long)H * W, label_format == ZH_GT_RG16, alpha}, logits_lo, B, n, h, w, H, W,
+            scale_h, scale_w, stream);
+  ZH_CHECK_LAUNCH("zh_upsample_argmax_bytes");
   return ZH_OK;
 }
 

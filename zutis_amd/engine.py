@@ -337,6 +337,21 @@ class ZutisEngine(_EngineBase):
         H, Wd = (h, w) if size is None else (int(size[0]), int(size[1]))
         ops.upsample_argmax_score(lo, gt, hist, B, n, h, w, H, Wd, gt_format=gt_format, labels=labels)
 
+    def label_bytes(self, patch_tokens: torch.Tensor, text: torch.Tensor, size: Optional[Tuple[int, int]], label_format: str = "u8",
+                    labels_out: Optional[torch.Tensor] = None, palette: Optional[torch.Tensor] = None, packed: Optional[torch.Tensor] = None,
+                    desc: Optional[torch.Tensor] = None, alpha: int = 128, overlay_out: Optional[torch.Tensor] = None, desc_host=None):
+        """predict_semantic with the label map leaving as the bytes of its PNG (zutis.py:355-372; imagenet_s.py:93 read backwards) and,
+        with overlay_out, the palette colours blended over the decoded images in the same launch (ops.upsample_argmax_bytes).
+        labels_out None: allocated (u8 [B,H,W] / [B,H,W,3]) unless only the overlay is asked for.  Returns (labels_out, overlay_out)."""
+        lo = self.semantic_logits_lowres(patch_tokens, text)
+        B, n, h, w = lo.shape
+        H, Wd = (h, w) if size is None else (int(size[0]), int(size[1]))
+        if labels_out is None and overlay_out is None:
+            labels_out = torch.empty((B, H, Wd) if label_format == "u8" else (B, H, Wd, 3), dtype=torch.uint8, device=lo.device)
+        ops.upsample_argmax_bytes(lo, B, n, h, w, H, Wd, label_format=label_format, labels_out=labels_out, overlay_out=overlay_out, packed=packed,
+                                  desc=desc, palette=palette, alpha=alpha, desc_host=desc_host)
+        return labels_out, overlay_out
+
     # ------------------------------------------------------------------ predict (instance)
     def instance_candidates(self, mask_proposals_last: torch.Tensor, patch_tokens: torch.Tensor, text: torch.Tensor,
                             threshold: float = 0.5, temperature: float = 5.0, size: Optional[Tuple[int, int]] = None,

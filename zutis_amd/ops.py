@@ -423,6 +423,51 @@ def upsample_argmax_score(logits_lo, gt, hist, B, n, h, w, H, W, gt_format: str 
           lin_scale(h, H), lin_scale(w, W), _stream())
 
 
+def upsample_argmax_bytes(logits_lo, B, n, h, w, H, W, label_format: str = "u8", labels_out=None, overlay_out=None, packed=None, desc=None,
+                          palette=None, alpha: int = 128, desc_host=None):
+    """upsample_argmax with the label leaving as the bytes of the file it becomes (zutis.py:366-372; imagenet_s.py:93 read backwards):
+    labels_out None or u8 [B,H,W] ("u8": the byte is the label, n <= 256) / u8 [B,H,W,3] ("rg16": R = label & 255, G = label >> 8, B = 0,
+    n <= 65536); overlay_out None or u8 [B,H,W,3] = (img * (256 - alpha) + palette[label] * alpha + 128) >> 8, alpha an integer in 0..256,
+    palette u8 [n,3], img the decoded images of a loader's staging buffer (packed u8 [bytes], desc int32 [B,8]: offset / 16, w, h, ...)
+    at the output's own size.  Not both None.  The kernel trusts packed / desc: every row's (w, h) must be (W, H) and its image lie
+    inside packed, which is checked HERE, on desc_host (the loader's host copy of the rows) when given, else on a blocking read of desc."""
+    _chk(logits_lo, f32, "upsample_argmax_bytes logits")
+    if label_format not in GT_FORMATS:
+        raise _lib.ZutisHipError(f"upsample_argmax_bytes: label_format {label_format!r} is not one of {sorted(GT_FORMATS)}")
+    if tuple(logits_lo.shape) != (B, n, h, w):
+        raise _lib.ZutisHipError(f"upsample_argmax_bytes: logits {(B, n, h, w)} expected, got {tuple(logits_lo.shape)}")
+    if labels_out is None and overlay_out is None:
+        raise _lib.ZutisHipError("upsample_argmax_bytes: labels_out and overlay_out are both None")
+    limit = 256 if label_format == "u8" else 65536
+    if n > limit:
+        raise _lib.ZutisHipError(f"upsample_argmax_bytes: {n} classes do not fit the label format {label_format!r} (at most {limit})")
+    if labels_out is not None:
+        _chk(labels_out, torch.uint8, "upsample_argmax_bytes labels_out")
+        want = (B, H, W) if label_format == "u8" else (B, H, W, 3)
+        if tuple(labels_out.shape) != want:
+            raise _lib.ZutisHipError(f"upsample_argmax_bytes: labels_out {tuple(labels_out.shape)}, expected {want}")
+    if overlay_out is not None:
+        if packed is None or desc is None or palette is None:
+            raise _lib.ZutisHipError("upsample_argmax_bytes: an overlay needs packed, desc and palette")
+        _chk(overlay_out, torch.uint8, "upsample_argmax_bytes overlay_out"); _chk(packed, torch.uint8, "upsample_argmax_bytes packed")
+        _chk(desc, torch.int32, "upsample_argmax_bytes desc"); _chk(palette, torch.uint8, "upsample_argmax_bytes palette")
+        if tuple(overlay_out.shape) != (B, H, W, 3) or packed.dim() != 1 or tuple(desc.shape) != (B, 8) or tuple(palette.shape) != (n, 3):
+            raise _lib.ZutisHipError(f"upsample_argmax_bytes: overlay_out {(B, H, W, 3)}, packed [bytes], desc {(B, 8)}, palette {(n, 3)} expected, got "
+                                     f"{tuple(overlay_out.shape)}, {tuple(packed.shape)}, {tuple(desc.shape)}, {tuple(palette.shape)}")
+        if int(alpha) != alpha or not 0 <= int(alpha) <= 256:
+            raise _lib.ZutisHipError(f"upsample_argmax_bytes: alpha {alpha!r} is not an integer in 0..256")
+        rows = (desc if desc_host is None else desc_host).cpu().numpy().reshape(B, 8)
+        for b, (off, iw, ih) in enumerate(rows[:, :3].tolist()):
+            if (iw, ih) != (W, H):
+                raise _lib.ZutisHipError(f"upsample_argmax_bytes: descriptor row {b} holds a {iw} x {ih} image, the overlay is {W} x {H}")
+            if off < 0 or off * 16 + 3 * W * H > packed.numel():
+                raise _lib.ZutisHipError(f"upsample_argmax_bytes: descriptor row {b} places its image outside packed ({packed.numel()} bytes)")
+    else:
+        packed = desc = palette = None
+    _call("zh_upsample_argmax_bytes", _p(logits_lo), _p(labels_out), GT_FORMATS[label_format], _p(overlay_out), _p(packed), _p(desc), _p(palette),
+          int(alpha), B, n, h, w, H, W, lin_scale(h, H), lin_scale(w, W), _stream())
+
+
 def upsample_bilinear_nchw(x, planes, h, w, H, W, out=None, mask_u8=None, threshold=0.5, scale_h=None, scale_w=None):
     """scale_* default to in/out (size= form); pass 1/scale_factor for the scale_factor form with a cropped output."""
     sh = lin_scale(h, H) if scale_h is None else float(np.float32(scale_h))

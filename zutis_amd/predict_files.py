@@ -1,0 +1,332 @@
+"""Predictions from image files: the loop of coco20k_eval.py:241-268 (forward, instance predict, collect the COCO result dicts) and the
+common case next to it — run the segmenter over a list of images, get label maps on disk — over the drop-in ZUTIS.
+
+The label of a pixel is zutis.py:366-372 (arg-max over the bilinear up-sampling of the low-res logits, at the file's own size as
+trainer.py:322-325 sizes it); it leaves the arg-max kernel as the bytes of the PNG it becomes (zh_upsample_argmax_bytes): one byte per
+pixel ("u8"), or R = label & 255, G = label >> 8, B = 0 ("rg16": imagenet_s.py:93 read backwards) — the two formats evaluate_from_files
+reads as ground truth.  The same launch can blend a palette colour over the decoded image, which is already on the device as the bytes
+of the batch's staging buffer.  Per batch: decoding threads fill a pinned staging buffer one batch ahead (preprocess.PredictBatchLoader:
+batches of one file size), ONE host-to-device copy, ops.resize_normalize, the module's forward, the byte kernel, ONE device-to-host copy
+into one of two pinned output buffers; writer threads encode and write batch k's PNGs while batch k + 1 is on the device.
+"""
+from __future__ import annotations
+
+import json
+import os
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+from PIL import Image
+
+MAX_THREADS = 16
+LABEL_LIMIT = {"u8": 256, "rg16": 65536}
+LABEL_CHANNELS = {"u8": 1, "rg16": 3}
+
+
+def encode_labels(labels: np.ndarray, label_format: str) -> np.ndarray:
+    """The bytes zh_upsample_argmax_bytes writes for an integer label map [..., H, W]: u8 [..., H, W] ("u8") or u8 [..., H, W, 3] =
+    (label & 255, label >> 8, 0) ("rg16").  NumPy statement of the formats; not a product path."""
+    v = np.asarray(labels).astype(np.int64)
+    if v.size and (v.min() < 0 or v.max() >= LABEL_LIMIT[label_format]):
+        raise ValueError(f"encode_labels: labels outside [0, {LABEL_LIMIT[label_format]}) do not fit {label_format!r}")
+    if label_format == "u8":
+        return v.astype(np.uint8)
+    return np.stack([v & 255, v >> 8, np.zeros_like(v)], axis=-1).astype(np.uint8)
+
+
+def decode_labels(raw: np.ndarray, label_format: str) -> np.ndarray:
+    """int64 label map of the bytes of a label PNG, as EvalBatchLoader / zh_upsample_argmax_score read them (B is ignored)."""
+    raw = np.asarray(raw)
+    if label_format == "u8":
+        return raw.astype(np.int64)
+    return raw[..., 0].astype(np.int64) + 256 * raw[..., 1].astype(np.int64)
+
+
+def blend(image_u8: np.ndarray, colours_u8: np.ndarray, alpha: int) -> np.ndarray:
+    """The overlay of zh_upsample_argmax_bytes in NumPy integers: (image * (256 - alpha) + colours * alpha + 128) >> 8, alpha in 0..256."""
+    if int(alpha) != alpha or not 0 <= int(alpha) <= 256:
+        raise ValueError(f"blend: alpha {alpha!r} is not an integer in 0..256")
+    a = int(alpha)
+    return ((np.asarray(image_u8).astype(np.int64) * (256 - a) + np.asarray(colours_u8).astype(np.int64) * a + 128) >> 8).astype(np.uint8)
+
+
+def normalise_palette(palette, n: int) -> np.ndarray:
+    """u8 [n, 3] from a dict {label: (r, g, b)} (utils.get_palette) or an array-like [>= n, 3]: it must cover 0 .. n - 1 with integer
+    colours in 0 .. 255 (entries beyond n - 1 are dropped)."""
+    if isinstance(palette, dict):
+        missing = [i for i in range(n) if i not in palette]
+        if missing:
+            raise ValueError(f"palette: no colour for label {missing[0]} ({len(missing)} of {n} labels missing)")
+        a = np.asarray([tuple(palette[i]) for i in range(n)])
+    else:
+        a = np.asarray(palette)
+        if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < n:
+            raise ValueError(f"palette: [{n}, 3] expected (one colour per label), got {a.shape}")
+        a = a[:n]
+    if a.shape != (n, 3):
+        raise ValueError(f"palette: every colour must be (r, g, b), got {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        if not np.array_equal(a, np.round(a)):
+            raise ValueError("palette: colours must be integers in 0..255 (get_palette's float form is for matplotlib)")
+        a = a.astype(np.int64)
+    if a.size and (a.min() < 0 or a.max() > 255):
+        raise ValueError("palette: colours must lie in 0..255")
+    return np.ascontiguousarray(a.astype(np.uint8))
+
+
+def resolve_output_paths(p_images: Sequence[str], out_dir: Optional[str], out_paths: Optional[Sequence[str]], overlay: bool = False):
+    """(label paths, overlay paths or None): out_paths[i] as given, or {out_dir}/{stem of the image}.png; the overlay goes to
+    {stem of the label map}_overlay.png beside it.  Exactly one of out_dir / out_paths; two outputs on one path: ValueError."""
+    if (out_dir is None) == (out_paths is None):
+        raise ValueError("predict_from_files: give exactly one of out_dir and out_paths")
+    if out_paths is not None:
+        labels = [os.fspath(p) for p in out_paths]
+        if len(labels) != len(p_images):
+            raise ValueError("predict_from_files: one output path per image")
+    else:
+        labels = [os.path.join(os.fspath(out_dir), os.path.splitext(os.path.basename(os.fspath(p)))[0] + ".png") for p in p_images]
+    overlays = [os.path.splitext(p)[0] + "_overlay.png" for p in labels] if overlay else None
+    seen = {}
+    for i, p in enumerate(labels + (overlays or [])):
+        key = os.path.normpath(os.path.abspath(p))
+        if key in seen:
+            a, b = p_images[seen[key] % len(labels)], p_images[i % len(labels)]
+            raise ValueError(f"predict_from_files: {a} and {b} map to one output path, {p}")
+        seen[key] = i
+    return labels, overlays
+
+
+def predictions_json_form(predictions: Sequence[dict]) -> List[dict]:
+    """What trainer.py:393-398 dumps: every prediction without its "bbox", the RLE "counts" as a str; new dicts, the given ones stay whole."""
+    out = []
+    for p in predictions:
+        q = {k: v for k, v in p.items() if k != "bbox"}
+        seg = dict(q["segmentation"])
+        if isinstance(seg["counts"], (bytes, bytearray)):
+            seg["counts"] = bytes(seg["counts"]).decode("ascii")
+        seg["size"] = [int(s) for s in seg["size"]]
+        q["segmentation"] = seg
+        out.append(q)
+    return out
+
+
+def _jsonable(o):
+    if isinstance(o, np.generic):
+        return o.item()
+    if isinstance(o, np.ndarray):
+        return o.tolist()
+    raise TypeError(f"predictions_json: {type(o).__name__} is not JSON serialisable")
+
+
+def _validate(n: int, n_images: int, semantic: bool, instance: bool, label_format: str, palette, overlay: bool, alpha, image_ids, compress_level):
+    if not semantic and not instance:
+        raise ValueError("predict_from_files: semantic=False and instance=False leave nothing to predict")
+    if label_format not in LABEL_LIMIT:
+        raise ValueError(f"predict_from_files: label_format {label_format!r} is not one of {sorted(LABEL_LIMIT)}")
+    if n > 65536:
+        raise ValueError(f"predict_from_files: {n} categories do not fit a label file (at most 65536, \"rg16\")")
+    if semantic and n > LABEL_LIMIT[label_format]:
+        raise ValueError(f"predict_from_files: {n} categories do not fit one byte per pixel: use label_format=\"rg16\"")
+    if image_ids is not None and len(image_ids) != n_images:
+        raise ValueError("predict_from_files: one image id per image")
+    if overlay and not semantic:
+        raise ValueError("predict_from_files: overlay=True colours the semantic labels: it needs semantic=True")
+    if overlay and palette is None:
+        raise ValueError("predict_from_files: overlay=True needs a palette")
+    if int(alpha) != alpha or not 0 <= int(alpha) <= 256:
+        raise ValueError(f"predict_from_files: alpha {alpha!r} is not an integer in 0..256")
+    if int(compress_level) != compress_level or not 0 <= int(compress_level) <= 9:
+        raise ValueError(f"predict_from_files: compress_level {compress_level!r} is not an integer in 0..9")
+    return normalise_palette(palette, n) if (palette is not None and semantic) else None
+
+
+def thread_split(n_workers: int, writers_needed: bool):
+    """(decoders, writers): together min(n_workers, 16) threads, at least one of each kind that is needed (so two when n_workers is 1
+    and files are written); writers get half, PNG encoding costing about what decoding costs."""
+    total = max(1, min(int(n_workers), MAX_THREADS))
+    if not writers_needed:
+        return total, 0
+    total = max(2, total)
+    return total - total // 2, total // 2
+
+
+def _write_png(path: str, a: np.ndarray, mode: str, palette_bytes: Optional[bytes], compress_level: int):
+    im = Image.fromarray(a)                     # u8 [H, W] -> L, u8 [H, W, 3] -> RGB
+    if palette_bytes is not None:
+        im.putpalette(palette_bytes)            # L -> P: the bytes stay, the palette travels with them
+    if im.mode != mode:
+        raise ValueError(f"{path}: a mode {im.mode} image where {mode} was meant")
+    im.save(path, format="PNG", compress_level=compress_level)
+
+
+class _OutputRing:
+    """Two pinned output buffers.  A slot is handed out again only after the writers that read it are done (their exception, if any,
+    is raised there)."""
+
+    def __init__(self, pin: bool):
+        self.pin = pin
+        self.buffers = [torch.empty(0, dtype=torch.uint8), torch.empty(0, dtype=torch.uint8)]
+        self.writers = [[], []]
+
+    def drain(self, slot: int):
+        futures, self.writers[slot] = self.writers[slot], []
+        error = None
+        for f in futures:
+            try:
+                f.result()
+            except BaseException as e:          # every writer of the slot is waited for; the first failure is the one reported
+                error = error or e
+        if error is not None:
+            raise error
+
+    def take(self, slot: int, nbytes: int) -> torch.Tensor:
+        self.drain(slot)
+        if self.buffers[slot].numel() < nbytes:
+            self.buffers[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=self.pin)
+        return self.buffers[slot][:nbytes]
+
+
+@torch.no_grad()
+def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[str] = None, out_paths: Optional[Sequence[str]] = None,
+                       semantic: bool = True, label_format: str = "u8", palette=None, overlay: bool = False, alpha: int = 128,
+                       max_size: Optional[int] = None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), batch_size: int = 4,
+                       n_workers: int = 16, window: int = 512, compress_level: int = 1, instance: bool = False,
+                       image_ids: Optional[Sequence] = None, new_label_id_to_old_label_id: Optional[Dict[int, int]] = None,
+                       label_id_to_category: Optional[Dict[int, str]] = None, nms_type: Optional[str] = "hard",
+                       predictions_json: Optional[str] = None) -> dict:
+    """The segmenter over a list of image files: label PNGs (and overlays) on disk, and / or the instance predictions.
+
+    network: the drop-in ZUTIS (zutis_amd/dropin/networks/zutis.py) on a GPU; its text embeddings are the n categories.
+    semantic=True: the label map of image i (zutis.py:366-372 at the file's own (H, W)) is written to out_paths[i], or to
+    {out_dir}/{stem of the image}.png — give exactly one of the two; directories are created; two images on one output path is a
+    ValueError before any work.  label_format "u8" (n <= 256): a mode L PNG, the byte is the label; with a palette a mode P PNG that
+    carries it — the exact label map and the coloured picture in one file.  "rg16" (n <= 65536): a mode RGB PNG, R = label & 255,
+    G = label >> 8, B = 0 (imagenet_s.py:93 read backwards).  These are the files evaluate_from_files reads as ground truth.
+    palette: {label: (r, g, b)} as utils.get_palette returns, or an array [n, 3]; integers 0..255 covering 0 .. n - 1.
+    overlay=True (needs the palette): {stem}_overlay.png beside the label map, (image * (256 - alpha) + colour * alpha + 128) >> 8 per
+    channel, alpha an integer in 0..256.  An image the loader had to resize on the host (a source side more than 75 times the target)
+    is not on the device at file size: NotImplementedError naming the file.
+    max_size None: the image goes in at its own size; else the longer edge is capped with Pillow BILINEAR (imagenet_s.py:71-76); the
+    prediction is made at the file's size either way.  Batches: up to batch_size images of one file size out of a window of `window`
+    paths, grouped as evaluate_from_files groups them.  Decoding and writing threads together: min(n_workers, 16) (two at the least).
+    instance=True: predict(mask_type="instance", size=(H, W), ...) per batch as coco20k_eval.py:258-265 calls it; image_ids: one per
+    image (None: 0, predict's default).  predictions_json: a path that receives what trainer.py:393-398 writes — the dicts without
+    "bbox", RLE counts as str, in input-path order.
+    Returns {"label_paths": [...] | None, "overlay_paths": [...] | None, "instance_predictions": the dicts predict gave (with "bbox"),
+    in input-path order, "n_images": int}.
+    A missing or unreadable image (FileNotFoundError / OSError / ValueError) and a directory or file that cannot be written (OSError)
+    are raised here; no decoding or writing thread outlives the call and the device stays usable."""
+    from . import ops, preprocess
+    p_images = [os.fspath(p) for p in p_images]
+    if not (hasattr(network, "_get_engine") and hasattr(network, "predict") and hasattr(network, "text_embeddings")):
+        raise TypeError("predict_from_files needs the MI355X drop-in ZUTIS (networks/zutis.py of the overlay): there is no torch / CPU fallback")
+    n = int(network.text_embeddings.shape[0])
+    pal = _validate(n, len(p_images), semantic, instance, label_format, palette, overlay, alpha, image_ids, compress_level)
+    label_paths = overlay_paths = None
+    if semantic:
+        label_paths, overlay_paths = resolve_output_paths(p_images, out_dir, out_paths, overlay)
+        for d in sorted({os.path.dirname(p) or "." for p in label_paths}):
+            os.makedirs(d, exist_ok=True)
+    elif out_dir is not None and out_paths is not None:
+        raise ValueError("predict_from_files: give exactly one of out_dir and out_paths")
+    per_image: List[List[dict]] = [[] for _ in p_images]
+    if p_images:
+        eng = network._get_engine()
+        dev = eng._device()
+        n_decode, n_write = thread_split(n_workers, semantic)
+        ch = LABEL_CHANNELS[label_format]
+        mode = "RGB" if label_format == "rg16" else ("P" if pal is not None else "L")
+        pal_bytes = pal.tobytes() if mode == "P" else None
+        lut = torch.from_numpy(preprocess.normalise_table(mean, std)).to(dev)
+        pal_dev = torch.from_numpy(pal).to(dev) if (overlay and pal is not None) else None
+        loader = preprocess.PredictBatchLoader(p_images, max_size, batch_size, n_decode, window=window)
+        ring = _OutputRing(loader.pin)
+        copied = torch.cuda.Event()
+        fetched = [torch.cuda.Event(), torch.cuda.Event()]
+        writers = ThreadPoolExecutor(max_workers=n_write, thread_name_prefix="zutis-write") if n_write else None
+        batches = iter(loader)
+        waiting = None                                                                     # (slot, host bytes, indices, (H, W)) of the batch whose copy back is in flight
+
+        def hand_to_writers(slot, host, indices, H, W):
+            fetched[slot].synchronize()                                                    # the bytes are in the pinned buffer
+            a = host.numpy()
+            B = len(indices)
+            lab = a[:B * H * W * ch].reshape((B, H, W) if ch == 1 else (B, H, W, ch))
+            ovl = a[B * H * W * ch:].reshape(B, H, W, 3) if overlay else None
+            for b, i in enumerate(indices):
+                ring.writers[slot].append(writers.submit(_write_png, label_paths[i], lab[b], mode, pal_bytes, int(compress_level)))
+                if overlay:
+                    ring.writers[slot].append(writers.submit(_write_png, overlay_paths[i], ovl[b], "RGB", None, int(compress_level)))
+
+        with torch.cuda.device(dev):
+            try:
+                for k, batch in enumerate(batches):
+                    B, (H, W), (oh, ow) = len(batch.paths), batch.size_hw, batch.out_hw
+                    if overlay and batch.n_host:
+                        raise NotImplementedError(f"predict_from_files: {batch.host_paths[0]} was resized on the host (a side more than 75 times its "
+                                                  f"target): its decoded image is not on the device at file size, no overlay can be made")
+                    staged = batch.staging.to(dev, non_blocking=True)                      # descriptors + image bytes: one H2D
+                    copied.record()
+                    packed, desc = preprocess.split_staging(staged, B)
+                    x = ops.resize_normalize(packed, desc, oh, ow, lut, filter="bilinear", kmax=batch.kmax)
+                    out = network(x)                                                       # the module's forward: its hipGraph replay applies
+                    if semantic:
+                        slot = k % 2
+                        nl = B * H * W * ch
+                        host = ring.take(slot, nl + (3 * B * H * W if overlay else 0))     # waits for the writers of batch k - 2
+                        dev_out = torch.empty((host.numel(),), dtype=torch.uint8, device=dev)
+                        eng.label_bytes(out["patch_tokens"], network.text_embeddings, (H, W), label_format=label_format,
+                                        labels_out=dev_out[:nl].view((B, H, W) if ch == 1 else (B, H, W, ch)), palette=pal_dev,
+                                        packed=packed if overlay else None, desc=desc if overlay else None, alpha=int(alpha),
+                                        overlay_out=dev_out[nl:].view(B, H, W, 3) if overlay else None, desc_host=batch.desc)
+                        host.copy_(dev_out, non_blocking=True)                             # labels + overlay: one D2H
+                        fetched[slot].record()
+                        if waiting is not None:
+                            hand_to_writers(*waiting)                                      # batch k - 1 is encoded while batch k is on the device
+                        waiting = (slot, host, list(batch.indices), H, W)
+                    if instance:                                                           # coco20k_eval.py:258-265, trainer.py:337-345
+                        for p in network.predict(dict_outputs=out, mask_type="instance", size=(H, W), image_ids=list(batch.indices),
+                                                 label_id_to_category=label_id_to_category,
+                                                 new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type):
+                            i = p["image_id"]
+                            p["image_id"] = image_ids[i] if image_ids is not None else 0
+                            per_image[i].append(p)
+                    copied.synchronize()                                                   # the loader may now decode into this staging buffer again
+                if waiting is not None:
+                    hand_to_writers(*waiting)
+                    waiting = None
+                ring.drain(0)
+                ring.drain(1)
+                eng.check_finite()                                                         # the forwards' status word: one read for the whole run
+            finally:
+                torch.cuda.synchronize(dev)                                                # nothing in flight on the pinned buffers when they go
+                batches.close()                                                            # a failure outside the loader: its threads end here
+                if writers is not None:
+                    writers.shutdown(wait=True, cancel_futures=True)
+    predictions = [p for ps in per_image for p in ps]
+    if predictions_json is not None:
+        d = os.path.dirname(os.fspath(predictions_json))
+        if d:
+            os.makedirs(d, exist_ok=True)
+        with open(predictions_json, "w") as f:
+            json.dump(predictions_json_form(predictions), f, default=_jsonable)
+    return {"label_paths": label_paths, "overlay_paths": overlay_paths, "instance_predictions": predictions, "n_images": len(p_images)}
+
+
+def predict_files_of(dataset):
+    """(p_images, max_size, image_ids) for predict_from_files from one of the reference's dataset objects — the image half of
+    evaluate.eval_files_of, so a split without ground truth (ImageNet-S test) is served:
+
+      imagenet-s50 / -s300 / -s919 (datasets/imagenet_s.py:63-99): p_images as globbed, max_size = its max_size (1024), no image ids;
+      coco2017, coco20k     (datasets/coco2017.py:121-149, coco20k.py:165-202): get_image_path(image_id) over image_ids, None, image_ids.
+
+    TypeError for anything else."""
+    name = getattr(dataset, "name", None)
+    if isinstance(name, str) and name.startswith("imagenet-s"):
+        return list(dataset.p_images), int(dataset.max_size), None
+    if name in ("coco2017", "coco20k"):
+        ids = list(dataset.image_ids)
+        return [dataset.get_image_path(i) for i in ids], None, ids
+    raise TypeError(f"predict_files_of: no path rules for the dataset {name!r} ({type(dataset).__name__})")

@@ -13,6 +13,7 @@ is also what crosses PCIe (3 bytes per source pixel instead of 12 per output pix
                         gathered from a bounded window of paths ahead, so that the batched SelfMask + solver run batched
 
   EvalBatchLoader       ShapeBucketLoader for evaluation: every image travels with its ground-truth PNG (one staging buffer, one copy)
+  PredictBatchLoader    EvalBatchLoader's batches without the ground truth: images of one file size, for predictions at that size
 
 Threads, not processes: no child ever holds the device open, nothing is pickled, a worker's exception is raised by the caller.
 """
@@ -439,3 +440,41 @@ class EvalBatchLoader(ShapeBucketLoader):
         gt_np = gt.numpy()
         futures += [pool.submit(self._decode_gt, p, gt_np[b]) for b, p in enumerate(gts)]
         return EvalBatch(chunk, gts, idx, (h, w), (nh, nw), staging, packed.numel(), gt, kmax, n_host), futures
+
+
+PredictBatch = collections.namedtuple("PredictBatch", "paths indices size_hw out_hw staging packed desc kmax n_host host_paths")
+PredictBatch.__doc__ = """One decoded batch of images of ONE file size that resize to ONE shape.  paths / indices: the files and their
+positions in the loader's list; size_hw: the (H, W) every file of the batch has; out_hw: what the images resize to; staging / packed /
+desc / kmax / n_host as in Batch; host_paths: the files that were resized on the host (their packed bytes are NOT at file size)."""
+
+
+class PredictBatchLoader(ShapeBucketLoader):
+    """EvalBatchLoader without ground truth: the prediction of image i is made at the file's own size (trainer.py:322-325), so a batch
+    shares the file size as well as the resized shape.  It groups by the very key evaluation groups by, eval_bucket_key(w, h, w, h,
+    max_size): for one path list, batch_size and window its batches are EvalBatchLoader's.  max_size as there."""
+
+    def __init__(self, paths: Sequence[str], max_size, batch_size: int, n_workers: int, window: int = 512, pin=None):
+        super().__init__(paths, max_size, batch_size, n_workers, window=window, filter="bilinear", pin=pin)
+        self.max_size = max_size
+
+    def _groups(self, pool: ThreadPoolExecutor):
+        sizes = {}
+
+        def keys():
+            for start in range(0, len(self.paths), self.window):
+                block = self.paths[start:start + self.window]
+                for i, wh in enumerate(pool.map(self._size, block), start):
+                    sizes[i] = wh
+                for i in range(start, start + len(block)):
+                    yield eval_bucket_key(*sizes[i], *sizes[i], self.max_size)
+
+        for idx in _buckets(keys(), self.batch_size, self.window):
+            wh = [sizes.pop(i) for i in idx]
+            yield idx, wh, longer_edge_size(*wh[0], self.max_size)
+
+    def _start(self, pool: ThreadPoolExecutor, slot: int, group):
+        idx, sizes, (nw, nh) = group
+        (w, h), chunk = sizes[0], [self.paths[i] for i in idx]
+        staging, packed, desc, kmax, n_host, futures = self._pack(pool, slot, chunk, sizes, [((nw, nh), (0, 0))] * len(idx), (nw, nh))
+        host = [p for p in chunk if not _taps_ok(w, h, nw, nh, self.filter)] if n_host else []
+        return PredictBatch(chunk, idx, (h, w), (nh, nw), staging, packed, desc, kmax, n_host, host), futures
