@@ -353,7 +353,8 @@ int zh_bgrid_coords(const unsigned char* rgb, int H, int W, double sigma_spatial
  * constants of bilateral_solver_output (:162-175: confidence 0.999, lam 256, A_diag_min 1e-5, cg_tol 1e-5, maxiter 25)
  * passed by the caller.  rgb u8 [H,W,3]; target u8 [H,W] or f64 [H,W] (exactly one non-NULL); out_soft f64 [H,W];
  * stats int32 [2] = {nvertices, cg iterations} (device, may be NULL); n_out/m_out f64 [H*W] debug copies of the
- * bistochastisation vectors (may be NULL). */
+ * bistochastisation vectors (may be NULL).  The device lattice is dense; it matches the reference's, whose vertex hash is
+ * sum c_d 255^d, only while every lattice coordinate stays below 255 (sigmas of about 1 or more, at most 254 spatial cells a side). */
 size_t zh_bilateral_workspace_size(int H, int W, double sigma_spatial, double sigma_luma, double sigma_chroma);
 int zh_bilateral_solve(const unsigned char* rgb, const unsigned char* target_u8, const double* target_f64, int H, int W,
                        double sigma_spatial, double sigma_luma, double sigma_chroma, double confidence, double lam,

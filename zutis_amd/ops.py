@@ -694,43 +694,70 @@ def synth_compose(rgbm, blurred, desc, samples, work, lut, ignore_index: int):
 
 
 # ---------------------------------------------------------------------------------------- bilateral solver (float64)
-def denormalize_u8(x, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
-    """utils/utils.py:261-273 on device: x f32 [3,H,W] -> rgb u8 [H,W,3]."""
+def _caller_buffer(t, dtype, shape, name: str):
+    """A caller's output buffer viewed as `shape`: contiguous, of `dtype`, with exactly as many elements."""
+    _chk(t, dtype, name)
+    n = 1
+    for d in shape:
+        n *= int(d)
+    if t.numel() != n:
+        raise _lib.ZutisHipError(f"{name}: holds {t.numel()} elements, {n} needed for {tuple(shape)}")
+    return t.view(shape)
+
+
+def denormalize_u8(x, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), out=None):
+    """utils/utils.py:261-273 on device: x f32 [3,H,W] -> rgb u8 [H,W,3] (out: the caller's buffer of H*W*3 bytes)."""
     import ctypes as C
     _chk(x, f32, "denormalize x")
     _, H, W = x.shape
-    out = torch.empty((H, W, 3), dtype=torch.uint8, device=x.device)
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=x.device) if out is None else _caller_buffer(out, torch.uint8, (H, W, 3), "denormalize out")
     m = (C.c_float * 3)(*[float(np.float32(v)) for v in mean])
     s = (C.c_float * 3)(*[float(np.float32(v)) for v in std])
     _call("zh_denormalize_u8", _p(x), _p(out), H, W, m, s, _stream())
     return out
 
 
-def bgrid_coords(rgb_u8, sigma_spatial=16, sigma_luma=16, sigma_chroma=8):
+def bgrid_coords(rgb_u8, sigma_spatial=16, sigma_luma=16, sigma_chroma=8, out=None):
     H, W, _ = rgb_u8.shape
-    out = torch.empty((H * W, 5), dtype=torch.int32, device=rgb_u8.device)
+    _chk(rgb_u8, torch.uint8, "rgb")
+    out = torch.empty((H * W, 5), dtype=torch.int32, device=rgb_u8.device) if out is None else _caller_buffer(out, torch.int32, (H * W, 5), "bgrid_coords out")
     _call("zh_bgrid_coords", _p(rgb_u8), H, W, float(sigma_spatial), float(sigma_luma), float(sigma_chroma), _p(out), _stream())
     return out
 
 
+def bilateral_workspace_size(H, W, sigma_spatial=16, sigma_luma=16, sigma_chroma=8) -> int:
+    """Bytes of workspace ONE H x W image needs (a batch needs B times that)."""
+    return int(_lib.load(raw=True).zh_bilateral_workspace_size(H, W, float(sigma_spatial), float(sigma_luma), float(sigma_chroma)))
+
+
 def bilateral_solve(rgb_u8, target, sigma_spatial=16, sigma_luma=16, sigma_chroma=8, confidence=0.999, lam=256.0,
-                    a_diag_min=1e-5, cg_tol=1e-5, cg_maxiter=25, debug=False):
+                    a_diag_min=1e-5, cg_tol=1e-5, cg_maxiter=25, debug=False, workspace=None, out=None, stats=None):
     """rgb u8 [H,W,3] + target u8|f64 [H,W] (device) -> soft f64 [H,W] (device), stats int32 [2] (device)
     [, n, m f64 [H*W] when debug].  A batch ([B,H,W,3] + [B,H,W]) returns [B,H,W], [B,2] (, [B,H*W] x 2): one sequence of
-    launches for all B images."""
+    launches for all B images.
+    Caller buffers (optional; each contiguous, of the dtype and element count of what it replaces, and returned viewed at that
+    shape): `workspace` (any dtype, >= B * bilateral_workspace_size(...) bytes; whatever it holds is overwritten), `out` f64,
+    `stats` int32, and `debug=(n, m)`, a pair of f64 buffers of B*H*W elements of which the first V of each image's row are written."""
     batched = rgb_u8.dim() == 4
     r4 = rgb_u8 if batched else rgb_u8[None]
     t3 = target if batched else target[None]
     B, H, W, _ = r4.shape
     _chk(r4, torch.uint8, "rgb")
     assert t3.shape == (B, H, W) and t3.is_contiguous() and t3.dtype in (torch.uint8, torch.float64)
-    need = B * _lib.load(raw=True).zh_bilateral_workspace_size(H, W, float(sigma_spatial), float(sigma_luma), float(sigma_chroma))
+    need = B * bilateral_workspace_size(H, W, sigma_spatial, sigma_luma, sigma_chroma)
     dev = r4.device
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    out = torch.empty((B, H, W), dtype=torch.float64, device=dev)
-    stats = torch.zeros((B, 2), dtype=torch.int32, device=dev)
-    n = torch.zeros((B, H * W), dtype=torch.float64, device=dev) if debug else None
-    m = torch.zeros((B, H * W), dtype=torch.float64, device=dev) if debug else None
+    ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=dev)
+    if not ws.is_contiguous() or _nbytes(ws) < need:
+        raise _lib.ZutisHipError(f"bilateral_solve: workspace holds {_nbytes(ws)} bytes (contiguous={ws.is_contiguous()}), {need} needed")
+    out = torch.empty((B, H, W), dtype=torch.float64, device=dev) if out is None else _caller_buffer(out, torch.float64, (B, H, W), "bilateral_solve out")
+    stats = torch.zeros((B, 2), dtype=torch.int32, device=dev) if stats is None else _caller_buffer(stats, torch.int32, (B, 2), "bilateral_solve stats")
+    if debug is True:
+        n = torch.zeros((B, H * W), dtype=torch.float64, device=dev)
+        m = torch.zeros((B, H * W), dtype=torch.float64, device=dev)
+    elif debug:
+        n, m = (_caller_buffer(d, torch.float64, (B, H * W), "bilateral_solve debug") for d in debug)
+    else:
+        n = m = None
     t8 = t3 if t3.dtype == torch.uint8 else None
     t64 = t3 if t3.dtype == torch.float64 else None
     _call("zh_bilateral_solve_batch", _p(r4), _p(t8), _p(t64), B, H, W, float(sigma_spatial), float(sigma_luma), float(sigma_chroma),
@@ -742,10 +769,10 @@ def bilateral_solve(rgb_u8, target, sigma_spatial=16, sigma_luma=16, sigma_chrom
     return (out, stats, n, m) if debug else (out, stats)
 
 
-def threshold_f64_u8(x, threshold=0.5):
-    """x f64 (device, contiguous) -> u8 {0,1} of the same shape: x > threshold."""
+def threshold_f64_u8(x, threshold=0.5, out=None):
+    """x f64 (device, contiguous) -> u8 {0,1} of the same shape: x > threshold (out: the caller's buffer of x.numel() bytes)."""
     _chk(x, torch.float64, "threshold x")
-    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if out is None else _caller_buffer(out, torch.uint8, tuple(x.shape), "threshold out")
     _call("zh_threshold_f64_u8", _p(x), float(threshold), _p(out), x.numel(), _stream())
     return out
 
