@@ -13,7 +13,8 @@ stay fp32.  Every mode returns unit-norm fp32 embeddings.  Weights come from `cl
 `state_dict=`.
 Pre-processing (bicubic resize of the shorter side, centre crop, CLIP mean/std; SimpleDataset :90-116): `n_workers` threads (at most
 16; the reference's DataLoader workers, :64-65) open and decode the files one batch ahead (zutis_amd.preprocess.BatchLoader), the decoded
-bytes cross to the device in one copy per batch, and one kernel (ops.resize_crop_normalize) resizes, crops and normalises them — the
+bytes cross to the device in one copy per batch (zutis_amd.preprocess.device_batches), and one kernel (ops.resize_crop_normalize)
+resizes, crops and normalises them — the
 very bytes of Pillow's resampler and the very fp32 values of `_preprocess`, which stays here as the host statement of the same
 transform (the tests' reference), so the embeddings are bit for bit those of the host path.
 """
@@ -77,14 +78,18 @@ def extract_image_embeddings(
     out: Dict[str, torch.Tensor] = {}
     lut = torch.from_numpy(preprocess.normalise_table(_MEAN, _STD)).to(device)
     loader = preprocess.BatchLoader(p_images, n_px, batch_size, n_workers, resize_crop_box)
-    for k, batch in enumerate(loader):
-        i, chunk = k * batch_size, batch.paths
-        packed, desc = preprocess.split_staging(batch.staging.to(device, non_blocking=True), len(chunk))   # one H2D: descriptors + bytes
-        x = ops.resize_crop_normalize(packed, desc, n_px, lut, kmax=batch.kmax)
-        emb = enc.encode_image(x).cpu()                                 # L2-normalised, fp32 (reference :72-76); the copy back is the
-                                                                        # synchronisation after which the loader may reuse the staging buffer
-        for p, e in zip(chunk, emb):
-            out[os.path.basename(p)] = e.clone()
-        if fp is not None and ((i // batch_size) % max(1, (len(p_images) // batch_size) // 20) == 0 or i + batch_size >= len(p_images)):
-            pkl.dump(out, open(fp, "wb"))                               # periodic checkpoint (reference :80-85)
+
+    def transform(batch, staged):
+        packed, desc = preprocess.split_staging(staged, len(batch.paths))
+        return (packed, desc), ops.resize_crop_normalize(packed, desc, n_px, lut, kmax=batch.kmax)
+
+    with preprocess.device_batches(loader, device, transform) as steps:
+        for k, (batch, _, x) in enumerate(steps):
+            i, chunk = k * batch_size, batch.paths
+            emb = enc.encode_image(x).cpu()                                 # L2-normalised, fp32 (reference :72-76); the copy back completes
+                                                                            # behind the batch's upload, so the loop's event wait never blocks
+            for p, e in zip(chunk, emb):
+                out[os.path.basename(p)] = e.clone()
+            if fp is not None and ((i // batch_size) % max(1, (len(p_images) // batch_size) // 20) == 0 or i + batch_size >= len(p_images)):
+                pkl.dump(out, open(fp, "wb"))                               # periodic checkpoint (reference :80-85)
     return out

@@ -3,10 +3,11 @@ validation dataset's work split between decoding threads and the device, and the
 
 The reference's loop, per image: DataLoader workers decode, run to_tensor + normalize and pickle an fp32 tensor to the parent; the
 parent uploads it, forwards, pulls an int64 label map to the host (predict "semantic"), and RunningScore.update converts ground truth
-and prediction to int64 and uploads both again.  Here: threads decode the image and its ground-truth PNG one batch ahead into pinned
-staging (preprocess.EvalBatchLoader: batches of one file size); per batch ONE host-to-device copy of bytes (3 per image pixel, 1 or 3
-per ground-truth pixel), ops.resize_normalize (Pillow BILINEAR + to_tensor + normalize, bit for bit; the identity when the image is
-not resized), the module's own forward, and zh_upsample_argmax_score, which adds every pixel's (gt, label) pair to one device
+and prediction to int64 and uploads both again.  Here the file pipeline of preprocess.py: threads decode the image and its
+ground-truth PNG one batch ahead into pinned staging (EvalBatchLoader: batches of one file size); per batch (device_batches) ONE
+host-to-device copy of bytes (3 per image pixel, 1 or 3 per ground-truth pixel) and ops.resize_normalize (Pillow BILINEAR + to_tensor
++ normalize, bit for bit; the identity when the image is not resized); then the module's own forward, and
+zh_upsample_argmax_score, which adds every pixel's (gt, label) pair to one device
 histogram while the label is in a register — no label map, no copy back.  The histogram crosses to the host once, at the end.
 """
 from __future__ import annotations
@@ -17,9 +18,22 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import ops
+from . import preprocess
+from .preprocess import MAX_THREADS
 
-MAX_THREADS = 16
+
+def _require_dropin(network, who: str):
+    if not (hasattr(network, "_get_engine") and hasattr(network, "predict") and hasattr(network, "text_embeddings")):
+        raise TypeError(f"{who} needs the MI355X drop-in ZUTIS (networks/zutis.py of the overlay): there is no torch / CPU fallback")
+
+
+def collect_instance_predictions(network, out: dict, batch, image_ids: Optional[Sequence], per_image: List[List[dict]], **predict_args):
+    """predict(mask_type="instance") of one batch at the files' size (trainer.py:337-345, coco20k_eval.py:258-265): predict numbers the
+    images by their positions in the path list, which file each dict under per_image and are then replaced by image_ids' entry (None: 0)."""
+    for p in network.predict(dict_outputs=out, mask_type="instance", size=batch.size_hw, image_ids=list(batch.indices), **predict_args):
+        i = p["image_id"]
+        p["image_id"] = image_ids[i] if image_ids is not None else 0
+        per_image[i].append(p)
 
 
 def confusion_scores(hist: np.ndarray):
@@ -57,14 +71,12 @@ def evaluate_from_files(network, p_images: Sequence[str], p_gts: Sequence[str], 
     prediction dicts in input-path order ([] without instance), "labels": {index: int64 [H, W] label map} with return_labels, else None}.
     A missing or unreadable file and a ground truth of the wrong mode or size are raised here (FileNotFoundError / OSError /
     ValueError); no decoding thread outlives the call and the device stays usable."""
-    from . import preprocess
     p_images, p_gts = list(p_images), list(p_gts)
     if len(p_images) != len(p_gts):
         raise ValueError("evaluate_from_files: one ground-truth file per image")
     if image_ids is not None and len(image_ids) != len(p_images):
         raise ValueError("evaluate_from_files: one image id per image")
-    if not (hasattr(network, "_get_engine") and hasattr(network, "predict") and hasattr(network, "text_embeddings")):
-        raise TypeError("evaluate_from_files needs the MI355X drop-in ZUTIS (networks/zutis.py of the overlay): there is no torch / CPU fallback")
+    _require_dropin(network, "evaluate_from_files")
     n = int(n_categories)
     if network.text_embeddings.shape[0] != n:
         raise ValueError(f"evaluate_from_files: the network holds {network.text_embeddings.shape[0]} text embeddings, n_categories is {n}")
@@ -77,33 +89,19 @@ def evaluate_from_files(network, p_images: Sequence[str], p_gts: Sequence[str], 
         lut = torch.from_numpy(preprocess.normalise_table(mean, std)).to(dev)
         loader = preprocess.EvalBatchLoader(p_images, p_gts, max_size, batch_size, max(1, min(int(n_workers), MAX_THREADS)), window=window,
                                             gt_format=gt_format)
-        copied = torch.cuda.Event()
-        batches = iter(loader)
-        with torch.cuda.device(dev):
-            try:
-                for batch in batches:
-                    B, (H, W), (oh, ow) = len(batch.paths), batch.size_hw, batch.out_hw
-                    staged = batch.staging.to(dev, non_blocking=True)                  # descriptors + image bytes + ground truth: one H2D
-                    copied.record()
-                    packed, desc, gt = preprocess.split_eval_staging(staged, B, batch.packed_bytes, tuple(batch.gt.shape))
-                    x = ops.resize_normalize(packed, desc, oh, ow, lut, filter="bilinear", kmax=batch.kmax)
-                    out = network(x)                                                   # the module's forward: its hipGraph replay applies
-                    labels = torch.empty((B, H, W), dtype=torch.int64, device=dev) if return_labels else None
-                    eng.score_semantic(out["patch_tokens"], network.text_embeddings, gt, hist, gt_format=gt_format, size=(H, W), labels=labels)
-                    if instance:                                                       # trainer.py:337-345
-                        for p in network.predict(dict_outputs=out, mask_type="instance", size=(H, W), image_ids=list(batch.indices),
-                                                 new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type):
-                            i = p["image_id"]
-                            p["image_id"] = image_ids[i] if image_ids is not None else 0
-                            per_image[i].append(p)
-                    if return_labels:
-                        for i, m in zip(batch.indices, labels.cpu().numpy()):
-                            labels_out[i] = m
-                    copied.synchronize()                                               # the loader may now decode into this staging buffer again
-                eng.check_finite()                                                     # the forwards' status word: one read for the whole run
-            finally:
-                torch.cuda.synchronize(dev)                                            # nothing in flight on the pinned buffers when they go
-                batches.close()                                                        # a failure outside the loader: its threads end here
+        with preprocess.device_batches(loader, dev, preprocess.resize_normalize_of(lut)) as steps:
+            for batch, (_, _, gt), x in steps:
+                B, (H, W) = len(batch.paths), batch.size_hw
+                out = network(x)                                                       # the module's forward: its hipGraph replay applies
+                labels = torch.empty((B, H, W), dtype=torch.int64, device=dev) if return_labels else None
+                eng.score_semantic(out["patch_tokens"], network.text_embeddings, gt, hist, gt_format=gt_format, size=(H, W), labels=labels)
+                if instance:
+                    collect_instance_predictions(network, out, batch, image_ids, per_image,
+                                                 new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type)
+                if return_labels:
+                    for i, m in zip(batch.indices, labels.cpu().numpy()):
+                        labels_out[i] = m
+            eng.check_finite()                                                         # the forwards' status word: one read for the whole run
     cm = hist.cpu().numpy().reshape(n, n).astype(np.float64)                           # the one crossing of the histogram
     scores, cls_iu = confusion_scores(cm)
     return {"scores": scores, "cls_iu": cls_iu, "confusion_matrix": cm, "instance_predictions": [p for ps in per_image for p in ps],

@@ -5,22 +5,24 @@ The label of a pixel is zutis.py:366-372 (arg-max over the bilinear up-sampling 
 trainer.py:322-325 sizes it); it leaves the arg-max kernel as the bytes of the PNG it becomes (zh_upsample_argmax_bytes): one byte per
 pixel ("u8"), or R = label & 255, G = label >> 8, B = 0 ("rg16": imagenet_s.py:93 read backwards) — the two formats evaluate_from_files
 reads as ground truth.  The same launch can blend a palette colour over the decoded image, which is already on the device as the bytes
-of the batch's staging buffer.  Per batch: decoding threads fill a pinned staging buffer one batch ahead (preprocess.PredictBatchLoader:
-batches of one file size), ONE host-to-device copy, ops.resize_normalize, the module's forward, the byte kernel, ONE device-to-host copy
-into one of two pinned output buffers; writer threads encode and write batch k's PNGs while batch k + 1 is on the device.
+of the batch's staging buffer.  The file pipeline of preprocess.py: decoding threads fill a pinned staging buffer one batch ahead
+(PredictBatchLoader: batches of one file size); per batch (device_batches) ONE host-to-device copy and ops.resize_normalize; then the
+module's forward, the byte kernel, ONE device-to-host copy into one of the two pinned output buffers of a WriterRing, whose threads
+encode and write batch k's PNGs while batch k + 1 is on the device.
 """
 from __future__ import annotations
 
 import json
 import os
-from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 from PIL import Image
 
-MAX_THREADS = 16
+from . import preprocess
+from .evaluate import _require_dropin, collect_instance_predictions
+from .preprocess import MAX_THREADS
 LABEL_LIMIT = {"u8": 256, "rg16": 65536}
 LABEL_CHANNELS = {"u8": 1, "rg16": 3}
 
@@ -145,11 +147,9 @@ def _validate(n: int, n_images: int, semantic: bool, instance: bool, label_forma
 def thread_split(n_workers: int, writers_needed: bool):
     """(decoders, writers): together min(n_workers, 16) threads, at least one of each kind that is needed (so two when n_workers is 1
     and files are written); writers get half, PNG encoding costing about what decoding costs."""
-    total = max(1, min(int(n_workers), MAX_THREADS))
     if not writers_needed:
-        return total, 0
-    total = max(2, total)
-    return total - total // 2, total // 2
+        return max(1, min(int(n_workers), MAX_THREADS)), 0
+    return preprocess.thread_split(n_workers, 0.5)
 
 
 def _write_png(path: str, a: np.ndarray, mode: str, palette_bytes: Optional[bytes], compress_level: int):
@@ -159,33 +159,6 @@ def _write_png(path: str, a: np.ndarray, mode: str, palette_bytes: Optional[byte
     if im.mode != mode:
         raise ValueError(f"{path}: a mode {im.mode} image where {mode} was meant")
     im.save(path, format="PNG", compress_level=compress_level)
-
-
-class _OutputRing:
-    """Two pinned output buffers.  A slot is handed out again only after the writers that read it are done (their exception, if any,
-    is raised there)."""
-
-    def __init__(self, pin: bool):
-        self.pin = pin
-        self.buffers = [torch.empty(0, dtype=torch.uint8), torch.empty(0, dtype=torch.uint8)]
-        self.writers = [[], []]
-
-    def drain(self, slot: int):
-        futures, self.writers[slot] = self.writers[slot], []
-        error = None
-        for f in futures:
-            try:
-                f.result()
-            except BaseException as e:          # every writer of the slot is waited for; the first failure is the one reported
-                error = error or e
-        if error is not None:
-            raise error
-
-    def take(self, slot: int, nbytes: int) -> torch.Tensor:
-        self.drain(slot)
-        if self.buffers[slot].numel() < nbytes:
-            self.buffers[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=self.pin)
-        return self.buffers[slot][:nbytes]
 
 
 @torch.no_grad()
@@ -218,10 +191,8 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     in input-path order, "n_images": int}.
     A missing or unreadable image (FileNotFoundError / OSError / ValueError) and a directory or file that cannot be written (OSError)
     are raised here; no decoding or writing thread outlives the call and the device stays usable."""
-    from . import ops, preprocess
     p_images = [os.fspath(p) for p in p_images]
-    if not (hasattr(network, "_get_engine") and hasattr(network, "predict") and hasattr(network, "text_embeddings")):
-        raise TypeError("predict_from_files needs the MI355X drop-in ZUTIS (networks/zutis.py of the overlay): there is no torch / CPU fallback")
+    _require_dropin(network, "predict_from_files")
     n = int(network.text_embeddings.shape[0])
     pal = _validate(n, len(p_images), semantic, instance, label_format, palette, overlay, alpha, image_ids, compress_level)
     label_paths = overlay_paths = None
@@ -242,69 +213,48 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
         lut = torch.from_numpy(preprocess.normalise_table(mean, std)).to(dev)
         pal_dev = torch.from_numpy(pal).to(dev) if (overlay and pal is not None) else None
         loader = preprocess.PredictBatchLoader(p_images, max_size, batch_size, n_decode, window=window)
-        ring = _OutputRing(loader.pin)
-        copied = torch.cuda.Event()
-        fetched = [torch.cuda.Event(), torch.cuda.Event()]
-        writers = ThreadPoolExecutor(max_workers=n_write, thread_name_prefix="zutis-write") if n_write else None
-        batches = iter(loader)
         waiting = None                                                                     # (slot, host bytes, indices, (H, W)) of the batch whose copy back is in flight
 
         def hand_to_writers(slot, host, indices, H, W):
-            fetched[slot].synchronize()                                                    # the bytes are in the pinned buffer
+            ring.events[slot].synchronize()                                                # the bytes are in the pinned buffer
             a = host.numpy()
             B = len(indices)
             lab = a[:B * H * W * ch].reshape((B, H, W) if ch == 1 else (B, H, W, ch))
             ovl = a[B * H * W * ch:].reshape(B, H, W, 3) if overlay else None
             for b, i in enumerate(indices):
-                ring.writers[slot].append(writers.submit(_write_png, label_paths[i], lab[b], mode, pal_bytes, int(compress_level)))
+                ring.submit(slot, _write_png, label_paths[i], lab[b], mode, pal_bytes, int(compress_level))
                 if overlay:
-                    ring.writers[slot].append(writers.submit(_write_png, overlay_paths[i], ovl[b], "RGB", None, int(compress_level)))
+                    ring.submit(slot, _write_png, overlay_paths[i], ovl[b], "RGB", None, int(compress_level))
 
-        with torch.cuda.device(dev):
-            try:
-                for k, batch in enumerate(batches):
-                    B, (H, W), (oh, ow) = len(batch.paths), batch.size_hw, batch.out_hw
-                    if overlay and batch.n_host:
-                        raise NotImplementedError(f"predict_from_files: {batch.host_paths[0]} was resized on the host (a side more than 75 times its "
-                                                  f"target): its decoded image is not on the device at file size, no overlay can be made")
-                    staged = batch.staging.to(dev, non_blocking=True)                      # descriptors + image bytes: one H2D
-                    copied.record()
-                    packed, desc = preprocess.split_staging(staged, B)
-                    x = ops.resize_normalize(packed, desc, oh, ow, lut, filter="bilinear", kmax=batch.kmax)
-                    out = network(x)                                                       # the module's forward: its hipGraph replay applies
-                    if semantic:
-                        slot = k % 2
-                        nl = B * H * W * ch
-                        host = ring.take(slot, nl + (3 * B * H * W if overlay else 0))     # waits for the writers of batch k - 2
-                        dev_out = torch.empty((host.numel(),), dtype=torch.uint8, device=dev)
-                        eng.label_bytes(out["patch_tokens"], network.text_embeddings, (H, W), label_format=label_format,
-                                        labels_out=dev_out[:nl].view((B, H, W) if ch == 1 else (B, H, W, ch)), palette=pal_dev,
-                                        packed=packed if overlay else None, desc=desc if overlay else None, alpha=int(alpha),
-                                        overlay_out=dev_out[nl:].view(B, H, W, 3) if overlay else None, desc_host=batch.desc)
-                        host.copy_(dev_out, non_blocking=True)                             # labels + overlay: one D2H
-                        fetched[slot].record()
-                        if waiting is not None:
-                            hand_to_writers(*waiting)                                      # batch k - 1 is encoded while batch k is on the device
-                        waiting = (slot, host, list(batch.indices), H, W)
-                    if instance:                                                           # coco20k_eval.py:258-265, trainer.py:337-345
-                        for p in network.predict(dict_outputs=out, mask_type="instance", size=(H, W), image_ids=list(batch.indices),
-                                                 label_id_to_category=label_id_to_category,
-                                                 new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type):
-                            i = p["image_id"]
-                            p["image_id"] = image_ids[i] if image_ids is not None else 0
-                            per_image[i].append(p)
-                    copied.synchronize()                                                   # the loader may now decode into this staging buffer again
-                if waiting is not None:
-                    hand_to_writers(*waiting)
-                    waiting = None
-                ring.drain(0)
-                ring.drain(1)
-                eng.check_finite()                                                         # the forwards' status word: one read for the whole run
-            finally:
-                torch.cuda.synchronize(dev)                                                # nothing in flight on the pinned buffers when they go
-                batches.close()                                                            # a failure outside the loader: its threads end here
-                if writers is not None:
-                    writers.shutdown(wait=True, cancel_futures=True)
+        with preprocess.WriterRing(loader.pin, n_write, "zutis-write") as ring, \
+                preprocess.device_batches(loader, dev, preprocess.resize_normalize_of(lut)) as steps:
+            for k, (batch, (packed, desc), x) in enumerate(steps):
+                B, (H, W) = len(batch.paths), batch.size_hw
+                if overlay and batch.n_host:
+                    raise NotImplementedError(f"predict_from_files: {batch.host_paths[0]} was resized on the host (a side more than 75 times its "
+                                              f"target): its decoded image is not on the device at file size, no overlay can be made")
+                out = network(x)                                                           # the module's forward: its hipGraph replay applies
+                if semantic:
+                    slot = k % 2
+                    nl = B * H * W * ch
+                    host, _ = ring.take(slot, nl + (3 * B * H * W if overlay else 0))      # waits for the writers of batch k - 2
+                    dev_out = torch.empty((host.numel(),), dtype=torch.uint8, device=dev)
+                    eng.label_bytes(out["patch_tokens"], network.text_embeddings, (H, W), label_format=label_format,
+                                    labels_out=dev_out[:nl].view((B, H, W) if ch == 1 else (B, H, W, ch)), palette=pal_dev,
+                                    packed=packed if overlay else None, desc=desc if overlay else None, alpha=int(alpha),
+                                    overlay_out=dev_out[nl:].view(B, H, W, 3) if overlay else None, desc_host=batch.desc)
+                    host.copy_(dev_out, non_blocking=True)                                 # labels + overlay: one D2H
+                    ring.events[slot].record()
+                    if waiting is not None:
+                        hand_to_writers(*waiting)                                          # batch k - 1 is encoded while batch k is on the device
+                    waiting = (slot, host, list(batch.indices), H, W)
+                if instance:
+                    collect_instance_predictions(network, out, batch, image_ids, per_image, label_id_to_category=label_id_to_category,
+                                                 new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type)
+            if waiting is not None:
+                hand_to_writers(*waiting)
+            ring.drain()
+            eng.check_finite()                                                             # the forwards' status word: one read for the whole run
     predictions = [p for ps in per_image for p in ps]
     if predictions_json is not None:
         d = os.path.dirname(os.fspath(predictions_json))

@@ -1,5 +1,8 @@
-"""Host side of the device pre-processing of embedding extraction (csrc/preprocess.hip, ops.resize_crop_normalize) and of pseudo-label
-generation from files (ops.resize_normalize).
+"""Host side of every "from image files" driver: embedding extraction (csrc/preprocess.hip, ops.resize_crop_normalize), pseudo-labels,
+evaluation and prediction (ops.resize_normalize) and, through synth.TrainBatchLoader, training samples.  ONE pipeline: threads decode one
+batch ahead into one of two reused pinned buffers (prefetch, DoubleBuffer), one host-to-device copy and one kernel per batch
+(device_batches), and, where files are written, two pinned output buffers whose writer threads work while the next batch is on the
+device (WriterRing).
 
 The reference feeds CLIP through SimpleDataset's transform (utils/extract_image_embeddings.py:97-103: Resize BICUBIC, CenterCrop,
 ToTensor, Normalize) under a 16-worker DataLoader (:64-65).  Here the workers are THREADS that only open and decode (Pillow
@@ -8,18 +11,24 @@ is also what crosses PCIe (3 bytes per source pixel instead of 12 per output pix
 
   pil_resize_reference  NumPy restatement of Pillow's 8-bit resampler (bicubic, bilinear) — the CPU oracle of the tests, not a product path
   normalise_table       the 3 x 256 fp32 table the kernel looks normalised values up in
+  DoubleBuffer          two reused byte buffers, regrown by a quarter: every staging and output buffer of the pipeline
+  prefetch              the "start item k + 1, wait for item k, yield it" loop over a pool of decoding threads — the only one
   BatchLoader           paths -> batches of (packed bytes + descriptor rows) in reused staging buffers, decoded one batch ahead
   ShapeBucketLoader     the same staging for MaskDataset's transform (datasets/index_dataset.py:405-411): batches of ONE resized shape,
-                        gathered from a bounded window of paths ahead, so that the batched SelfMask + solver run batched
-
-  EvalBatchLoader       ShapeBucketLoader for evaluation: every image travels with its ground-truth PNG (one staging buffer, one copy)
-  PredictBatchLoader    EvalBatchLoader's batches without the ground truth: images of one file size, for predictions at that size
+                        gathered from a bounded window of paths ahead, so that the batched SelfMask + solver run batched; optionally
+                        of one file size too, and with a ground-truth PNG per image in the tail of the same staging buffer
+  EvalBatchLoader       its constructor for evaluation: one file size per batch, every image travels with its ground truth
+  PredictBatchLoader    its constructor for prediction: EvalBatchLoader's batches without the ground truth
+  device_batches        the per-batch device sequence of every driver: H2D, event, views, the resize kernel, clean-up
+  WriterRing            two output slots (pinned buffer, event, writer futures) over a pool of writer threads; thread_split beside it
 
 Threads, not processes: no child ever holds the device open, nothing is pickled, a worker's exception is raised by the caller.
 """
 from __future__ import annotations
 
 import collections
+import contextlib
+import itertools
 import math
 from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, List, Sequence
@@ -30,7 +39,7 @@ from PIL import Image
 
 PRECISION_BITS = 32 - 8 - 2     # Pillow's fixed-point coefficients: src/libImaging/Resample.c
 KMAX = 152                      # taps per output pixel the kernel serves (include/zutis_hip.h ZH_RCN_KMAX)
-MAX_WORKERS = 16
+MAX_THREADS = 16                # decoding and writing threads of one call, together
 ALIGN = 16                      # byte alignment of an image inside the packed buffer (descriptors hold offset / 16)
 DESC_INTS = 8                   # offset / 16, w, h, nw, nh, left, top, 0
 
@@ -134,10 +143,65 @@ def device_supported(w: int, h: int, n_px: int) -> bool:
     return nw > 0 and nh > 0 and _taps_ok(w, h, nw, nh)
 
 
-Batch = collections.namedtuple("Batch", "paths staging packed desc kmax n_host")
-Batch.__doc__ = """One decoded batch.  staging: u8 tensor [32 * B + pixel bytes] (pinned when the loader pins), descriptor rows first —
-one host-to-device copy moves both; packed / desc: its two views (u8 [bytes], int32 [B, 8]), offsets relative to `packed`; kmax: the
-batch's largest tap count; n_host: images that were resized on the host (outside device_supported).  Valid until the loader is advanced."""
+Batch = collections.namedtuple("Batch", "paths indices sizes_hw size_hw out_hw staging packed desc kmax n_host host_paths gt_paths gt packed_bytes",
+                               defaults=(None,) * 14)
+Batch.__doc__ = """One decoded batch of any loader; a field that does not apply is None.  paths: its files; staging: u8 tensor [32 * B +
+packed_bytes (+ ground-truth bytes)] (pinned when the loader pins), descriptor rows first — one host-to-device copy moves all of it;
+packed / desc: its first two views (u8 [packed_bytes], int32 [B, 8]), offsets relative to `packed`; kmax: the batch's largest tap count;
+n_host / host_paths: the images that were resized on the host (outside device_supported: their packed bytes are NOT at file size).
+ShapeBucketLoader adds indices: the files' positions in the loader's path list; sizes_hw: the files' own (H, W); out_hw: the (out_h,
+out_w) every image of the batch resizes to; size_hw: the (H, W) every file has, when the file size is part of the bucket key;
+gt_paths / gt: the ground-truth files and the host view u8 [B, H, W] ("u8") or [B, H, W, 3] ("rg16") of the staging buffer's tail.
+Valid until the loader is advanced."""
+
+
+class DoubleBuffer:
+    """Two reused u8 buffers, pinned host memory (`pin`) or memory of `device`: take(slot, nbytes) is a view of nbytes bytes of buffer
+    `slot`, which is replaced by one a quarter larger when the request exceeds it (from the calling thread)."""
+
+    def __init__(self, pin: bool, device=None):
+        self.pin, self.device = bool(pin), device
+        self.buffers: List[torch.Tensor] = [torch.empty(0, dtype=torch.uint8), torch.empty(0, dtype=torch.uint8)]
+
+    def take(self, slot: int, nbytes: int) -> torch.Tensor:
+        if self.buffers[slot].numel() < nbytes:
+            self.buffers[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, device=self.device, pin_memory=self.pin)
+        return self.buffers[slot][:nbytes]
+
+
+def prefetch(items, start: Callable, n_threads: int):
+    """Decode one item ahead: over a pool of n_threads threads, `start(pool, slot, item)` -> (batch, futures) lays item k + 1 out in
+    staging slot (k + 1) % 2 and submits its decodes, after the futures of item k have been waited for (a worker's exception is raised
+    there, by the step that needs its batch) and before batch k is yielded.  items: an iterable of work items — none: no pool is made —
+    or a function of the pool that returns one (a source that reads file headers with the same threads).  `start` runs on the calling
+    thread, in item order.  When the generator is closed or fails, what is still pending is cancelled and the pool joined: no thread
+    outlives it."""
+    if not callable(items):
+        rest = iter(items)
+        first = next(rest, None)
+        if first is None:
+            return
+        items = lambda pool: itertools.chain((first,), rest)       # noqa: E731
+    with ThreadPoolExecutor(max_workers=n_threads, thread_name_prefix="zutis-decode") as pool:
+        items, slot, pending = iter(items(pool)), 0, None
+        try:
+            item = next(items, None)
+            if item is not None:
+                pending = start(pool, slot, item)
+            while pending is not None:
+                batch, futures = pending
+                pending = None
+                for f in futures:
+                    f.result()                  # raises what the worker raised
+                item = next(items, None)
+                if item is not None:
+                    slot ^= 1
+                    pending = start(pool, slot, item)
+                yield batch
+        finally:
+            if pending is not None:
+                for f in pending[1]:
+                    f.cancel()
 
 
 def split_staging(staging: torch.Tensor, B: int):
@@ -158,19 +222,13 @@ class BatchLoader:
         if batch_size < 1 or n_px < 1:
             raise ValueError("BatchLoader: batch_size and n_px must be positive")
         self.paths, self.n_px, self.batch_size, self.box = list(paths), int(n_px), int(batch_size), box
-        self.n_threads = max(1, min(int(n_workers), MAX_WORKERS))
+        self.n_threads = max(1, min(int(n_workers), MAX_THREADS))
         self.pin = torch.cuda.is_available() if pin is None else bool(pin)
         self.filter = "bicubic"
-        self._buffers: List[torch.Tensor] = [torch.empty(0, dtype=torch.uint8), torch.empty(0, dtype=torch.uint8)]
+        self._staging = DoubleBuffer(self.pin)
 
     def __len__(self):
         return (len(self.paths) + self.batch_size - 1) // self.batch_size
-
-    def _staging(self, slot: int, nbytes: int) -> torch.Tensor:
-        """The slot's staging buffer, grown (from the calling thread) when the batch needs more."""
-        if self._buffers[slot].numel() < nbytes:
-            self._buffers[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=self.pin)
-        return self._buffers[slot][:nbytes]
 
     @staticmethod
     def _size(path: str):
@@ -188,8 +246,8 @@ class BatchLoader:
 
     def _pack(self, pool: ThreadPoolExecutor, slot: int, chunk, sizes, boxes, out_wh, extra: int = 0):
         """Lay `chunk` (files of `sizes` = (w, h), resized and cropped as `boxes` = ((nw, nh), (left, top)) say, to out_wh = (w, h) of the
-        kernel's output) out in staging buffer `slot` and start its decodes: (staging, packed, desc, kmax, images resized on the host,
-        futures).  extra: bytes the staging buffer holds behind the packed images (packed stops in front of them)."""
+        kernel's output) out in staging buffer `slot` and start its decodes: (Batch, futures).  extra: bytes the staging buffer holds
+        behind the packed images (packed stops in front of them)."""
         B, (ow, oh) = len(chunk), out_wh
         rows = np.zeros((B, DESC_INTS), np.int32)
         host_boxes, shapes, kmax, off = [], [], ksize(1, 1, self.filter), 0
@@ -206,41 +264,24 @@ class BatchLoader:
             shapes.append((off, h, w))
             off += -(-3 * w * h // ALIGN) * ALIGN
         head = B * DESC_INTS * 4
-        staging = self._staging(slot, head + off + extra)
+        staging = self._staging.take(slot, head + off + extra)
         packed, desc = split_staging(staging[:head + off], B)
         desc.numpy()[...] = rows
         pix = packed.numpy()
         futures = [pool.submit(self._decode, p, pix[o:o + 3 * w * h].reshape(h, w, 3), size, hb, out_wh)
                    for p, (o, h, w), size, hb in zip(chunk, shapes, sizes, host_boxes)]
-        return staging, packed, desc, kmax, sum(hb is not None for hb in host_boxes), futures
+        host = [p for p, hb in zip(chunk, host_boxes) if hb is not None]
+        return Batch(paths=chunk, staging=staging, packed=packed, desc=desc, kmax=kmax, n_host=len(host), host_paths=host, packed_bytes=off), futures
 
-    def _submit(self, pool: ThreadPoolExecutor, k: int):
+    def _start(self, pool: ThreadPoolExecutor, slot: int, k: int):
         """Fix batch k's layout from the headers and start its decodes: (Batch, futures)."""
         chunk = self.paths[k * self.batch_size:(k + 1) * self.batch_size]
         sizes = list(pool.map(self._size, chunk))
         n = self.n_px
-        staging, packed, desc, kmax, n_host, futures = self._pack(pool, k % 2, chunk, sizes, [self.box(w, h, n) for w, h in sizes], (n, n))
-        return Batch(chunk, staging, packed, desc, kmax, n_host), futures
+        return self._pack(pool, slot, chunk, sizes, [self.box(w, h, n) for w, h in sizes], (n, n))
 
     def __iter__(self):
-        n_batches = len(self)
-        if n_batches == 0:
-            return
-        with ThreadPoolExecutor(max_workers=self.n_threads, thread_name_prefix="zutis-decode") as pool:
-            pending = self._submit(pool, 0)
-            try:
-                for k in range(n_batches):
-                    batch, futures = pending
-                    pending = None
-                    for f in futures:
-                        f.result()              # raises what the worker raised
-                    if k + 1 < n_batches:
-                        pending = self._submit(pool, k + 1)
-                    yield batch
-            finally:
-                if pending is not None:
-                    for f in pending[1]:
-                        f.cancel()
+        return prefetch(range(len(self)), self._start, self.n_threads)
 
 
 def mask_dataset_size(w: int, h: int, image_size):
@@ -289,30 +330,51 @@ def bucket_batches(shapes: Sequence, batch_size: int, window: int) -> List[List[
     return list(_buckets(shapes, batch_size, window))
 
 
-ShapeBatch = collections.namedtuple("ShapeBatch", "paths indices sizes_hw out_hw staging packed desc kmax n_host")
-ShapeBatch.__doc__ = """One decoded batch of ONE resized shape.  paths / indices: its files and their positions in the loader's path list;
-sizes_hw: the files' own (H, W); out_hw: the (out_h, out_w) every image of the batch resizes to; the rest as in Batch."""
+GT_MODES = {"u8": ("L", "P"), "rg16": ("RGB",)}      # Pillow modes np.array() turns into u8 [H, W] / u8 [H, W, 3]
+GT_CHANNELS = {"u8": 1, "rg16": 3}
 
 
 class ShapeBucketLoader(BatchLoader):
     """BatchLoader's threads and staging for MaskDataset's transform (datasets/index_dataset.py:388-411): every image is resized whole —
-    shorter side to `image_size` (mask_dataset_size), `filter` bilinear — so a batch for ops.resize_normalize must be of one resized
-    shape.  The loader reads the headers of at most `window` paths at a time, groups them with bucket_batches (a deterministic function
-    of the path list, batch_size and window: batches come OUT OF INPUT ORDER and carry their indices) and decodes one batch ahead.
-    An image outside the kernel's envelope (more than KMAX taps per output pixel — a source side over 75 times the target with
-    bilinear's 3-tap support — or 3 w h >= 2^31) is resized by Pillow in its worker and packed as an identity image.  A missing or
-    unreadable file raises in the step that reads its header or needs its batch, at the latest."""
+    `size_rule(w, h, image_size)` gives its (nw, nh): mask_dataset_size (shorter side to image_size), `filter` bilinear — so a batch for
+    ops.resize_normalize must be of one resized shape.  The loader reads the headers of at most `window` paths at a time, groups them
+    with bucket_batches (a deterministic function of the path list, batch_size and window: batches come OUT OF INPUT ORDER and carry
+    their indices) and decodes one batch ahead.  An image outside the kernel's envelope (more than KMAX taps per output pixel — a source
+    side over 75 times the target with bilinear's 3-tap support — or 3 w h >= 2^31) is resized by Pillow in its worker and packed as an
+    identity image.  A missing or unreadable file raises in the step that reads its header or needs its batch, at the latest.
+    by_file_size: the file's (w, h) is part of the bucket key, (the resized (nw, nh), (w, h)) — with longer_edge_size the value of
+    eval_bucket_key(w, h, w, h, image_size) — and the batch carries size_hw.
+    gt_paths: one ground-truth PNG per image, of `gt_format` ("u8": an 8-bit grey or palette PNG, the byte is the label; "rg16": an RGB
+    PNG, label R + 256 G, imagenet_s.py:93), decoded by the same threads into the tail of the same staging buffer.  A ground-truth file
+    of another mode, or of another size than its image, raises ValueError naming the file."""
 
-    def __init__(self, paths: Sequence[str], image_size, batch_size: int, n_workers: int, window: int = 512, filter: str = "bilinear", pin=None):
+    def __init__(self, paths: Sequence[str], image_size, batch_size: int, n_workers: int, window: int = 512, filter: str = "bilinear", pin=None, *,
+                 size_rule: Callable = mask_dataset_size, by_file_size: bool = False, gt_paths=None, gt_format: str = "u8"):
         if image_size is not None and image_size < 1:
             raise ValueError("ShapeBucketLoader: image_size must be positive or None")
         if window < 1 or filter not in FILTERS:
             raise ValueError(f"ShapeBucketLoader: window must be positive and filter one of {sorted(FILTERS)}")
         super().__init__(paths, 1, batch_size, n_workers, None, pin)
         self.image_size, self.window, self.filter = image_size, int(window), filter
+        self.size_rule, self.by_file_size = size_rule, bool(by_file_size)
+        self.gt_paths, self.gt_format = None if gt_paths is None else list(gt_paths), gt_format
 
     def __len__(self):
         raise TypeError("ShapeBucketLoader: the number of batches depends on the files' shapes")
+
+    def _gt_size(self, path: str):
+        with Image.open(path) as im:            # header only
+            if im.mode not in GT_MODES[self.gt_format]:
+                raise ValueError(f"{path}: ground truth of mode {im.mode!r}, gt_format {self.gt_format!r} needs one of {GT_MODES[self.gt_format]}")
+            return im.size
+
+    @staticmethod
+    def _decode_gt(path: str, dst: np.ndarray):
+        with Image.open(path) as im:
+            a = np.asarray(im)
+        if a.dtype != np.uint8 or a.shape != dst.shape:
+            raise ValueError(f"{path}: ground truth decodes to {a.dtype} {a.shape}, expected uint8 {dst.shape}")
+        np.copyto(dst, a)
 
     def _groups(self, pool: ThreadPoolExecutor):
         """bucket_batches over the path list, its shape keys read from the headers `window` paths at a time: yields (indices, the files'
@@ -322,56 +384,39 @@ class ShapeBucketLoader(BatchLoader):
         def keys():
             for start in range(0, len(self.paths), self.window):
                 block = self.paths[start:start + self.window]
+                gts = None if self.gt_paths is None else list(pool.map(self._gt_size, self.gt_paths[start:start + self.window]))
                 for i, wh in enumerate(pool.map(self._size, block), start):
+                    if gts is not None and gts[i - start] != wh:
+                        raise ValueError(f"{self.gt_paths[i]}: ground truth of size {gts[i - start]}, its image {self.paths[i]} is {wh}")
                     sizes[i] = wh
                 for i in range(start, start + len(block)):
-                    yield mask_dataset_size(*sizes[i], self.image_size)
+                    resized = self.size_rule(*sizes[i], self.image_size)
+                    yield (resized, sizes[i]) if self.by_file_size else resized
 
         for idx in _buckets(keys(), self.batch_size, self.window):
             wh = [sizes.pop(i) for i in idx]
-            yield idx, wh, mask_dataset_size(*wh[0], self.image_size)
+            yield idx, wh, self.size_rule(*wh[0], self.image_size)
 
     def _start(self, pool: ThreadPoolExecutor, slot: int, group):
         idx, sizes, (nw, nh) = group
-        chunk = [self.paths[i] for i in idx]
-        staging, packed, desc, kmax, n_host, futures = self._pack(pool, slot, chunk, sizes, [((nw, nh), (0, 0))] * len(idx), (nw, nh))
-        return ShapeBatch(chunk, idx, [(h, w) for w, h in sizes], (nh, nw), staging, packed, desc, kmax, n_host), futures
+        B, (w, h) = len(idx), sizes[0]
+        ch = 0 if self.gt_paths is None else GT_CHANNELS[self.gt_format]
+        batch, futures = self._pack(pool, slot, [self.paths[i] for i in idx], sizes, [((nw, nh), (0, 0))] * B, (nw, nh), extra=B * h * w * ch)
+        batch = batch._replace(indices=idx, sizes_hw=[(h_, w_) for w_, h_ in sizes], out_hw=(nh, nw), size_hw=(h, w) if self.by_file_size else None)
+        if ch:
+            gts = [self.gt_paths[i] for i in idx]
+            gt = batch.staging[B * DESC_INTS * 4 + batch.packed_bytes:].view((B, h, w) if ch == 1 else (B, h, w, ch))
+            gt_np = gt.numpy()
+            futures += [pool.submit(self._decode_gt, p, gt_np[b]) for b, p in enumerate(gts)]
+            batch = batch._replace(gt_paths=gts, gt=gt)
+        return batch, futures
 
     def __iter__(self):
-        with ThreadPoolExecutor(max_workers=self.n_threads, thread_name_prefix="zutis-decode") as pool:
-            groups = self._groups(pool)
-            first = next(groups, None)
-            pending = None if first is None else self._start(pool, 0, first)
-            k = 0
-            try:
-                while pending is not None:
-                    batch, futures = pending
-                    pending = None
-                    for f in futures:
-                        f.result()              # raises what the worker raised
-                    k += 1
-                    nxt = next(groups, None)
-                    if nxt is not None:
-                        pending = self._start(pool, k % 2, nxt)
-                    yield batch
-            finally:
-                if pending is not None:
-                    for f in pending[1]:
-                        f.cancel()
-
-
-GT_MODES = {"u8": ("L", "P"), "rg16": ("RGB",)}      # Pillow modes np.array() turns into u8 [H, W] / u8 [H, W, 3]
-GT_CHANNELS = {"u8": 1, "rg16": 3}
-
-EvalBatch = collections.namedtuple("EvalBatch", "paths gt_paths indices size_hw out_hw staging packed_bytes gt kmax n_host")
-EvalBatch.__doc__ = """One decoded evaluation batch: images of ONE file size that resize to ONE shape, with their ground truth.  paths /
-gt_paths / indices: the files and their positions in the loader's lists; size_hw: the (H, W) every file of the batch has; out_hw: what
-the images resize to; staging: u8 [32 * B + packed_bytes + ground-truth bytes] — descriptor rows, the packed images, then gt, the host
-view u8 [B, H, W] ("u8") or [B, H, W, 3] ("rg16") of its tail; kmax, n_host as in Batch."""
+        return prefetch(self._groups, self._start, self.n_threads)
 
 
 def split_eval_staging(staging: torch.Tensor, B: int, packed_bytes: int, gt_shape):
-    """(packed, desc, gt) views of an EvalBatch's staging tensor (host or device)."""
+    """(packed, desc, gt) views of the staging tensor (host or device) of a batch with ground truth."""
     head = B * DESC_INTS * 4 + packed_bytes
     packed, desc = split_staging(staging[:head], B)
     return packed, desc, staging[head:].view(gt_shape)
@@ -385,11 +430,9 @@ def eval_bucket_key(w: int, h: int, gw: int, gh: int, max_size):
 
 class EvalBatchLoader(ShapeBucketLoader):
     """ShapeBucketLoader for the validation datasets: image i is scored against the ground-truth PNG gt_paths[i] at the file's own size
-    (trainer.py:322-325), so a batch shares the image file size as well as the resized shape (eval_bucket_key), and the ground truth is
-    decoded by the same threads into the tail of the same staging buffer.  max_size: None (the image goes in as it is: coco2017.py,
-    coco20k.py) or the cap of the longer edge (longer_edge_size, imagenet_s.py:71-76), Pillow BILINEAR.  gt_format "u8": an 8-bit
-    grey or palette PNG, the byte is the label; "rg16": an RGB PNG, label R + 256 G (imagenet_s.py:93).  A ground-truth file of
-    another mode, or of another size than its image, raises ValueError naming the file."""
+    (trainer.py:322-325), so a batch shares the image file size as well as the resized shape (eval_bucket_key), and the ground truth
+    travels in the same staging buffer.  max_size: None (the image goes in as it is: coco2017.py, coco20k.py) or the cap of the longer
+    edge (longer_edge_size, imagenet_s.py:71-76), Pillow BILINEAR.  gt_format as ShapeBucketLoader's."""
 
     def __init__(self, paths: Sequence[str], gt_paths: Sequence[str], max_size, batch_size: int, n_workers: int, window: int = 512,
                  gt_format: str = "u8", pin=None):
@@ -397,55 +440,8 @@ class EvalBatchLoader(ShapeBucketLoader):
             raise ValueError(f"EvalBatchLoader: gt_format {gt_format!r} is not one of {sorted(GT_MODES)}")
         if len(paths) != len(gt_paths):
             raise ValueError("EvalBatchLoader: one ground-truth file per image")
-        super().__init__(paths, max_size, batch_size, n_workers, window=window, filter="bilinear", pin=pin)
-        self.gt_paths, self.max_size, self.gt_format = list(gt_paths), max_size, gt_format
-
-    def _gt_size(self, path: str):
-        with Image.open(path) as im:            # header only
-            if im.mode not in GT_MODES[self.gt_format]:
-                raise ValueError(f"{path}: ground truth of mode {im.mode!r}, gt_format {self.gt_format!r} needs one of {GT_MODES[self.gt_format]}")
-            return im.size
-
-    def _decode_gt(self, path: str, dst: np.ndarray):
-        with Image.open(path) as im:
-            a = np.asarray(im)
-        if a.dtype != np.uint8 or a.shape != dst.shape:
-            raise ValueError(f"{path}: ground truth decodes to {a.dtype} {a.shape}, expected uint8 {dst.shape}")
-        np.copyto(dst, a)
-
-    def _groups(self, pool: ThreadPoolExecutor):
-        sizes = {}
-
-        def keys():
-            for start in range(0, len(self.paths), self.window):
-                block = self.paths[start:start + self.window]
-                gts = list(pool.map(self._gt_size, self.gt_paths[start:start + self.window]))
-                for i, wh in enumerate(pool.map(self._size, block), start):
-                    if gts[i - start] != wh:
-                        raise ValueError(f"{self.gt_paths[i]}: ground truth of size {gts[i - start]}, its image {self.paths[i]} is {wh}")
-                    sizes[i] = wh
-                for i in range(start, start + len(block)):
-                    yield eval_bucket_key(*sizes[i], *sizes[i], self.max_size)
-
-        for idx in _buckets(keys(), self.batch_size, self.window):
-            wh = [sizes.pop(i) for i in idx]
-            yield idx, wh, longer_edge_size(*wh[0], self.max_size)
-
-    def _start(self, pool: ThreadPoolExecutor, slot: int, group):
-        idx, sizes, (nw, nh) = group
-        B, (w, h), ch = len(idx), sizes[0], GT_CHANNELS[self.gt_format]
-        chunk, gts = [self.paths[i] for i in idx], [self.gt_paths[i] for i in idx]
-        staging, packed, desc, kmax, n_host, futures = self._pack(pool, slot, chunk, sizes, [((nw, nh), (0, 0))] * B, (nw, nh), extra=B * h * w * ch)
-        gt = staging[B * DESC_INTS * 4 + packed.numel():].view((B, h, w) if ch == 1 else (B, h, w, ch))
-        gt_np = gt.numpy()
-        futures += [pool.submit(self._decode_gt, p, gt_np[b]) for b, p in enumerate(gts)]
-        return EvalBatch(chunk, gts, idx, (h, w), (nh, nw), staging, packed.numel(), gt, kmax, n_host), futures
-
-
-PredictBatch = collections.namedtuple("PredictBatch", "paths indices size_hw out_hw staging packed desc kmax n_host host_paths")
-PredictBatch.__doc__ = """One decoded batch of images of ONE file size that resize to ONE shape.  paths / indices: the files and their
-positions in the loader's list; size_hw: the (H, W) every file of the batch has; out_hw: what the images resize to; staging / packed /
-desc / kmax / n_host as in Batch; host_paths: the files that were resized on the host (their packed bytes are NOT at file size)."""
+        super().__init__(paths, max_size, batch_size, n_workers, window=window, filter="bilinear", pin=pin, size_rule=longer_edge_size,
+                         by_file_size=True, gt_paths=gt_paths, gt_format=gt_format)
 
 
 class PredictBatchLoader(ShapeBucketLoader):
@@ -454,27 +450,93 @@ class PredictBatchLoader(ShapeBucketLoader):
     max_size): for one path list, batch_size and window its batches are EvalBatchLoader's.  max_size as there."""
 
     def __init__(self, paths: Sequence[str], max_size, batch_size: int, n_workers: int, window: int = 512, pin=None):
-        super().__init__(paths, max_size, batch_size, n_workers, window=window, filter="bilinear", pin=pin)
-        self.max_size = max_size
+        super().__init__(paths, max_size, batch_size, n_workers, window=window, filter="bilinear", pin=pin, size_rule=longer_edge_size,
+                         by_file_size=True)
 
-    def _groups(self, pool: ThreadPoolExecutor):
-        sizes = {}
 
-        def keys():
-            for start in range(0, len(self.paths), self.window):
-                block = self.paths[start:start + self.window]
-                for i, wh in enumerate(pool.map(self._size, block), start):
-                    sizes[i] = wh
-                for i in range(start, start + len(block)):
-                    yield eval_bucket_key(*sizes[i], *sizes[i], self.max_size)
+# ------------------------------------------------------------------------------------------------- the device side of a driver
+def resize_normalize_of(lut: torch.Tensor):
+    """The `transform` of device_batches for a ShapeBucketLoader: (the staging views — split_staging's, or split_eval_staging's with ground
+    truth —, ops.resize_normalize of the batch: Pillow BILINEAR + to_tensor + normalize, the identity where nothing is resized)."""
+    from . import ops
 
-        for idx in _buckets(keys(), self.batch_size, self.window):
-            wh = [sizes.pop(i) for i in idx]
-            yield idx, wh, longer_edge_size(*wh[0], self.max_size)
+    def transform(batch: Batch, staged: torch.Tensor):
+        B, (oh, ow) = len(batch.paths), batch.out_hw
+        views = split_staging(staged, B) if batch.gt is None else split_eval_staging(staged, B, batch.packed_bytes, tuple(batch.gt.shape))
+        return views, ops.resize_normalize(views[0], views[1], oh, ow, lut, filter="bilinear", kmax=batch.kmax)
+    return transform
 
-    def _start(self, pool: ThreadPoolExecutor, slot: int, group):
-        idx, sizes, (nw, nh) = group
-        (w, h), chunk = sizes[0], [self.paths[i] for i in idx]
-        staging, packed, desc, kmax, n_host, futures = self._pack(pool, slot, chunk, sizes, [((nw, nh), (0, 0))] * len(idx), (nw, nh))
-        host = [p for p in chunk if not _taps_ok(w, h, nw, nh, self.filter)] if n_host else []
-        return PredictBatch(chunk, idx, (h, w), (nh, nw), staging, packed, desc, kmax, n_host, host), futures
+
+@contextlib.contextmanager
+def device_batches(loader, dev, transform: Callable):
+    """The device loop every driver shares, `dev` the current device inside: `with device_batches(...) as steps: for batch, views, x in
+    steps: <the driver's work on the batch>`.  Per batch: ONE non-blocking host-to-device copy of batch.staging (descriptors + decoded
+    bytes + whatever rides behind them), an event behind it, `transform(batch, staged)` -> (views, x); after the driver's body, and before
+    the loader is advanced, the event is waited for — the loader may then decode into that staging buffer again.  On the way out, whether
+    the body, the loader or a kernel failed or nothing did: the device is synchronised (nothing in flight on the pinned buffers when they
+    go) and the loader's generator closed (a failure outside the loader: its threads end here)."""
+    copied = torch.cuda.Event()
+    batches = iter(loader)
+
+    def steps():
+        for batch in batches:
+            staged = batch.staging.to(dev, non_blocking=True)
+            copied.record()
+            yield (batch, *transform(batch, staged))
+            copied.synchronize()
+
+    with torch.cuda.device(dev):
+        try:
+            yield steps()
+        finally:
+            torch.cuda.synchronize(dev)
+            batches.close()
+
+
+# ------------------------------------------------------------------------------------------------- the output side of a driver
+def thread_split(n_workers: int, share: float):
+    """(decoders, writers) of a driver that writes files: together min(n_workers, 16) threads but two at the least, the writers `share`
+    of them (rounded down) but one at the least."""
+    total = max(2, min(int(n_workers), MAX_THREADS))
+    n_write = max(1, int(total * share))
+    return total - n_write, n_write
+
+
+class WriterRing:
+    """Two output slots over a pool of `n_writers` threads named `prefix`: per slot a pinned host buffer (and its twin on `device`, when
+    one is given), the event the driver records behind the copy into it, and the futures of the writers that read it.  take() hands a
+    slot out again only after those writers are done.  Leaving the `with` block cancels what has not started and joins the pool."""
+
+    def __init__(self, pin: bool, n_writers: int, prefix: str, device=None):
+        self.host, self.dev = DoubleBuffer(pin), None if device is None else DoubleBuffer(False, device)
+        self.events = [torch.cuda.Event(), torch.cuda.Event()] if torch.cuda.is_available() else [None, None]
+        self.writers: List[list] = [[], []]
+        self.pool = ThreadPoolExecutor(max_workers=n_writers, thread_name_prefix=prefix) if n_writers else None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self.pool is not None:
+            self.pool.shutdown(wait=True, cancel_futures=True)
+
+    def submit(self, slot: int, fn: Callable, *args):
+        self.writers[slot].append(self.pool.submit(fn, *args))
+
+    def drain(self, slot=None):
+        """Wait for EVERY writer of the slot (None: of both); the first failure is the one raised."""
+        error = None
+        for s in (0, 1) if slot is None else (slot,):
+            futures, self.writers[s] = self.writers[s], []
+            for f in futures:
+                try:
+                    f.result()
+                except BaseException as e:
+                    error = error or e
+        if error is not None:
+            raise error
+
+    def take(self, slot: int, nbytes: int):
+        """(host view, device view or None) of nbytes bytes of the slot, once its writers are done (drain)."""
+        self.drain(slot)
+        return self.host.take(slot, nbytes), None if self.dev is None else self.dev.take(slot, nbytes)

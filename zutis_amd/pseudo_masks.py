@@ -10,13 +10,12 @@ from __future__ import annotations
 
 import json
 import os
-from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import ops, rle
+from . import ops, preprocess, rle
 from .engine import SelfMaskEngine
 
 
@@ -143,30 +142,6 @@ def generate_pseudo_masks(engine: SelfMaskEngine, images: Sequence[torch.Tensor]
 
 
 # ------------------------------------------------------------------------------------- files in, JSON out
-MAX_THREADS = 16        # decoders + writers
-
-
-class _Slot:
-    """One of the two sets of buffers a batch's masks travel through: a device buffer the masks are resized into, its pinned host twin,
-    the event behind the copy between them, and the writer tasks that still read the host side."""
-
-    def __init__(self, device):
-        self.device, self.dev, self.host = device, None, None
-        self.event = torch.cuda.Event()
-        self.tasks = []
-
-    def reserve(self, nbytes: int):
-        if self.dev is None or self.dev.numel() < nbytes:
-            self.dev = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, device=self.device)
-            self.host = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=True)
-
-    def drain(self):
-        """Wait for the writers of the batch that used this slot; raises what a writer raised."""
-        tasks, self.tasks = self.tasks, []
-        for t in tasks:
-            t.result()
-
-
 def _write_masks(event, host: np.ndarray, items):
     """A writer task: once the batch's copy has landed, index_dataset.py:219-224 for some of its masks.  items: (offset, (H, W), path)."""
     event.synchronize()
@@ -179,60 +154,44 @@ def generate_pseudo_masks_from_files(engine: SelfMaskEngine, p_images: Sequence[
                                      mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), bilateral_solver: bool = True,
                                      batch_size: int = 8, n_workers: int = 16, window: int = 512) -> List[str]:
     """IndexDataset.generate_pseudo_masks (datasets/index_dataset.py:177-226) from a list of image files to the RLE JSON files
-    `out_paths`, MaskDataset's transform (:405-411) included.  Threads decode into pinned staging one batch ahead
-    (preprocess.ShapeBucketLoader: batches of ONE resized shape out of a window of `window` paths, so SelfMask and the solver run
-    batched on a corpus of mixed shapes); per batch one host-to-device copy of the decoded bytes, ops.resize_normalize (Pillow's
-    BILINEAR + the normalisation, bit for bit), the device steps of pseudo_masks_batch, every mask resized to its file's own size into
-    one device buffer, one copy to pinned memory behind an event; RLE encoding, the JSON write and its read-back check run on writer
-    threads while the next batch is on the GPU.  n_workers (at most 16) is split between decoders and writers (a quarter, at least one).
+    `out_paths`, MaskDataset's transform (:405-411) included, over the file pipeline of preprocess.py.  Threads decode into pinned
+    staging one batch ahead (ShapeBucketLoader: batches of ONE resized shape out of a window of `window` paths, so SelfMask and the
+    solver run batched on a corpus of mixed shapes); per batch (device_batches) one host-to-device copy of the decoded bytes and
+    ops.resize_normalize (Pillow's BILINEAR + the normalisation, bit for bit); then the device steps of pseudo_masks_batch, every mask
+    resized to its file's own size into one device buffer of a WriterRing slot, one copy to its pinned twin behind the slot's event; RLE
+    encoding, the JSON write and its read-back check run on the ring's threads while the next batch is on the GPU.  n_workers (at most
+    16) is split between decoders and writers (a quarter, at least one).
     Each file is what save_rle_json writes; returns out_paths (input order).  A missing or unreadable image and a writer's exception
     are raised here.  The grouping is preprocess.bucket_batches of the files' resized shapes."""
-    from . import preprocess
     p_images, out_paths = list(p_images), list(out_paths)
     if len(p_images) != len(out_paths):
         raise ValueError("generate_pseudo_masks_from_files: one output path per image")
     if not p_images:
         return out_paths
     dev = engine._device()
-    n_threads = max(2, min(int(n_workers), MAX_THREADS))
-    n_writers = max(1, n_threads // 4)
+    n_decode, n_writers = preprocess.thread_split(n_workers, 0.25)
     lut = torch.from_numpy(preprocess.normalise_table(mean, std)).to(dev)
-    loader = preprocess.ShapeBucketLoader(p_images, image_size, batch_size, n_threads - n_writers, window=window, filter="bilinear")
-    slots = [_Slot(dev), _Slot(dev)]
-    copied = torch.cuda.Event()
-    with ThreadPoolExecutor(max_workers=n_writers, thread_name_prefix="zutis-rle") as writers, torch.cuda.device(dev):
-        try:
-            for k, batch in enumerate(loader):
-                B, (oh, ow) = len(batch.paths), batch.out_hw
-                staged = batch.staging.to(dev, non_blocking=True)                      # descriptors + decoded bytes: one H2D
-                copied.record()
-                packed, desc = preprocess.split_staging(staged, B)
-                x = ops.resize_normalize(packed, desc, oh, ow, lut, filter="bilinear", kmax=batch.kmax)
-                dts = _device_masks_batch(engine, x, bilateral_solver, mean=mean, std=std)
-                slot = slots[k % 2]
-                slot.drain()                                                            # the writers of batch k - 2 are done with its host buffer
-                offs = np.concatenate(([0], np.cumsum([h * w for h, w in batch.sizes_hw]))).tolist()
-                slot.reserve(offs[-1])
-                for b, (h, w) in enumerate(batch.sizes_hw):                             # index_dataset.py:214-215
-                    dst = slot.dev[offs[b]:offs[b + 1]].view(h, w)
-                    if (h, w) == (oh, ow):
-                        dst.copy_(dts[b])
-                    else:
-                        ops.resize_nearest_u8(dts[b], h, w, out=dst)
-                slot.host[:offs[-1]].copy_(slot.dev[:offs[-1]], non_blocking=True)     # one D2H
-                slot.event.record()
-                host = slot.host.numpy()
-                items = [(offs[b], batch.sizes_hw[b], out_paths[i]) for b, i in enumerate(batch.indices)]
-                per = -(-B // n_writers)
-                slot.tasks = [writers.submit(_write_masks, slot.event, host, items[j:j + per]) for j in range(0, B, per)]
-                copied.synchronize()                                                    # the loader may now decode into this staging buffer again
-            for slot in slots:
-                slot.drain()
-        finally:
-            torch.cuda.synchronize(dev)                                                 # nothing in flight on the pinned buffers when they go
-            for slot in slots:
-                for t in slot.tasks:
-                    t.cancel()
+    loader = preprocess.ShapeBucketLoader(p_images, image_size, batch_size, n_decode, window=window, filter="bilinear")
+    with preprocess.WriterRing(loader.pin, n_writers, "zutis-rle", device=dev) as ring, \
+            preprocess.device_batches(loader, dev, preprocess.resize_normalize_of(lut)) as steps:
+        for k, (batch, _, x) in enumerate(steps):
+            B, (oh, ow) = len(batch.paths), batch.out_hw
+            dts = _device_masks_batch(engine, x, bilateral_solver, mean=mean, std=std)
+            offs = np.concatenate(([0], np.cumsum([h * w for h, w in batch.sizes_hw]))).tolist()
+            host, out = ring.take(k % 2, offs[-1])                                      # the writers of batch k - 2 are done with its host buffer
+            for b, (h, w) in enumerate(batch.sizes_hw):                                 # index_dataset.py:214-215
+                dst = out[offs[b]:offs[b + 1]].view(h, w)
+                if (h, w) == (oh, ow):
+                    dst.copy_(dts[b])
+                else:
+                    ops.resize_nearest_u8(dts[b], h, w, out=dst)
+            host.copy_(out, non_blocking=True)                                          # one D2H
+            ring.events[k % 2].record()
+            items, host_np = [(offs[b], batch.sizes_hw[b], out_paths[i]) for b, i in enumerate(batch.indices)], host.numpy()
+            per = -(-B // n_writers)
+            for j in range(0, B, per):
+                ring.submit(k % 2, _write_masks, ring.events[k % 2], host_np, items[j:j + per])
+        ring.drain()
     return out_paths
 
 

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import collections
 import dataclasses
+import functools
 import json
 import math
 import random
@@ -33,7 +34,6 @@ from PIL import Image
 from . import preprocess, rle
 
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # IndexDataset.mean / .std (datasets/index_dataset.py:43)
-MAX_WORKERS = 16
 MAX_SUB = 64                    # sub-images per sample the compose kernel serves (csrc/synth.hip SY_MAX_SUB)
 BLUR_RMAX = 48                  # blur radius the kernel serves (SY_BLUR_RMAX)
 DESC_INTS, WORK_INTS, SAMPLE_INTS = 32, 12, 4
@@ -573,14 +573,17 @@ def synthesize(decoded: Packed, recipes: Sequence[SampleRecipe], mean=MEAN, std=
 
 
 # ------------------------------------------------------------------------------------------------------------------ the loader
-TrainBatch = collections.namedtuple("TrainBatch", "recipes packed")
+class TrainBatch(collections.namedtuple("TrainBatch", "recipes packed")):
+    __slots__ = ()
+    staging = property(lambda self: self.packed.staging)        # what preprocess.device_batches copies to the device
 
 
 class TrainBatchLoader:
     """Batches of training samples from files.  Recipes are drawn on the MAIN thread from one random.Random(seed), so the batches do not
     depend on n_workers; min(n_workers, 16) threads open and decode the images (Pillow releases the GIL) and RLE-decode the masks of the
-    NEXT batch straight into one of two reused (pinned) staging buffers while the caller works on the current one — preprocess.BatchLoader's
-    scheme.  Iterating yields TrainBatch(recipes, packed) for synthesize(); batches() yields synthesize()'s dicts, one host-to-device
+    NEXT batch straight into one of two reused (pinned) staging buffers while the caller works on the current one — the loop and the
+    buffers of every loader (preprocess.prefetch, preprocess.DoubleBuffer).  Iterating yields TrainBatch(recipes, packed) for
+    synthesize(); batches() yields synthesize()'s dicts, one host-to-device
     copy each.  The caller must be done with a batch's staging (its copy complete) before it advances the loader.  `n_batches`: the
     length of one pass (default: ceil(len(p_images) / batch_size), the reference's DataLoader length)."""
 
@@ -589,10 +592,10 @@ class TrainBatchLoader:
         if batch_size < 1:
             raise ValueError("TrainBatchLoader: batch_size must be positive")
         self.fields, self.batch_size, self.seed = dataset_fields, int(batch_size), seed
-        self.n_threads = max(1, min(int(n_workers), MAX_WORKERS))
+        self.n_threads = max(1, min(int(n_workers), preprocess.MAX_THREADS))
         self.n_batches = -(-len(dataset_fields.p_images) // self.batch_size) if n_batches is None else int(n_batches)
         self.pin = torch.cuda.is_available() if pin is None else bool(pin)
-        self._buffers = [torch.empty(0, dtype=torch.uint8), torch.empty(0, dtype=torch.uint8)]
+        self._staging = preprocess.DoubleBuffer(self.pin)
         self._sizes: Dict[str, Tuple[int, int]] = {}
 
     def __len__(self):
@@ -603,19 +606,14 @@ class TrainBatchLoader:
             self._sizes[path] = image_size(path)
         return self._sizes[path]
 
-    def _staging(self, slot: int, nbytes: int) -> torch.Tensor:
-        if self._buffers[slot].numel() < nbytes:
-            self._buffers[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=self.pin)
-        return self._buffers[slot][:nbytes]
-
     @staticmethod
     def _decode(sub: SubRecipe, dst_img, dst_mask, host):
         _place(dst_img, dst_mask, *load_files(sub), sub, host)
 
-    def _submit(self, pool: ThreadPoolExecutor, rng: random.Random, k: int):
+    def _start(self, rng: random.Random, pool: ThreadPoolExecutor, slot: int, k: int):
         recipes = [draw_recipe(rng, self.fields, self._size_of) for _ in range(self.batch_size)]
         head, items, nbytes, (N, B, C, ign, ks, kmax, fill) = _layout(recipes)
-        staging = self._staging(k % 2, head.size * 4 + nbytes)
+        staging = self._staging.take(slot, head.size * 4 + nbytes)
         buf = staging.numpy()
         buf[:head.size * 4] = head.view(np.uint8)
         pix = buf[head.size * 4:]
@@ -625,36 +623,19 @@ class TrainBatchLoader:
         return TrainBatch(recipes, packed), futures
 
     def __iter__(self):
-        if self.n_batches <= 0:
-            return
-        rng = random.Random(self.seed)
-        with ThreadPoolExecutor(max_workers=self.n_threads, thread_name_prefix="zutis-decode") as pool:
-            pending = self._submit(pool, rng, 0)
-            try:
-                for k in range(self.n_batches):
-                    batch, futures = pending
-                    pending = None
-                    for f in futures:
-                        f.result()              # raises what the worker raised
-                    if k + 1 < self.n_batches:
-                        pending = self._submit(pool, rng, k + 1)
-                    yield batch
-            finally:
-                if pending is not None:
-                    for f in pending[1]:
-                        f.cancel()
+        return preprocess.prefetch(range(self.n_batches), functools.partial(self._start, random.Random(self.seed)), self.n_threads)
 
     def batches(self, device=None):
-        """synthesize() of every batch: the dicts IndexDataset.collate_fn returns, on the device."""
+        """synthesize() of every batch: the dicts IndexDataset.collate_fn returns, on the device (`device` is the current one while the
+        generator is open)."""
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        copied = torch.cuda.Event()
-        for batch in self:
-            with torch.cuda.device(dev):
-                staged = batch.packed.staging.to(dev, non_blocking=True)            # descriptors + decoded bytes: one H2D
-                copied.record()
-                out = synthesize(batch.packed._replace(staging=staged), batch.recipes, self.fields.mean, self.fields.std, dev)
-                copied.synchronize()            # the loader may now decode into this staging buffer again
-            yield out
+
+        def transform(batch, staged):
+            return None, synthesize(batch.packed._replace(staging=staged), batch.recipes, self.fields.mean, self.fields.std, dev)
+
+        with preprocess.device_batches(self, dev, transform) as steps:
+            for _, _, out in steps:
+                yield out
 
 
 def dataset_train_batches(self, batch_size: int, n_workers: int = 16, seed: int = 0, n_batches: Optional[int] = None, device=None):
