@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 233 /* 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 234 /* 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -500,6 +500,42 @@ int zh_linear_assignment(const float* costs, const int* inst_off, const int* ski
  * source with gt_u8 is undefined.  gt_u8 may be NULL when every count is 0. */
 int zh_pack_masks_u8(const void* const* src, const int* counts, int B, int elem_size, long HW, unsigned char* gt_u8, int* inst_off,
                      zh_stream_t stream);
+
+/* ---- COCO mask AP, trainer.py:255-292 / coco20k_eval.py:280-308: what pycocotools' COCOeval.evaluate computes for iouType "segm"
+ * (zutis_amd/coco_eval.py; accumulate / summarize stay NumPy float64 on the host: they touch flags and scores only).  A call serves
+ * n_masks masks — detections and ground truths alike — as uncompressed run counts (column-major, the run of zeros first, as the RLE
+ * strings of zutis.py:290,448 decode): counts int32, mask m's runs at run_off[m] .. run_off[m + 1] - 1 (run_off int32 [n_masks + 1]).
+ *
+ * zh_rle_prefix (the area and the running sums behind maskApi's rleArea / rleIou): one wave per mask scans its counts into
+ * run_end int32 (position where run k ends) and run_fg int32 (foreground pixels in front of run k), both laid out as counts, and
+ * area int32 [n_masks].  hw int32 [n_masks] = h * w of each mask: a mask with a negative count, or whose counts do not sum to its
+ * h * w, gets bit (m & 31) of status[m >> 5] (int32 [(n_masks + 31) / 32], zeroed by the caller) and area 0, and no later entry
+ * reads its runs. */
+int zh_rle_prefix(const int* counts, const int* run_off, const int* hw, int n_masks, int* run_end, int* run_fg, int* area, int* status,
+                  zh_stream_t stream);
+/* IoU of every (detection, ground truth) pair of every group in one launch (COCOeval.computeIoU -> maskUtils.iou -> rleIou), one wave
+ * per pair.  groups int32 [n_groups, 8] = {det_off, D, gt_off, G, pair_off, 0, 0, 0}: the group's D detections are the masks
+ * det_mask[det_off ..] (score-descending, cut to the largest max-det by the host), its G ground truths gt_mask[gt_off ..] with
+ * gt_crowd[gt_off ..] (iscrowd), and its D x G results lie row-major at pair_off (= the sum of D * G over the groups in front: ascending;
+ * n_pairs = the total, at most 2^31 - 1).  inter int32 [n_pairs] = pixels in both; iou f64 [n_pairs] = inter / (area_d + area_g - inter),
+ * or inter / area_d against a crowd, 0 when inter is 0 (as rleIou): ONE float64 division of integers, bit for bit NumPy's.  A pair with
+ * a mask that zh_rle_prefix flagged gets inter -1 and iou -1.  A ground truth of up to ZH_RLE_IOU_LDS_RUNS runs is searched in LDS, a
+ * longer one in global memory (zh_rle_iou_lds_runs() = the value the library was built with).  n_pairs = 0 launches nothing. */
+#define ZH_RLE_IOU_LDS_RUNS 1024
+int zh_rle_iou_lds_runs(void);
+int zh_rle_pair_iou(const int* run_end, const int* run_fg, const int* run_off, const int* area, const int* status, const int* groups,
+                    int n_groups, const int* det_mask, const int* gt_mask, const int* gt_crowd, long n_pairs, int* inter, double* iou,
+                    zh_stream_t stream);
+/* COCOeval.evaluateImg for every (group, area range, IoU threshold), one lane each, the T * A <= 64 problems of a group in one wave.
+ * iou / groups / det_mask / area / gt_crowd as above (area is read for the detections only: an unmatched detection whose area lies
+ * outside the range is ignored); n_gt = length of the ground-truth lists; gt_order / gt_ignore int32 [A, n_gt]: per area range the
+ * group's ground truths ignored-last (stable) as indices local to the group, and their ignore flags in that order; thresholds f64 [T];
+ * area_ranges f64 [A, 2].  Outputs, with n_det = length of det_mask: match int32 [n_det, A, T] = the matched ground truth's index in
+ * its group or -1; ignore u8 [n_det, A, T].  workspace >= zh_coco_match_workspace_size bytes (the lanes' matched flags). */
+size_t zh_coco_match_workspace_size(long n_gt, int T, int A);
+int zh_coco_match(const double* iou, const int* groups, int n_groups, const int* det_mask, const int* area, const int* gt_order,
+                  const int* gt_ignore, const int* gt_crowd, long n_gt, const double* thresholds, int T, const double* area_ranges, int A,
+                  int* match, unsigned char* ignore, void* workspace, size_t workspace_bytes, zh_stream_t stream);
 
 /* Native launch plans (zutis_amd/plan.py): replay n recorded calls of the entry points above (op id + 32 argument words
  * each; dispatcher generated from this header) in one C loop; zh_plan_run2 alternates two plans on two streams. */

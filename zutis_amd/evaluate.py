@@ -55,7 +55,7 @@ def evaluate_from_files(network, p_images: Sequence[str], p_gts: Sequence[str], 
                         max_size: Optional[int] = None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), batch_size: int = 4,
                         n_workers: int = 16, window: int = 512, instance: bool = False, image_ids: Optional[Sequence] = None,
                         new_label_id_to_old_label_id: Optional[Dict[int, int]] = None, nms_type: Optional[str] = "hard",
-                        return_labels: bool = False) -> dict:
+                        return_labels: bool = False, coco_annotations=None) -> dict:
     """trainer.evaluate's loop (trainer.py:316-347) from lists of image files and ground-truth PNGs.
 
     network: the drop-in ZUTIS (zutis_amd/dropin/networks/zutis.py) on a GPU, its text embeddings those of the n_categories classes.
@@ -69,6 +69,8 @@ def evaluate_from_files(network, p_images: Sequence[str], p_gts: Sequence[str], 
     (trainer.py:337-345); image_ids: one per image (None: 0, as predict's default).
     Returns {"scores", "cls_iu": RunningScore.get_scores()'s pair, "confusion_matrix": float64 [n, n], "instance_predictions": the
     prediction dicts in input-path order ([] without instance), "labels": {index: int64 [H, W] label map} with return_labels, else None}.
+    coco_annotations (a COCO annotation dict or the path of its JSON) together with instance=True adds "coco_metrics": coco_eval.mask_ap of
+    the instance predictions against it (trainer.py:400-405), over image_ids when they are given (coco20k_eval.py:282).
     A missing or unreadable file and a ground truth of the wrong mode or size are raised here (FileNotFoundError / OSError /
     ValueError); no decoding thread outlives the call and the device stays usable."""
     p_images, p_gts = list(p_images), list(p_gts)
@@ -104,8 +106,12 @@ def evaluate_from_files(network, p_images: Sequence[str], p_gts: Sequence[str], 
             eng.check_finite()                                                         # the forwards' status word: one read for the whole run
     cm = hist.cpu().numpy().reshape(n, n).astype(np.float64)                           # the one crossing of the histogram
     scores, cls_iu = confusion_scores(cm)
-    return {"scores": scores, "cls_iu": cls_iu, "confusion_matrix": cm, "instance_predictions": [p for ps in per_image for p in ps],
-            "labels": labels_out}
+    res = {"scores": scores, "cls_iu": cls_iu, "confusion_matrix": cm, "instance_predictions": [p for ps in per_image for p in ps],
+           "labels": labels_out}
+    if coco_annotations is not None and instance:
+        from . import coco_eval
+        res["coco_metrics"] = coco_eval.mask_ap(coco_annotations, res["instance_predictions"], image_ids=image_ids, device=dev)
+    return res
 
 
 def eval_files_of(dataset):

@@ -169,3 +169,107 @@ def rles_from_transitions(positions: np.ndarray, nruns: np.ndarray, h: int, w: i
     size = [int(h), int(w)]
     o = off.tolist()
     return [({"size": size, "counts": raw[o[i]:o[i + 1]]} if nt[i] <= keep else None) for i in range(n)]
+
+
+def counts_np(counts) -> np.ndarray:
+    """The uncompressed run lengths (int64, the run of zeros first) behind any of the three forms a COCO RLE's "counts" takes: the
+    compressed string as bytes or as str (what json writes and reads back), or the list of an uncompressed RLE.  The string form is
+    decode_np's arithmetic without the pixels: COCO mask AP (zutis_amd/coco_eval.py) works on the runs themselves."""
+    if not isinstance(counts, (bytes, bytearray, str)):
+        return np.asarray(counts, dtype=np.int64).reshape(-1)
+    c = np.frombuffer(counts.encode("ascii") if isinstance(counts, str) else bytes(counts), np.uint8).astype(np.int64) - 48
+    if not c.size:
+        return np.zeros((0,), np.int64)
+    ends = np.flatnonzero((c & 0x20) == 0)
+    if not ends.size or ends[-1] != c.size - 1:
+        raise ValueError("RLE string ends inside a value")
+    starts = np.concatenate(([0], ends[:-1] + 1))
+    nchar = ends - starts + 1
+    if nchar.max() > 12:
+        raise ValueError("RLE string holds a value of more than 12 characters")
+    part = (c & 0x1F) << (5 * (np.arange(c.size) - np.repeat(starts, nchar)))
+    cnts = np.add.reduceat(part, starts)
+    cnts = np.where((c[ends] & 0x10) != 0, cnts | np.left_shift(np.int64(-1), 5 * nchar), cnts)
+    cnts[1::2] = np.cumsum(cnts[1::2])
+    cnts[2::2] = np.cumsum(cnts[2::2])
+    return cnts
+
+
+def _polygon_boundary(xy, h: int, w: int) -> np.ndarray:
+    """rleFrPoly (pycocotools maskApi.c) up to its sort: the column-major positions x * h + y at which one polygon's boundary crosses a
+    pixel column.  xy = [x0, y0, x1, y1, ...] in pixels.  C's (int) truncates toward zero: int() here."""
+    scale = 5.0
+    k = len(xy) // 2
+    x = [int(scale * float(xy[2 * j]) + .5) for j in range(k)]
+    y = [int(scale * float(xy[2 * j + 1]) + .5) for j in range(k)]
+    x.append(x[0])
+    y.append(y[0])
+    u, v = [], []                                   # every integer step along every edge, at 5 x the resolution
+    for j in range(k):
+        xs, xe, ys, ye = x[j], x[j + 1], y[j], y[j + 1]
+        dx, dy = abs(xe - xs), abs(ys - ye)
+        flip = (dx >= dy and xs > xe) or (dx < dy and ys > ye)
+        if flip:
+            xs, xe, ys, ye = xe, xs, ye, ys
+        if dx >= dy:
+            s = (ye - ys) / dx if dx else 0.0       # (dx == dy == 0: C divides 0 by 0 and multiplies the NaN by t = 0 only — one point)
+            for d in range(dx + 1):
+                t = dx - d if flip else d
+                u.append(t + xs)
+                v.append(int(ys + s * t + .5))
+        else:
+            s = (xe - xs) / dy
+            for d in range(dy + 1):
+                t = dy - d if flip else d
+                v.append(t + ys)
+                u.append(int(xs + s * t + .5))
+    out = []
+    for j in range(1, len(u)):                      # where the walk changes column: keep the crossings of pixel-column centres
+        if u[j] == u[j - 1]:
+            continue
+        xd = float(u[j] if u[j] < u[j - 1] else u[j] - 1)
+        xd = (xd + .5) / scale - .5
+        if np.floor(xd) != xd or xd < 0 or xd > w - 1:
+            continue
+        yd = float(v[j] if v[j] < v[j - 1] else v[j - 1])
+        yd = (yd + .5) / scale - .5
+        yd = 0.0 if yd < 0 else (float(h) if yd > h else yd)
+        out.append(int(xd) * h + int(np.ceil(yd)))
+    return np.asarray(out, dtype=np.int64)
+
+
+def _polygon_counts(xy, h: int, w: int) -> np.ndarray:
+    """rleFrPoly's tail: sort the crossings, take differences, and merge what a zero-length run separates."""
+    a = np.sort(np.concatenate((_polygon_boundary(xy, h, w), [h * w])))
+    a = np.diff(np.concatenate(([0], a))).tolist()
+    b, j = [a[0]], 1
+    while j < len(a):
+        if a[j] > 0:
+            b.append(a[j])
+            j += 1
+        else:
+            j += 1
+            if j < len(a):
+                b[-1] += a[j]
+                j += 1
+    return np.asarray(b, dtype=np.int64)
+
+
+def _dense(cnts, h: int, w: int) -> np.ndarray:
+    return np.repeat((np.arange(len(cnts)) & 1).astype(np.uint8), cnts)[:h * w].reshape((h, w), order="F")
+
+
+def from_polygons(polys, h: int, w: int) -> Dict:
+    """COCO RLE dict of the union of polygons [[x0, y0, x1, y1, ...], ...] on an h x w image: pycocotools' annToRLE for a polygon
+    annotation (mask.frPyObjects + mask.merge), its rleFrPoly procedure restated — scale by 5, walk each edge in integer steps, keep
+    the crossings of pixel-column centres, downsample, take differences.  One flat list of numbers is one polygon."""
+    if len(polys) and not isinstance(polys[0], (list, tuple, np.ndarray)):
+        polys = [polys]
+    if len(polys) == 1:
+        cnts = _polygon_counts(polys[0], h, w)
+    else:
+        m = np.zeros((h, w), np.uint8)
+        for p in polys:
+            m |= _dense(_polygon_counts(p, h, w), h, w)
+        cnts = _counts(m) if m.size else np.zeros((0,), np.int64)
+    return {"size": [int(h), int(w)], "counts": _to_string(cnts)}
