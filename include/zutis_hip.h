@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 234 /* 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 235 /* 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -429,6 +429,28 @@ int zh_mask_rle_kept(const int* positions, long packed_capacity, const int* nrun
 int zh_mask_rle_fused_supported(int H, int W, int max_runs);
 int zh_mask_rle_fused_kept(const unsigned char* masks, const unsigned long long* bits, const int* kept_index, const int* kept_count, int B, int Q,
                            int H, int W, int max_runs, unsigned char* out, long out_capacity, int* cursor, int* info, zh_stream_t stream);
+
+/* A picture of the instance predictions, painted behind zh_mask_nms where the masks, the kept list and the decoded image already lie:
+ * what utils/visualiser.py:154-187 (trainer.py:368-372, coco20k_eval.py:271-276) asks detectron2 for, as an id map and / or a colour
+ * overlay.  Masks: bits (u64 [B*Q][(H*W + 63) / 64] as zh_mask_iou_counts leaves them, see zh_mask_rle_fused_kept) when not NULL, else
+ * masks u8 [B,Q,H,W] (non-zero = in the mask); both give the same output.  Slot table exactly as zh_mask_nms writes it, consumed from
+ * that launch with no host visit: index int32 [B,Q] (slot j of image b shows mask index[b,j]), score f64 [B,Q], count int32 [B];
+ * entries past count[b] are never read, a slot whose index is outside [0, Q) is not painted.  colours u8 [B,Q,3], one per SLOT.
+ *   painted slots: j < count[b] with score[b,j] > min_score (float64, strict, as convert_to_instances compares, visualiser.py:139);
+ *   paint rank:    the painted slots by score descending, ties to the lower slot (ordered on the device);
+ *   top(p):        the painted slot of lowest rank whose mask is non-zero at pixel p = y W + x, or none.
+ * ids_out (may be NULL): top(p) + 1, 0 for none — ZH_GT_U8 u8 [B,H,W] (Q <= 255, else ZH_ERR_ARG), ZH_GT_RG16 u8 [B,H,W,3] = (id & 255,
+ * id >> 8, 0), the convention of the label files (zh_upsample_argmax_bytes).  overlay_out (may be NULL; not both) u8 [B,H,W,3]: the
+ * image byte where there is no top; else with c = colours[b, top(p)]: c itself when outline != 0 and a 4-neighbour INSIDE the image has
+ * another top (another slot, or none), otherwise (img * (256 - alpha) + c * alpha + 128) >> 8 per channel, alpha in 0..256 — the integers
+ * of zh_upsample_argmax_bytes.  Pixels without a top are never outline pixels; the image border alone makes no outline.  img: packed +
+ * desc under the contract of zh_upsample_argmax_bytes (NOT checked here; read only with an overlay).  Q <= 1024 (the rank table lives in
+ * LDS).  workspace >= zh_instance_paint_workspace_size bytes, 16-byte aligned: the rank table and a u16 id per pixel for the outline. */
+size_t zh_instance_paint_workspace_size(int B, int Q, int H, int W);
+int zh_instance_paint(const unsigned char* masks, const unsigned long long* bits, const int* index, const double* score, const int* count,
+                      const unsigned char* colours, int alpha, int outline, double min_score, const unsigned char* packed, const int* desc,
+                      unsigned char* ids_out, int id_format, unsigned char* overlay_out, int B, int Q, int H, int W, void* workspace,
+                      size_t workspace_bytes, zh_stream_t stream);
 
 /* ---- Training criterion, criterion.py::Criterion (called by Trainer.fit, trainer.py:105-160).  All fp32; the full-resolution
  * proposals, tokens, logits and their gradients are never written: every full-res value is a bilinear sample (ATen size= form,

@@ -414,6 +414,14 @@ class ZUTIS(nn.Module):
             eng.check_finite()                   # the forward's status word, read behind the synchronisation the label copy just made
             return labels
 
+        return self._predict_instances(dict_outputs, threshold, image_ids, size, label_id_to_category, new_label_id_to_old_label_id,
+                                       temperature, nms_type)[0]
+
+    def _predict_instances(self, dict_outputs, threshold, image_ids, size, label_id_to_category, new_label_id_to_old_label_id, temperature,
+                           nms_type, paint: Optional[dict] = None):
+        """predict(mask_type="instance") -> (predictions, ids).  paint (None: ids is None): the keyword arguments of
+        ZutisEngine.paint_kept — the picture of the kept masks is launched behind the NMS, and ids[i] is prediction i's id in the map."""
+        eng = self._get_engine()
         # instance prediction                                                              # zutis.py:374-470
         mask_proposals: torch.Tensor = dict_outputs["mask_proposals"]
         if len(mask_proposals.shape) == 5:
@@ -444,15 +452,35 @@ class ZUTIS(nn.Module):
             kept = [(bi, int(c), q, float(s)) for bi in range(B)
                     for q, (s, c) in enumerate(zip(confidence_scores[bi], category_ids_h[bi])) if c != 0]
             sel = np.array([bi * Q + q for bi, _, q, _ in kept], dtype=np.int32)
+            slots = None
+            if paint is not None:                       # the slot table is the host-built kept list, uploaded: image bi's j-th entry is slot j
+                table = np.zeros((B, Q, 3), np.float64)
+                count = np.zeros((B,), np.int32)
+                slots = []
+                for bi, c, q, s in kept:
+                    table[bi, count[bi]] = (q, s, c)
+                    slots.append(int(count[bi]))
+                    count[bi] += 1
+                t = torch.from_numpy(table).to(masks_dev.device)
+                eng.paint_kept(masks_dev, t[..., 0].to(torch.int32).contiguous(), t[..., 1].contiguous(), t[..., 2].to(torch.int64).contiguous(),
+                               torch.from_numpy(count).to(masks_dev.device), **paint)
             rles, boxes, areas = eng.encode_masks(masks_dev.view(B * Q, Hm, Wm), sel)
         else:
             assert nms_type in ["hard", "linear", "gaussian"]
-            kept, rles, boxes, areas, status = eng.instance_nms_encode(masks_dev, scores, category_ids, nms_type, range_flag=range_flag)
+            if paint is None:
+                kept, rles, boxes, areas, status = eng.instance_nms_encode(masks_dev, scores, category_ids, nms_type, range_flag=range_flag)
+                slots = None
+            else:
+                kept, rles, boxes, areas, status, slots = eng.instance_nms_encode(masks_dev, scores, category_ids, nms_type,
+                                                                                  range_flag=range_flag, paint=paint)
             raise_on(status)
         predictions: List[dict] = list()
-        for (bi, c, q, s), r, box, area in zip(kept, rles, boxes, areas):
+        ids: Optional[List[int]] = None if slots is None else list()
+        for k, ((bi, c, q, s), r, box, area) in enumerate(zip(kept, rles, boxes, areas)):
             if area == 0:                               # `if m.sum() == 0: continue` (zutis.py:281,439)
                 continue
+            if ids is not None:
+                ids.append(slots[k] + 1)
             label_id = new_label_id_to_old_label_id[c] if new_label_id_to_old_label_id is not None else c
             prediction = {
                 "category_id": label_id,
@@ -465,7 +493,36 @@ class ZUTIS(nn.Module):
             if label_id_to_category is not None:
                 prediction["pred_class"] = label_id_to_category[label_id]
             predictions.append(prediction)
-        return predictions
+        return predictions, ids
+
+    @torch.no_grad()
+    def predict_instances_painted(self, dict_outputs: dict, threshold: float = 0.5, image_ids: Optional[List[int]] = None,
+                                  size: Optional[Tuple[int, int]] = None, label_id_to_category: Optional[Dict[int, str]] = None,
+                                  new_label_id_to_old_label_id: Optional[Dict[int, int]] = None, temperature: float = 5,
+                                  nms_type: str = "hard", *, packed: Optional[torch.Tensor] = None, desc: Optional[torch.Tensor] = None,
+                                  desc_host=None, colours: Optional[torch.Tensor] = None, palette: Optional[torch.Tensor] = None,
+                                  alpha: int = 128, outline: bool = True, min_score: float = 0.0, id_format: str = "u8",
+                                  ids_out: Optional[torch.Tensor] = None, overlay_out: Optional[torch.Tensor] = None):
+        """predict(mask_type="instance") with a picture of what it returns, painted on the device behind the NMS (zh_instance_paint; what
+        utils/visualiser.py:154-187 draws with detectron2): the same predict arguments, and
+          ids_out     None or u8 [B,H,W] (id_format "u8", up to 255 queries) / u8 [B,H,W,3] ("rg16": R = id & 255, G = id >> 8, B = 0) on the
+                      device: per pixel the id of the prediction of highest score (ties: the lower id) among those with score > min_score
+                      that cover it, 0 where none does;
+          overlay_out None or u8 [B,H,W,3] on the device: the decoded images (packed / desc: the views of the batch's staging buffer, as
+                      ZutisEngine.label_bytes takes them; desc_host: the loader's host copy of desc, checked instead of a blocking read)
+                      with every such pixel blended with its prediction's colour — (img * (256 - alpha) + colour * alpha + 128) >> 8 — or,
+                      with outline, in the pure colour where a 4-neighbour belongs to another prediction or to none;
+          colours     u8 [B,Q,3] on the device, one per id (id - 1), or palette u8 [n,3] by the network's category index, or neither: entry
+                      id - 1 of zutis_amd.instance_paint.instance_colours.
+        Not both outputs None.  The launch rides the predict's stream: the buffers are complete once the predict has returned (its one
+        copy of the small results is behind them); no copy and no synchronisation is added.  Returns (predictions, ids): the list
+        predict(mask_type="instance") returns, and per prediction its id in the map (ids are unique per image, not across a batch)."""
+        if ids_out is None and overlay_out is None:
+            raise ValueError("predict_instances_painted: ids_out and overlay_out are both None")
+        paint = dict(packed=packed, desc=desc, desc_host=desc_host, colours=colours, palette=palette, alpha=alpha, outline=outline,
+                     min_score=min_score, id_format=id_format, ids_out=ids_out, overlay_out=overlay_out)
+        return self._predict_instances(dict_outputs, threshold, image_ids, size, label_id_to_category, new_label_id_to_old_label_id,
+                                       temperature, nms_type, paint=paint)
 
     @torch.no_grad()
     def score_semantic(self, dict_outputs: dict, gt_dev: torch.Tensor, metric_meter, size: Optional[Tuple[int, int]] = None,

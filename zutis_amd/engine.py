@@ -429,7 +429,7 @@ class ZutisEngine(_EngineBase):
     def instance_nms_encode(self, masks_u8: torch.Tensor, scores: torch.Tensor, category_ids: torch.Tensor, nms_type: str = "hard",
                             nms_threshold: float = 0.3, sigma: float = 0.5, threshold: float = 0.001,
                             range_flag: Optional[torch.Tensor] = None, max_runs: int = 8192, pack_head: Optional[int] = None,
-                            fused: Optional[bool] = None):
+                            fused: Optional[bool] = None, paint: Optional[dict] = None):
         """instance_nms + encode_masks chained on the device (zutis.py:211-299,423-469): popcount IoU counts, the greedy per-category
         loop, then the run extraction of the kept masks straight from the loop's device outputs (zh_mask_runs_kept) — the NMS result
         does not visit the host in between.  ONE device -> host copy brings the kept triples, every query's category, the counts, the
@@ -438,7 +438,10 @@ class ZutisEngine(_EngineBase):
         Returns (kept [(batch index, category, query index, score)] in the reference's emission order, rles, boxes, areas, status) — status =
         the word behind `range_flag` as the NMS kernel read it (bit ops.STATUS_RANGE: a proposal outside [0, 1]; the engine's own
         status_word() also carries ops.STATUS_NONFINITE from the forward).  fused (None = where supported): runs, boxes, areas and strings
-        from ONE launch (zh_mask_rle_fused_kept) instead of run extraction (two launches) + string kernel; same results."""
+        from ONE launch (zh_mask_rle_fused_kept) instead of run extraction (two launches) + string kernel; same results.
+        paint (the keyword arguments of paint_kept): the picture of the kept masks is launched behind the NMS loop, from its device outputs
+        and the bit-packed masks of the IoU step (zh_instance_paint: no copy, no synchronisation of its own), and the return value gains a
+        sixth entry, slots — per kept entry its position in the kernel's kept list, i.e. its id in the map minus 1."""
         from . import rle
         B, Q, H, W = masks_u8.shape
         dev = masks_u8.device
@@ -460,16 +463,18 @@ class ZutisEngine(_EngineBase):
             packed = small[:n1].view(torch.float64).view(B, 4 * Q + 2)
             info = small[n1:n1 + n2].view(torch.int32).view(B * Q, 8)
             cursor = small[n1 + n2:n1 + n2 + 8].view(torch.int32)    # zeroed by the NMS kernel (zero_word), used by the launch behind it
-            idx, _, _, cnt = ops.mask_nms(inter, uni, scores.contiguous(), category_ids.contiguous(), nms_type, nms_threshold, sigma, threshold,
-                                          packed=packed, range_flag=range_flag, zero_word=cursor)
+            idx, sc, kcat, cnt = ops.mask_nms(inter, uni, scores.contiguous(), category_ids.contiguous(), nms_type, nms_threshold, sigma, threshold,
+                                              packed=packed, range_flag=range_flag, zero_word=cursor)
             ops.mask_rle_fused_kept(m, idx, cnt, max_runs, small[n1 + n2 + 8:], cursor, info, bits=bits)
+            if paint is not None:
+                self.paint_kept(m, idx, sc, kcat, cnt, bits=bits, **paint)
             host = _to_host(small, getattr(self, "_pinned", None))                                   # the one synchronisation of the predict
             pk = host[:n1].view(np.float64).reshape(B, 4 * Q + 2)
             info_h = host[n1:n1 + n2].view(np.int32).reshape(B, Q, 8)
             chars_h = host[n1 + n2 + 8:]
             cnt_l = pk[:, 4 * Q].astype(np.int64).tolist()
             range_bad = int(pk[:, 4 * Q + 1].max()) if range_flag is not None else 0  # the status word as the NMS kernel read it (ops.STATUS_*)
-            kept, rles, boxes, areas = [], [], [], []
+            kept, rles, boxes, areas, slots = [], [], [], [], []
             size = [int(H), int(W)]
             redo = []                                                # (position in the output lists, flat mask index): strings the device did not write
             for b in range(B):
@@ -485,6 +490,7 @@ class ZutisEngine(_EngineBase):
                     if ln < 0:                                       # over max_runs transitions, or the strings outgrew `cap`
                         redo.append((len(kept), b * Q + q))
                     kept.append((b, int(row[2 * Q + j]), q, float(row[Q + j])))
+                    slots.append(j)
                     rles.append({"size": size, "counts": chars_h[c0:c0 + ln].tobytes()} if ln >= 0 else None)
                     boxes.append([float(x0), float(y0), float(x1), float(y1)])
                     areas.append(int(ar))
@@ -492,7 +498,7 @@ class ZutisEngine(_EngineBase):
                 r2, _, _ = ZutisEngine.encode_masks(self, masks_u8.view(B * Q, H, W), np.array([f for _, f in redo], dtype=np.int32))
                 for (at, _), r in zip(redo, r2):
                     rles[at] = r
-            return kept, rles, boxes, areas, range_bad
+            return (kept, rles, boxes, areas, range_bad) if paint is None else (kept, rles, boxes, areas, range_bad, slots)
         # ONE buffer for everything the host needs: [kept triples + categories + count + status (f64) | run counts | boxes + areas | string
         # lengths | the RLE strings of the kept masks, written by the device (zh_mask_rle_kept) from the packed transition list].  The list
         # itself (PACK_HEAD ints per image) stays on the device.
@@ -505,10 +511,12 @@ class ZutisEngine(_EngineBase):
         slen = small[n1 + n2 + n3:n1 + n2 + n3 + n4].view(torch.int32)
         chars = small[n1 + n2 + n3 + n4:]
         pos_head = torch.empty((head,), dtype=torch.int32, device=dev)
-        idx, _, _, cnt = ops.mask_nms(inter, uni, scores.contiguous(), category_ids.contiguous(), nms_type, nms_threshold, sigma, threshold,
-                                      packed=packed, range_flag=range_flag)
+        idx, sc, kcat, cnt = ops.mask_nms(inter, uni, scores.contiguous(), category_ids.contiguous(), nms_type, nms_threshold, sigma, threshold,
+                                          packed=packed, range_flag=range_flag)
         ops.mask_runs_kept(m, idx, cnt, max_runs, pos_head, nr, ba, packed=True)
         ops.mask_rle_kept(pos_head, nr, cnt, B, Q, max_runs, H * W, chars, slen)
+        if paint is not None:
+            self.paint_kept(m, idx, sc, kcat, cnt, bits=bits, **paint)
         host = _to_host(small, getattr(self, "_pinned", None))                                       # the one synchronisation of the predict
         pk = host[:n1].view(np.float64).reshape(B, 4 * Q + 2)
         nr_h = host[n1:n1 + n2].view(np.int32).reshape(B, Q, 2)
@@ -517,7 +525,7 @@ class ZutisEngine(_EngineBase):
         chars_h = host[n1 + n2 + n3 + n4:]
         cnt_l = pk[:, 4 * Q].astype(np.int64).tolist()
         range_bad = int(pk[:, 4 * Q + 1].max()) if range_flag is not None else 0      # the status word as the NMS kernel read it (ops.STATUS_*)
-        kept, rles, boxes, areas = [], [], [], []
+        kept, rles, boxes, areas, slots = [], [], [], [], []
         if B and max(cnt_l) > 0:
             lens = [np.minimum(nr_h[b, :cnt_l[b], 0], max_runs).tolist() for b in range(B)]          # list length of every kept mask
             total = sum(sum(l) for l in lens)
@@ -553,10 +561,32 @@ class ZutisEngine(_EngineBase):
                     if r[j] is None:                                 # pathological mask (> max_runs transitions): the host encoder
                         r[j] = rle.encode(masks_u8[b, q].cpu().numpy())
                     kept.append((b, int(row[2 * Q + j]), q, float(row[Q + j])))
+                    slots.append(j)
                     rles.append(r[j])
                     boxes.append([float(v) for v in ba_l[j][:4]])
                     areas.append(int(ba_l[j][4]))
-        return kept, rles, boxes, areas, range_bad
+        return (kept, rles, boxes, areas, range_bad) if paint is None else (kept, rles, boxes, areas, range_bad, slots)
+
+    def paint_kept(self, masks_u8: torch.Tensor, index: torch.Tensor, score: torch.Tensor, category: torch.Tensor, count: torch.Tensor, *,
+                   bits: Optional[torch.Tensor] = None, packed=None, desc=None, desc_host=None, colours=None, palette=None, alpha: int = 128,
+                   outline: bool = True, min_score: float = 0.0, id_format: str = "u8", ids_out=None, overlay_out=None):
+        """The picture of a kept list (ops.instance_paint) on the current stream: index / score / category / count as zh_mask_nms writes
+        them ([B,Q] int32 / f64 / int64, [B] int32), on the device.  The colour of slot j of image b: colours[b, j] (u8 [B,Q,3]), or
+        palette[category[b, j]] (palette u8 [n,3] by the network's category index; gathered on the device), or — both None — entry j of
+        instance_paint.instance_colours.  ids_out / overlay_out: the caller's device buffers (ops.instance_paint's shapes)."""
+        B, Q, H, W = masks_u8.shape
+        if overlay_out is not None and colours is None:
+            if palette is not None:
+                colours = palette[category.clamp(0, palette.shape[0] - 1)].contiguous()      # entries past count are not read by the kernel
+            else:
+                from .instance_paint import instance_colours
+                key = (Q, str(masks_u8.device))
+                if getattr(self, "_slot_colours", (None,))[0] != key:
+                    self._slot_colours = (key, torch.from_numpy(instance_colours(Q)).to(masks_u8.device))
+                colours = self._slot_colours[1].unsqueeze(0).expand(B, Q, 3).contiguous()
+        return ops.instance_paint(index, score, count, H, W, masks=masks_u8, bits=bits, colours=colours, alpha=alpha, outline=outline,
+                                  min_score=min_score, packed=packed, desc=desc, desc_host=desc_host, id_format=id_format, ids_out=ids_out,
+                                  overlay_out=overlay_out)
 
     # ints of the packed transition list that ride along with the small tables, per image (256 KB; a quarter of it per image in batches
     # above 4): the 17 kept masks of the config-3 fixture (480x640, noisy: ~1750 transitions each) are 29.8 k

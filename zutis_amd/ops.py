@@ -574,8 +574,78 @@ def mask_rle_fused_kept(masks_u8, kept_index, kept_count, max_runs, out, cursor,
           _p(out), out.numel(), _p(cursor), _p(info), _stream())
 
 
+PAINT_MAX_Q = 1024      # zh_instance_paint: slots per image (its rank table lives in LDS)
+
+
+def instance_paint_workspace_size(B, Q, H, W) -> int:
+    return int(_lib.load(raw=True).zh_instance_paint_workspace_size(int(B), int(Q), int(H), int(W)))
+
+
+def instance_paint(index, score, count, H, W, *, masks=None, bits=None, colours=None, alpha: int = 128, outline: bool = True,
+                   min_score: float = 0.0, packed=None, desc=None, desc_host=None, id_format: str = "u8", ids_out=None, overlay_out=None,
+                   workspace=None):
+    """A picture of the kept instances (include/zutis_hip.h zh_instance_paint): index int32 [B,Q] / score f64 [B,Q] / count int32 [B] =
+    mask_nms' outputs, read on the device; masks u8 [B,Q,H,W] or bits int64 [B,Q,(H*W + 63) // 64] (mask_iou_counts' workspace; read
+    instead of the bytes when given).  ids_out None or u8 [B,H,W] ("u8", Q <= 255) / u8 [B,H,W,3] ("rg16"): slot + 1 of the painted slot
+    (score > min_score) of highest score that covers the pixel, 0 for none; overlay_out None or u8 [B,H,W,3]: colours u8 [B,Q,3] (one per
+    slot) blended over the decoded images of a loader's staging buffer (packed / desc as upsample_argmax_bytes takes and checks them,
+    on desc_host when given) with alpha in 0..256, outline pixels in the pure colour.  Not both None.  Returns (ids_out, overlay_out)."""
+    _chk(index, torch.int32, "instance_paint index"); _chk(score, torch.float64, "instance_paint score"); _chk(count, torch.int32, "instance_paint count")
+    if index.dim() != 2 or tuple(score.shape) != tuple(index.shape) or tuple(count.shape) != (index.shape[0],):
+        raise _lib.ZutisHipError(f"instance_paint: index [B,Q], score [B,Q], count [B] expected, got {tuple(index.shape)}, {tuple(score.shape)}, "
+                                 f"{tuple(count.shape)}")
+    (B, Q), H, W = index.shape, int(H), int(W)
+    if id_format not in GT_FORMATS:
+        raise _lib.ZutisHipError(f"instance_paint: id_format {id_format!r} is not one of {sorted(GT_FORMATS)}")
+    if B < 1 or Q < 1 or H < 1 or W < 1:
+        raise _lib.ZutisHipError(f"instance_paint: B, Q, H, W must be positive, got {(B, Q, H, W)}")
+    if masks is None and bits is None:
+        raise _lib.ZutisHipError("instance_paint: masks and bits are both None")
+    if ids_out is None and overlay_out is None:
+        raise _lib.ZutisHipError("instance_paint: ids_out and overlay_out are both None")
+    if bits is not None:
+        _chk(bits, torch.int64, "instance_paint bits")
+        if bits.numel() != B * Q * ((H * W + 63) // 64):
+            raise _lib.ZutisHipError(f"instance_paint: bits holds {bits.numel()} words, {B * Q * ((H * W + 63) // 64)} expected")
+        masks = None
+    else:
+        _chk(masks, torch.uint8, "instance_paint masks")
+        if tuple(masks.shape) != (B, Q, H, W):
+            raise _lib.ZutisHipError(f"instance_paint: masks {tuple(masks.shape)}, expected {(B, Q, H, W)}")
+    if ids_out is not None:
+        _chk(ids_out, torch.uint8, "instance_paint ids_out")
+        want = (B, H, W) if id_format == "u8" else (B, H, W, 3)
+        if tuple(ids_out.shape) != want:
+            raise _lib.ZutisHipError(f"instance_paint: ids_out {tuple(ids_out.shape)}, expected {want}")
+    if overlay_out is not None:
+        if packed is None or desc is None or colours is None:
+            raise _lib.ZutisHipError("instance_paint: an overlay needs packed, desc and colours")
+        _chk(overlay_out, torch.uint8, "instance_paint overlay_out"); _chk(packed, torch.uint8, "instance_paint packed")
+        _chk(desc, torch.int32, "instance_paint desc"); _chk(colours, torch.uint8, "instance_paint colours")
+        if tuple(overlay_out.shape) != (B, H, W, 3) or packed.dim() != 1 or tuple(desc.shape) != (B, 8) or tuple(colours.shape) != (B, Q, 3):
+            raise _lib.ZutisHipError(f"instance_paint: overlay_out {(B, H, W, 3)}, packed [bytes], desc {(B, 8)}, colours {(B, Q, 3)} expected, got "
+                                     f"{tuple(overlay_out.shape)}, {tuple(packed.shape)}, {tuple(desc.shape)}, {tuple(colours.shape)}")
+        if int(alpha) != alpha or not 0 <= int(alpha) <= 256:
+            raise _lib.ZutisHipError(f"instance_paint: alpha {alpha!r} is not an integer in 0..256")
+        rows = (desc if desc_host is None else desc_host).cpu().numpy().reshape(B, 8)
+        for b, (off, iw, ih) in enumerate(rows[:, :3].tolist()):
+            if (iw, ih) != (W, H):
+                raise _lib.ZutisHipError(f"instance_paint: descriptor row {b} holds a {iw} x {ih} image, the overlay is {W} x {H}")
+            if off < 0 or off * 16 + 3 * W * H > packed.numel():
+                raise _lib.ZutisHipError(f"instance_paint: descriptor row {b} places its image outside packed ({packed.numel()} bytes)")
+    else:
+        packed = desc = colours = None
+    need = instance_paint_workspace_size(B, Q, H, W)
+    ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=index.device)
+    if _nbytes(ws) < need:
+        raise _lib.ZutisHipError(f"instance_paint: workspace holds {_nbytes(ws)} bytes, {need} needed")
+    _call("zh_instance_paint", _p(masks), _p(bits), _p(index), _p(score), _p(count), _p(colours), int(alpha), int(bool(outline)), float(min_score),
+          _p(packed), _p(desc), _p(ids_out), GT_FORMATS[id_format], _p(overlay_out), B, Q, H, W, _p(ws), need, _stream())
+    return ids_out, overlay_out
+
+
 # ---------------------------------------------------------------------------------------- CLIP image pre-processing
-RCN_KMAX = 152      # include/zutis_hip.h ZH_RCN_KMAX
+RCN_KMAX = 152     # include/zutis_hip.h ZH_RCN_KMAX
 
 
 def resize_crop_normalize(packed, desc, n_px: int, lut, out=None, kmax: Optional[int] = None):

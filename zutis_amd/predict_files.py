@@ -100,6 +100,45 @@ def resolve_output_paths(p_images: Sequence[str], out_dir: Optional[str], out_pa
     return labels, overlays
 
 
+def resolve_instance_paths(p_images: Sequence[str], label_paths: Sequence[str], written: Sequence[Optional[Sequence[str]]], instance_map: bool,
+                           instance_overlay: bool):
+    """(id-map paths or None, instance-overlay paths or None): {stem of the label map}_instances.png and {stem}_instances_overlay.png beside
+    where image i's label map goes (or would go: label_paths, resolve_output_paths' first result).  They take part in the
+    one-path-one-output check together with `written`, the lists of files the call writes besides them (None entries are skipped)."""
+    maps = [os.path.splitext(p)[0] + "_instances.png" for p in label_paths] if instance_map else None
+    overlays = [os.path.splitext(p)[0] + "_instances_overlay.png" for p in label_paths] if instance_overlay else None
+    seen = {}
+    for paths in list(written) + [maps, overlays]:
+        for i, p in enumerate(paths or []):
+            key = os.path.normpath(os.path.abspath(p))
+            if key in seen:
+                raise ValueError(f"predict_from_files: {p_images[seen[key]]} and {p_images[i]} map to one output path, {p}")
+            seen[key] = i
+    return maps, overlays
+
+
+def _validate_instance_pictures(instance: bool, instance_map: bool, instance_overlay: bool, instance_colours, instance_min_score, palette, n: int):
+    """The instance_* arguments of predict_from_files, before any work -> (colour mode, u8 colour table or None)."""
+    if not (instance_map or instance_overlay):
+        return None, None
+    if not instance:
+        raise ValueError("predict_from_files: instance_map / instance_overlay picture the instance predictions: they need instance=True")
+    if isinstance(instance_min_score, bool) or not isinstance(instance_min_score, (int, float, np.integer, np.floating)) or instance_min_score != instance_min_score:
+        raise ValueError(f"predict_from_files: instance_min_score {instance_min_score!r} is not a number")
+    if isinstance(instance_colours, str):
+        if instance_colours not in ("category", "instance"):
+            raise ValueError(f"predict_from_files: instance_colours {instance_colours!r} is not \"category\", \"instance\" or an array [queries, 3]")
+        if instance_colours == "category":
+            if palette is None:
+                raise ValueError("predict_from_files: instance_colours=\"category\" needs a palette (indexed by the network's category index)")
+            return "category", normalise_palette(palette, n)
+        return "instance", None
+    a = np.asarray(instance_colours)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 1:
+        raise ValueError(f"predict_from_files: instance_colours as an array is [queries, 3] (one colour per id), got {a.shape}")
+    return "array", normalise_palette(a, a.shape[0])
+
+
 def predictions_json_form(predictions: Sequence[dict]) -> List[dict]:
     """What trainer.py:393-398 dumps: every prediction without its "bbox", the RLE "counts" as a str; new dicts, the given ones stay whole."""
     out = []
@@ -168,7 +207,8 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
                        n_workers: int = 16, window: int = 512, compress_level: int = 1, instance: bool = False,
                        image_ids: Optional[Sequence] = None, new_label_id_to_old_label_id: Optional[Dict[int, int]] = None,
                        label_id_to_category: Optional[Dict[int, str]] = None, nms_type: Optional[str] = "hard",
-                       predictions_json: Optional[str] = None) -> dict:
+                       predictions_json: Optional[str] = None, instance_map: bool = False, instance_overlay: bool = False,
+                       instance_colours="instance", instance_min_score: float = 0.0, instance_outline: bool = True) -> dict:
     """The segmenter over a list of image files: label PNGs (and overlays) on disk, and / or the instance predictions.
 
     network: the drop-in ZUTIS (zutis_amd/dropin/networks/zutis.py) on a GPU; its text embeddings are the n categories.
@@ -187,6 +227,17 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     instance=True: predict(mask_type="instance", size=(H, W), ...) per batch as coco20k_eval.py:258-265 calls it; image_ids: one per
     image (None: 0, predict's default).  predictions_json: a path that receives what trainer.py:393-398 writes — the dicts without
     "bbox", RLE counts as str, in input-path order.
+    instance_map / instance_overlay (need instance=True): a picture of the instance predictions per image, painted on the device behind
+    the NMS (zh_instance_paint; what utils/visualiser.py:154-187 draws with detectron2) — {stem}_instances.png: per pixel the id of the
+    prediction of highest score (ties: the lower id) among those with score > instance_min_score that cover it, 0 where none does, mode L
+    (the byte is the id), or RGB (R = id & 255, G = id >> 8, B = 0) when the network has more than 255 queries;
+    {stem}_instances_overlay.png: mode RGB, the image with every such pixel blended with its prediction's colour (alpha, as the semantic
+    overlay) and, with instance_outline, in the pure colour where a 4-neighbour belongs to another prediction or to none.  Both sit beside
+    where the label map goes or would go (out_dir / out_paths are accepted without semantic=True) and take part in the one-path check.
+    instance_colours: "instance" (entry id - 1 of instance_paint.instance_colours), "category" (palette[the network's category index], needs
+    the palette), or an array [>= queries, 3] with one colour per id.  The bytes share the batch's device buffer, its one copy back and the
+    writer slot with the semantic outputs.  The result gains "instance_map_paths", "instance_overlay_paths" and "instance_ids": parallel to
+    "instance_predictions", the id of each prediction in its image's map.
     Returns {"label_paths": [...] | None, "overlay_paths": [...] | None, "instance_predictions": the dicts predict gave (with "bbox"),
     in input-path order, "n_images": int}.
     A missing or unreadable image (FileNotFoundError / OSError / ValueError) and a directory or file that cannot be written (OSError)
@@ -195,62 +246,104 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     _require_dropin(network, "predict_from_files")
     n = int(network.text_embeddings.shape[0])
     pal = _validate(n, len(p_images), semantic, instance, label_format, palette, overlay, alpha, image_ids, compress_level)
-    label_paths = overlay_paths = None
-    if semantic:
-        label_paths, overlay_paths = resolve_output_paths(p_images, out_dir, out_paths, overlay)
-        for d in sorted({os.path.dirname(p) or "." for p in label_paths}):
+    colour_mode, colour_table = _validate_instance_pictures(instance, instance_map, instance_overlay, instance_colours, instance_min_score, palette, n)
+    paint = colour_mode is not None
+    label_paths = overlay_paths = map_paths = iovl_paths = None
+    if semantic or paint:
+        would_be, overlay_paths = resolve_output_paths(p_images, out_dir, out_paths, overlay)
+        label_paths = would_be if semantic else None
+        if paint:
+            map_paths, iovl_paths = resolve_instance_paths(p_images, would_be, [label_paths, overlay_paths], instance_map, instance_overlay)
+        for d in sorted({os.path.dirname(p) or "." for paths in (label_paths, map_paths, iovl_paths) for p in (paths or [])}):
             os.makedirs(d, exist_ok=True)
     elif out_dir is not None and out_paths is not None:
         raise ValueError("predict_from_files: give exactly one of out_dir and out_paths")
     per_image: List[List[dict]] = [[] for _ in p_images]
+    per_image_ids: List[List[int]] = [[] for _ in p_images]
     if p_images:
         eng = network._get_engine()
         dev = eng._device()
-        n_decode, n_write = thread_split(n_workers, semantic)
+        n_decode, n_write = thread_split(n_workers, semantic or paint)
         ch = LABEL_CHANNELS[label_format]
         mode = "RGB" if label_format == "rg16" else ("P" if pal is not None else "L")
         pal_bytes = pal.tobytes() if mode == "P" else None
         lut = torch.from_numpy(preprocess.normalise_table(mean, std)).to(dev)
         pal_dev = torch.from_numpy(pal).to(dev) if (overlay and pal is not None) else None
+        colour_dev = torch.from_numpy(colour_table).to(dev) if colour_table is not None else None
         loader = preprocess.PredictBatchLoader(p_images, max_size, batch_size, n_decode, window=window)
-        waiting = None                                                                     # (slot, host bytes, indices, (H, W)) of the batch whose copy back is in flight
+        waiting = None                                                                     # (slot, host bytes, indices, (H, W), parts) of the batch whose copy back is in flight
 
-        def hand_to_writers(slot, host, indices, H, W):
+        def hand_to_writers(slot, host, indices, H, W, parts):
             ring.events[slot].synchronize()                                                # the bytes are in the pinned buffer
             a = host.numpy()
             B = len(indices)
-            lab = a[:B * H * W * ch].reshape((B, H, W) if ch == 1 else (B, H, W, ch))
-            ovl = a[B * H * W * ch:].reshape(B, H, W, 3) if overlay else None
-            for b, i in enumerate(indices):
-                ring.submit(slot, _write_png, label_paths[i], lab[b], mode, pal_bytes, int(compress_level))
-                if overlay:
-                    ring.submit(slot, _write_png, overlay_paths[i], ovl[b], "RGB", None, int(compress_level))
+            at = 0
+            for paths, c, md, pb in parts:                                                 # the byte ranges of the buffer, in the order they were laid out
+                view = a[at:at + B * H * W * c].reshape((B, H, W) if c == 1 else (B, H, W, c))
+                at += B * H * W * c
+                for b, i in enumerate(indices):
+                    ring.submit(slot, _write_png, paths[i], view[b], md, pb, int(compress_level))
+
+        def copy_back(slot, host, dev_out, batch, H, W, parts):
+            nonlocal waiting
+            host.copy_(dev_out, non_blocking=True)                                         # labels + overlay + instance pictures: one D2H
+            ring.events[slot].record()
+            if waiting is not None:
+                hand_to_writers(*waiting)                                                  # batch k - 1 is encoded while batch k is on the device
+            waiting = (slot, host, list(batch.indices), H, W, parts)
 
         with preprocess.WriterRing(loader.pin, n_write, "zutis-write") as ring, \
                 preprocess.device_batches(loader, dev, preprocess.resize_normalize_of(lut)) as steps:
             for k, (batch, (packed, desc), x) in enumerate(steps):
                 B, (H, W) = len(batch.paths), batch.size_hw
-                if overlay and batch.n_host:
+                if (overlay or instance_overlay) and batch.n_host:
                     raise NotImplementedError(f"predict_from_files: {batch.host_paths[0]} was resized on the host (a side more than 75 times its "
                                               f"target): its decoded image is not on the device at file size, no overlay can be made")
                 out = network(x)                                                           # the module's forward: its hipGraph replay applies
-                if semantic:
+                if semantic or paint:
                     slot = k % 2
-                    nl = B * H * W * ch
-                    host, _ = ring.take(slot, nl + (3 * B * H * W if overlay else 0))      # waits for the writers of batch k - 2
+                    nl = B * H * W * ch if semantic else 0
+                    no = 3 * B * H * W if overlay else 0
+                    parts = ([(label_paths, ch, mode, pal_bytes)] if semantic else []) + ([(overlay_paths, 3, "RGB", None)] if overlay else [])
+                    nm = ni = 0
+                    if paint:
+                        Q = int(out["mask_proposals"].shape[-3])
+                        id_format = "u8" if Q <= 255 else "rg16"
+                        nm = B * H * W * LABEL_CHANNELS[id_format] if instance_map else 0
+                        ni = 3 * B * H * W if instance_overlay else 0
+                        parts += ([(map_paths, LABEL_CHANNELS[id_format], "L" if id_format == "u8" else "RGB", None)] if instance_map else []) + \
+                                 ([(iovl_paths, 3, "RGB", None)] if instance_overlay else [])
+                    host, _ = ring.take(slot, nl + no + nm + ni)                           # waits for the writers of batch k - 2
                     dev_out = torch.empty((host.numel(),), dtype=torch.uint8, device=dev)
-                    eng.label_bytes(out["patch_tokens"], network.text_embeddings, (H, W), label_format=label_format,
-                                    labels_out=dev_out[:nl].view((B, H, W) if ch == 1 else (B, H, W, ch)), palette=pal_dev,
-                                    packed=packed if overlay else None, desc=desc if overlay else None, alpha=int(alpha),
-                                    overlay_out=dev_out[nl:].view(B, H, W, 3) if overlay else None, desc_host=batch.desc)
-                    host.copy_(dev_out, non_blocking=True)                                 # labels + overlay: one D2H
-                    ring.events[slot].record()
-                    if waiting is not None:
-                        hand_to_writers(*waiting)                                          # batch k - 1 is encoded while batch k is on the device
-                    waiting = (slot, host, list(batch.indices), H, W)
-                if instance:
+                    if semantic:
+                        eng.label_bytes(out["patch_tokens"], network.text_embeddings, (H, W), label_format=label_format,
+                                        labels_out=dev_out[:nl].view((B, H, W) if ch == 1 else (B, H, W, ch)), palette=pal_dev,
+                                        packed=packed if overlay else None, desc=desc if overlay else None, alpha=int(alpha),
+                                        overlay_out=dev_out[nl:nl + no].view(B, H, W, 3) if overlay else None, desc_host=batch.desc)
+                    if not paint:
+                        copy_back(slot, host, dev_out, batch, H, W, parts)
+                if instance and not paint:
                     collect_instance_predictions(network, out, batch, image_ids, per_image, label_id_to_category=label_id_to_category,
                                                  new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type)
+                elif instance:
+                    if colour_mode == "array" and colour_table.shape[0] < Q:
+                        raise ValueError(f"predict_from_files: instance_colours holds {colour_table.shape[0]} colours, the network has {Q} queries")
+                    # the paint rides the predict's stream behind the NMS: the pictures are complete when the predict returns, and go back
+                    # with the semantic bytes of the batch in the one copy behind it
+                    preds, ids = network.predict_instances_painted(
+                        out, size=batch.size_hw, image_ids=list(batch.indices), label_id_to_category=label_id_to_category,
+                        new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type, packed=packed, desc=desc, desc_host=batch.desc,
+                        colours=colour_dev[:Q].unsqueeze(0).expand(B, Q, 3).contiguous() if colour_mode == "array" else None,
+                        palette=colour_dev if colour_mode == "category" else None, alpha=int(alpha), outline=bool(instance_outline),
+                        min_score=float(instance_min_score), id_format=id_format,
+                        ids_out=dev_out[nl + no:nl + no + nm].view((B, H, W) if id_format == "u8" else (B, H, W, 3)) if instance_map else None,
+                        overlay_out=dev_out[nl + no + nm:].view(B, H, W, 3) if instance_overlay else None)
+                    for p, pid in zip(preds, ids):
+                        i = p["image_id"]
+                        p["image_id"] = image_ids[i] if image_ids is not None else 0
+                        per_image[i].append(p)
+                        per_image_ids[i].append(pid)
+                    copy_back(slot, host, dev_out, batch, H, W, parts)
             if waiting is not None:
                 hand_to_writers(*waiting)
             ring.drain()
@@ -262,7 +355,10 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
             os.makedirs(d, exist_ok=True)
         with open(predictions_json, "w") as f:
             json.dump(predictions_json_form(predictions), f, default=_jsonable)
-    return {"label_paths": label_paths, "overlay_paths": overlay_paths, "instance_predictions": predictions, "n_images": len(p_images)}
+    result = {"label_paths": label_paths, "overlay_paths": overlay_paths, "instance_predictions": predictions, "n_images": len(p_images)}
+    if paint:
+        result.update(instance_map_paths=map_paths, instance_overlay_paths=iovl_paths, instance_ids=[i for ids in per_image_ids for i in ids])
+    return result
 
 
 def predict_files_of(dataset):
