@@ -47,13 +47,18 @@ def _put_pair(view, x32, x3):
     return x32.to(f16).double()                 # fp16 operands: the reference starts from the rounded values
 
 
-def attn_case(dev, *, x3, dh, heads, B, Tq, Tk, layout, split_o=None, causal=False, ksplit=1, scale=None, seed=0, expect_error=False):
+def attn_case(dev, *, x3, dh, heads, B, Tq, Tk, layout, split_o=None, causal=False, ksplit=1, scale=None, seed=0, expect_error=False,
+              inputs=None):
+    """inputs = (q32, k32, v32): float32 [B, Tq, D], [B, Tk, D], [B, Tk, D] instead of the seeded randn draws (tests/_attention_case.py)."""
     from zutis_amd import _lib, ops
     D = heads * dh
     planes = 2 if x3 else 1
     split_o = x3 if split_o is None else split_o
     qs = 2.5 if x3 else 1.0                     # the input scales of test_attention_x3_scores / test_attention
     q32, k32, v32 = _randn((B, Tq, D), seed + 1, qs), _randn((B, Tk, D), seed + 2, qs), _randn((B, Tk, D), seed + 3)
+    if inputs is not None:
+        q32, k32, v32 = (t.detach().cpu().to(f32) for t in inputs)
+        assert q32.shape == (B, Tq, D) and k32.shape == (B, Tk, D) and v32.shape == (B, Tk, D)
     ia = Arena(IN_FILL, dev)
     kt = _kt(x3)
     if layout == "packed":
