@@ -490,21 +490,21 @@ def test_retrieval_vs_oracle(dev):
 def test_mask_runs_device_rle_matches_host_encoder(dev):
     """Device run extraction + box + area == host RLE encoder / numpy box for random, empty, full and striped masks."""
     from zutis_amd import ops, rle
-    from zutis_amd.engine import ZutisEngine
+    from zutis_amd import instances
     rng = np.random.default_rng(1)
     H, W = 77, 145
     masks = (rng.random((7, H, W)) > 0.6).astype(np.uint8)
     masks[1] = 0; masks[2] = 1; masks[3] = 0; masks[3][10:30, 64:66] = 1; masks[4] = 0; masks[4][0, 0] = 1; masks[5][:, ::2] = 1
     dm = torch.from_numpy(masks).to(dev)
     sel = np.array([6, 0, 1, 2, 3, 4, 5], np.int32)
-    rles, boxes, areas = ZutisEngine.encode_masks(None, dm, sel, max_runs=20000)
+    rles, boxes, areas = instances.encode_masks(dm, sel, max_runs=20000)
     for j, q in enumerate(sel):
         m = masks[q]
         assert areas[j] == int(m.sum())
         assert rles[j] == rle.encode(m)
         if m.any():
             assert boxes[j] == rle.mask_to_box(m)
-    rles2, _, _ = ZutisEngine.encode_masks(None, dm, np.array([0], np.int32), max_runs=16)     # overflow -> host fallback
+    rles2, _, _ = instances.encode_masks(dm, np.array([0], np.int32), max_runs=16)     # overflow -> host fallback
     assert rles2[0] == rle.encode(masks[0])
 
 
@@ -514,7 +514,7 @@ def test_mask_runs_panel_blocks_at_evaluation_sizes(dev, H, W):
     16-byte load path), a tall narrow, a 3-row and a one-panel mask: RLE strings, boxes and areas equal the host encoder's;
     masks whose runs straddle every panel boundary (horizontal stripes) and empty / full masks included."""
     from zutis_amd import rle
-    from zutis_amd.engine import ZutisEngine
+    from zutis_amd import instances
     rng = np.random.default_rng(H * 1000 + W)
     yy, xx = np.mgrid[:H, :W]
     masks = []
@@ -526,7 +526,7 @@ def test_mask_runs_panel_blocks_at_evaluation_sizes(dev, H, W):
     m8 = np.stack(masks).astype(np.uint8)
     dm = torch.from_numpy(m8).to(dev)
     sel = np.arange(len(masks), dtype=np.int32)[::-1].copy()
-    rles, boxes, areas = ZutisEngine.encode_masks(None, dm, sel, max_runs=H * W + 1)
+    rles, boxes, areas = instances.encode_masks(dm, sel, max_runs=H * W + 1)
     for j, q in enumerate(sel):
         assert areas[j] == int(m8[q].sum()), (q, areas[j])
         assert rles[j] == rle.encode(m8[q]), q
@@ -557,7 +557,7 @@ def test_retrieval_shard_merge_equals_unsharded(dev):
 def test_device_rle_matches_hand_derived_vectors(dev, golden_dir):
     """Device run extraction (zh_mask_runs) + string packing reproduce the hand-derived COCO RLE vectors."""
     import json
-    from zutis_amd.engine import ZutisEngine
+    from zutis_amd import instances
     vecs = json.load(open(f"{golden_dir}/rle_vectors.json"))["vectors"]
     for v in vecs:
         h, w = v["size"]
@@ -566,7 +566,7 @@ def test_device_rle_matches_hand_derived_vectors(dev, golden_dir):
         for r in v["runs_colmajor"]:
             flat[pos:pos + r] = val; pos += r; val ^= 1
         m = flat.reshape((h, w), order="F")
-        rles, boxes, areas = ZutisEngine.encode_masks(None, torch.from_numpy(np.ascontiguousarray(m[None])).to(dev), np.array([0], np.int32))
+        rles, boxes, areas = instances.encode_masks(torch.from_numpy(np.ascontiguousarray(m[None])).to(dev), np.array([0], np.int32))
         assert rles[0]["counts"] == v["counts"].encode("ascii") and rles[0]["size"] == v["size"], v["name"]
         assert areas[0] == int(m.sum())
 
@@ -578,7 +578,7 @@ def test_device_mask_nms_matches_reference_control_flow(dev, nms_type, Q):
     (zutis.py:211-299) on random overlapping masks: same (category, query) emission order; scores equal (hard: exactly —
     only x1 / x0 products; linear / gaussian: float64 arithmetic, 1e-12)."""
     from zutis_amd import ops
-    from zutis_amd.engine import ZutisEngine
+    from zutis_amd import instances
     from oracle import zutis_ref as O
     rng = np.random.default_rng(5)
     B, H, W = 3, 48, 64
@@ -599,8 +599,7 @@ def test_device_mask_nms_matches_reference_control_flow(dev, nms_type, Q):
     # set(category_ids) (zutis.py:237-238), which is NOT ascending here — [40, 33, 2, 3] for {33, 2, 40, 3}
     cats[2] = np.array([33, 2, 40, 3, 80, 65], np.int64)[rng.integers(0, 6, Q)]
     assert [int(c) for c in set(cats[2])] != sorted(set(int(c) for c in cats[2]))
-    eng_kept = ZutisEngine.instance_nms(None, torch.from_numpy(masks).to(dev), torch.from_numpy(scores).to(dev),
-                                        torch.from_numpy(cats).to(dev), nms_type)
+    eng_kept = instances.nms(torch.from_numpy(masks).to(dev), torch.from_numpy(scores).to(dev), torch.from_numpy(cats).to(dev), nms_type)
     ref = []
     for b in range(B):
         ref += [(b, c, q, s) for (c, q, s) in O.mask_nms(masks[b].astype(bool), scores[b], cats[b], nms_type)]
@@ -615,19 +614,50 @@ def test_device_mask_nms_matches_reference_control_flow(dev, nms_type, Q):
     # same kept list, and RLE / boxes / areas identical to the two-step path (instance_nms -> host -> encode_masks)
     md = torch.from_numpy(masks).to(dev)
     flag = torch.zeros((1,), dtype=torch.int32, device=dev)
-    kept2, rles2, boxes2, areas2, bad = ZutisEngine.instance_nms_encode(None, md, torch.from_numpy(scores).to(dev), torch.from_numpy(cats).to(dev),
-                                                                        nms_type, range_flag=flag)
+    kept2, rles2, boxes2, areas2, bad, _ = instances.nms_encode(md, torch.from_numpy(scores).to(dev), torch.from_numpy(cats).to(dev), nms_type,
+                                                                range_flag=flag)
     assert not bad and kept2 == eng_kept
     sel = np.array([b * Q + q for b, _, q, _ in eng_kept], dtype=np.int32)
-    rles1, boxes1, areas1 = ZutisEngine.encode_masks(None, md.view(B * Q, H, W), sel)
+    rles1, boxes1, areas1 = instances.encode_masks(md.view(B * Q, H, W), sel)
     assert rles2 == rles1 and boxes2 == boxes1 and areas2 == areas1
     # the kept masks' run positions ride along with the small tables as ONE packed list: a head too short for them (second copy of the
     # whole list) and a run capacity below some masks' transitions (those are re-encoded from the mask) give the same strings
     for kw in (dict(pack_head=8), dict(max_runs=3), dict(max_runs=3, pack_head=8), dict(fused=False), dict(fused=False, pack_head=8),
                dict(fused=False, max_runs=3), dict(fused=True)):
-        kept3, rles3, boxes3, areas3, _ = ZutisEngine.instance_nms_encode(None, md, torch.from_numpy(scores).to(dev), torch.from_numpy(cats).to(dev),
-                                                                          nms_type, **kw)
+        kept3, rles3, boxes3, areas3, _, _ = instances.nms_encode(md, torch.from_numpy(scores).to(dev), torch.from_numpy(cats).to(dev), nms_type, **kw)
         assert kept3 == eng_kept and rles3 == rles1 and boxes3 == boxes1 and areas3 == areas1, kw
+
+
+def test_paint_behind_the_fused_and_the_chain_path_agree(dev):
+    """nms_encode(paint=) launches the picture behind either device path (the chain serves masks wider than 1024 columns): the two
+    give identical results and byte-identical id maps, and where a kept mask alone covers a pixel the map holds its slot + 1."""
+    from zutis_amd import instances
+    rng = np.random.default_rng(7)
+    B, Q, H, W = 2, 12, 48, 64
+    masks = np.zeros((B, Q, H, W), np.uint8)
+    for b in range(B):
+        for q in range(Q):
+            y0, x0 = rng.integers(0, H - 8), rng.integers(0, W - 8)
+            masks[b, q, y0:y0 + rng.integers(4, 24), x0:x0 + rng.integers(4, 32)] = 1
+    scores = rng.random((B, Q)).astype(np.float32) * 0.9 + 0.05
+    cats = np.array([33, 2, 40, 3], np.int64)[rng.integers(0, 4, (B, Q))]
+    md, sd, cd = torch.from_numpy(masks).to(dev), torch.from_numpy(scores).to(dev), torch.from_numpy(cats).to(dev)
+    res, ids = [], []
+    for fused in (True, False):
+        ids.append(torch.zeros((B, H, W), dtype=torch.uint8, device=dev))
+        res.append(instances.nms_encode(md, sd, cd, "hard", fused=fused, paint=dict(ids_out=ids[-1])))
+    assert tuple(res[0]) == tuple(res[1]) and torch.equal(ids[0], ids[1])
+    kept, slots, painted = res[0].kept, res[0].slots, ids[0].cpu().numpy()
+    cover = np.zeros((B, H, W), np.int32)
+    for b, _, q, _ in kept:
+        cover[b] += masks[b, q]
+    assert len(kept) > B and (painted[cover == 0] == 0).all()
+    n_alone = 0
+    for k, (b, _, q, _) in enumerate(kept):
+        alone = (masks[b, q] == 1) & (cover[b] == 1)
+        n_alone += int(alone.sum())
+        assert (painted[b][alone] == slots[k] + 1).all(), k
+    assert n_alone > 0
 
 
 def test_device_rle_strings_equal_the_host_encoder(dev):

@@ -39,12 +39,12 @@ def wrap(obj, name):
 from zutis_amd import rle
 wrap(eng, "instance_candidates"); wrap(eng, "instance_nms_encode"); wrap(rle, "rles_from_transitions"); wrap(eng, "forward_graphed")
 # the serial host stretch between the predict's synchronisation and the next forward's graph launch (the GPU idles through it)
-import zutis_amd.engine as E
+import zutis_amd.instances as E
 marks = {}
-_th = E._to_host
+_th = E.to_host
 def to_host(t, *a):
     r = _th(t, *a); marks["sync"] = time.perf_counter(); return r
-E._to_host = to_host
+E.to_host = to_host
 _rp = torch.cuda.CUDAGraph.replay
 def replay(self):
     marks["replay"] = time.perf_counter(); return _rp(self)

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from zutis_amd import instances as _instances
 from zutis_amd import ops as _ops
 from zutis_amd import rle as _rle
 from zutis_amd.engine import ZutisEngine
@@ -453,26 +454,15 @@ class ZUTIS(nn.Module):
                     for q, (s, c) in enumerate(zip(confidence_scores[bi], category_ids_h[bi])) if c != 0]
             sel = np.array([bi * Q + q for bi, _, q, _ in kept], dtype=np.int32)
             slots = None
-            if paint is not None:                       # the slot table is the host-built kept list, uploaded: image bi's j-th entry is slot j
-                table = np.zeros((B, Q, 3), np.float64)
-                count = np.zeros((B,), np.int32)
-                slots = []
-                for bi, c, q, s in kept:
-                    table[bi, count[bi]] = (q, s, c)
-                    slots.append(int(count[bi]))
-                    count[bi] += 1
-                t = torch.from_numpy(table).to(masks_dev.device)
-                eng.paint_kept(masks_dev, t[..., 0].to(torch.int32).contiguous(), t[..., 1].contiguous(), t[..., 2].to(torch.int64).contiguous(),
-                               torch.from_numpy(count).to(masks_dev.device), **paint)
+            if paint is not None:
+                table, slots = _instances.slot_table(kept, B, Q, masks_dev.device)
+                eng.paint_kept(masks_dev, *table, **paint)
             rles, boxes, areas = eng.encode_masks(masks_dev.view(B * Q, Hm, Wm), sel)
         else:
             assert nms_type in ["hard", "linear", "gaussian"]
-            if paint is None:
-                kept, rles, boxes, areas, status = eng.instance_nms_encode(masks_dev, scores, category_ids, nms_type, range_flag=range_flag)
-                slots = None
-            else:
-                kept, rles, boxes, areas, status, slots = eng.instance_nms_encode(masks_dev, scores, category_ids, nms_type,
-                                                                                  range_flag=range_flag, paint=paint)
+            kept, rles, boxes, areas, status, *slots = eng.instance_nms_encode(masks_dev, scores, category_ids, nms_type,
+                                                                               range_flag=range_flag, paint=paint)
+            slots = slots[0] if slots else None
             raise_on(status)
         predictions: List[dict] = list()
         ids: Optional[List[int]] = None if slots is None else list()

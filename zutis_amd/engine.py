@@ -11,30 +11,11 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, compose, ops
+from . import _lib, compose, instances, ops
 from ._lib import ZutisHipError
 from .engine_base import (ALL_SITES, DECODER_SITES, ENCODER_SITES, HEAD_SITES, PRECISIONS, P_shape0, _EngineBase, _rup, f16, f32,
                           resolve_precision)
 from .ops import Act
-
-
-def _to_host(t: torch.Tensor, cache: Dict[int, torch.Tensor]) -> np.ndarray:
-    """A 1-D uint8 device tensor on the host: one asynchronous copy into a cached PINNED buffer + one stream synchronisation (`.cpu()`
-    goes through pageable memory: an allocation, a staged copy and its own synchronisation).  `cache` belongs to ONE engine instance
-    (forks — one per stream / thread — have their own: a shared buffer would be overwritten by a sibling's predict).  The array is a
-    view of the cached buffer: valid until that engine's next call with the same size (callers take what they need out of it before
-    they return); a buffer that falls out of the cache stays alive as long as a view of it does."""
-    n = t.numel()
-    if cache is None:                                 # called without an engine instance (tests drive the predict's pieces that way)
-        cache = {}
-    buf = cache.get(n)
-    if buf is None:
-        while len(cache) >= 8:
-            cache.pop(next(iter(cache)))
-        buf = cache[n] = torch.empty((n,), dtype=torch.uint8, pin_memory=True)
-    buf.copy_(t, non_blocking=True)
-    torch.cuda.current_stream(t.device).synchronize()
-    return buf.numpy()
 
 
 class ZutisEngine(_EngineBase):
@@ -381,237 +362,34 @@ class ZutisEngine(_EngineBase):
             masks = binary
         return masks, score, cat
 
+    # Everything behind the candidates is zutis_amd/instances.py; these delegate with the engine's caches.
+    PACK_HEAD = instances.PACK_HEAD
+
     def mask_iou_matrix(self, masks_u8: torch.Tensor, return_areas: bool = False):
-        """Pairwise IoU of one image's [Q,H,W] u8 masks: exact popcounts on device, float64 divide on the host
-        (= utils/iou.py:30-32 on boolean masks).  The diagonal of the intersection counts is each mask's area."""
-        n = masks_u8.shape[0]
-        px = masks_u8[0].numel()
-        inter = torch.empty((n, n), dtype=torch.int32, device=masks_u8.device)
-        uni = torch.empty((n, n), dtype=torch.int32, device=masks_u8.device)
-        ops.mask_iou_counts(masks_u8.contiguous(), n, px, inter, uni)
-        ih = inter.cpu().numpy()
-        iou = ih / (uni.cpu().numpy() + 1e-7)
-        return (iou, np.diag(ih).copy()) if return_areas else iou
+        return instances.mask_iou_matrix(masks_u8, return_areas)
 
     def instance_nms(self, masks_u8: torch.Tensor, scores: torch.Tensor, category_ids: torch.Tensor, nms_type: str = "hard",
                      nms_threshold: float = 0.3, sigma: float = 0.5, threshold: float = 0.001):
-        """zutis.py:211-299 for a batch, entirely on the device: masks u8 [B,Q,H,W], scores f32 [B,Q], category_ids int64 [B,Q]
-        -> list of (batch index, category, query index, score) in the reference's emission order.  Popcount IoU counts per
-        image (zh_mask_iou_counts), then one launch of the greedy per-category loop (zh_mask_nms, one workgroup per image);
-        only the kept (index, score, category) triples and their count cross PCIe."""
-        B, Q, H, W = masks_u8.shape
-        dev = masks_u8.device
-        inter = torch.empty((B, Q, Q), dtype=torch.int32, device=dev)
-        uni = torch.empty((B, Q, Q), dtype=torch.int32, device=dev)
-        m = masks_u8.contiguous()
-        for b in range(B):
-            ops.mask_iou_counts(m[b], Q, H * W, inter[b], uni[b])
-        idx, sc, cat, cnt = ops.mask_nms(inter, uni, scores.contiguous(), category_ids.contiguous(), nms_type, nms_threshold, sigma,
-                                         threshold)
-        # ONE device -> host copy for the five small results (every copy synchronises the stream): indices, categories and counts are
-        # small integers, exact in float64 next to the float64 scores
-        f64 = torch.float64
-        packed = torch.cat([idx.to(f64), sc.to(f64), cat.to(f64), category_ids.to(f64), cnt.to(f64).view(B, 1)], dim=1).cpu().numpy()
-        idx_h, sc_h, cat_h = packed[:, :Q], packed[:, Q:2 * Q], packed[:, 2 * Q:3 * Q]    # entries past cnt are uninitialised: read per element
-        all_cat, cnt_h = packed[:, 3 * Q:4 * Q].astype(np.int64), packed[:, 4 * Q].astype(np.int64)
-        # The kernel walks the categories in ascending id; the reference walks `set(category_ids_per_image)` (zutis.py:237-238), i.e.
-        # CPython's iteration order of a set of numpy int64 scalars — ascending only while every id is below the hash table's
-        # size.  Re-create that very set on the host (Q ids per image) and order the per-category groups by it (stable: the
-        # selection order inside a category is the kernel's, which is the reference's).
-        out = []
-        for b in range(B):
-            rank = {int(c): i for i, c in enumerate(set(all_cat[b]))}
-            rows = [(b, int(cat_h[b, j]), int(idx_h[b, j]), float(sc_h[b, j])) for j in range(int(cnt_h[b]))]
-            rows.sort(key=lambda r: rank[r[1]])
-            out += rows
-        return out
+        return instances.nms(masks_u8, scores, category_ids, nms_type, nms_threshold, sigma, threshold)
 
     def instance_nms_encode(self, masks_u8: torch.Tensor, scores: torch.Tensor, category_ids: torch.Tensor, nms_type: str = "hard",
                             nms_threshold: float = 0.3, sigma: float = 0.5, threshold: float = 0.001,
                             range_flag: Optional[torch.Tensor] = None, max_runs: int = 8192, pack_head: Optional[int] = None,
                             fused: Optional[bool] = None, paint: Optional[dict] = None):
-        """instance_nms + encode_masks chained on the device (zutis.py:211-299,423-469): popcount IoU counts, the greedy per-category
-        loop, then the run extraction of the kept masks straight from the loop's device outputs (zh_mask_runs_kept) — the NMS result
-        does not visit the host in between.  ONE device -> host copy brings the kept triples, every query's category, the counts, the
-        range flag, the run counts, the boxes AND the kept masks' COCO RLE strings, encoded on the device (zh_mask_rle_kept) from the packed
-        run list; the host encodes only when that list outgrows its PACK_HEAD ints per image (a second copy) or a mask its max_runs.
-        Returns (kept [(batch index, category, query index, score)] in the reference's emission order, rles, boxes, areas, status) — status =
-        the word behind `range_flag` as the NMS kernel read it (bit ops.STATUS_RANGE: a proposal outside [0, 1]; the engine's own
-        status_word() also carries ops.STATUS_NONFINITE from the forward).  fused (None = where supported): runs, boxes, areas and strings
-        from ONE launch (zh_mask_rle_fused_kept) instead of run extraction (two launches) + string kernel; same results.
-        paint (the keyword arguments of paint_kept): the picture of the kept masks is launched behind the NMS loop, from its device outputs
-        and the bit-packed masks of the IoU step (zh_instance_paint: no copy, no synchronisation of its own), and the return value gains a
-        sixth entry, slots — per kept entry its position in the kernel's kept list, i.e. its id in the map minus 1."""
-        from . import rle
-        B, Q, H, W = masks_u8.shape
-        dev = masks_u8.device
-        inter = torch.empty((B, Q, Q), dtype=torch.int32, device=dev)
-        uni = torch.empty((B, Q, Q), dtype=torch.int32, device=dev)
-        m = masks_u8.contiguous()
-        bits = torch.empty((B, Q, (H * W + 63) // 64), dtype=torch.int64, device=dev)     # the IoU step's bit-packed masks, read again below
-        for b in range(B):
-            ops.mask_iou_counts(m[b], Q, H * W, inter[b], uni[b], workspace=bits[b])
-        per_image = (ZutisEngine.PACK_HEAD if B <= 4 else ZutisEngine.PACK_HEAD // 4) if pack_head is None else pack_head
-        if fused is None:
-            fused = ops.mask_rle_fused_supported(H, W, max_runs)     # masks up to 1024 columns whose bits + tables fit the LDS; else three launches
-        if fused:
-            # ONE launch behind the NMS loop does runs, boxes, areas and strings (zh_mask_rle_fused_kept: one workgroup per kept mask);
-            # ONE buffer = one copy for everything the host needs: [kept triples + categories + count + status (f64) | info | cursor | strings]
-            n1, n2 = B * (4 * Q + 2) * 8, B * Q * 8 * 4
-            cap = int(max(64, 4 * B * per_image))                    # bytes of strings that ride along (a string is ~2.2 B per transition)
-            small = torch.empty((n1 + n2 + 8 + cap,), dtype=torch.uint8, device=dev)
-            packed = small[:n1].view(torch.float64).view(B, 4 * Q + 2)
-            info = small[n1:n1 + n2].view(torch.int32).view(B * Q, 8)
-            cursor = small[n1 + n2:n1 + n2 + 8].view(torch.int32)    # zeroed by the NMS kernel (zero_word), used by the launch behind it
-            idx, sc, kcat, cnt = ops.mask_nms(inter, uni, scores.contiguous(), category_ids.contiguous(), nms_type, nms_threshold, sigma, threshold,
-                                              packed=packed, range_flag=range_flag, zero_word=cursor)
-            ops.mask_rle_fused_kept(m, idx, cnt, max_runs, small[n1 + n2 + 8:], cursor, info, bits=bits)
-            if paint is not None:
-                self.paint_kept(m, idx, sc, kcat, cnt, bits=bits, **paint)
-            host = _to_host(small, getattr(self, "_pinned", None))                                   # the one synchronisation of the predict
-            pk = host[:n1].view(np.float64).reshape(B, 4 * Q + 2)
-            info_h = host[n1:n1 + n2].view(np.int32).reshape(B, Q, 8)
-            chars_h = host[n1 + n2 + 8:]
-            cnt_l = pk[:, 4 * Q].astype(np.int64).tolist()
-            range_bad = int(pk[:, 4 * Q + 1].max()) if range_flag is not None else 0  # the status word as the NMS kernel read it (ops.STATUS_*)
-            kept, rles, boxes, areas, slots = [], [], [], [], []
-            size = [int(H), int(W)]
-            redo = []                                                # (position in the output lists, flat mask index): strings the device did not write
-            for b in range(B):
-                n = cnt_l[b]
-                if n == 0:
-                    continue
-                row, inf = pk[b].tolist(), info_h[b, :n].tolist()
-                # the kernel walks the categories in ascending id; the reference walks `set(category_ids_per_image)` (zutis.py:237-238):
-                # order the per-category groups by that very set (stable inside a category: the kernel's = the reference's selection order)
-                rank = {int(c): i for i, c in enumerate(set(pk[b, 3 * Q:4 * Q].astype(np.int64)))}
-                for j in sorted(range(n), key=lambda j: rank[int(row[2 * Q + j])]):
-                    q, (c0, ln, x0, y0, x1, y1, ar, _) = int(row[j]), inf[j]
-                    if ln < 0:                                       # over max_runs transitions, or the strings outgrew `cap`
-                        redo.append((len(kept), b * Q + q))
-                    kept.append((b, int(row[2 * Q + j]), q, float(row[Q + j])))
-                    slots.append(j)
-                    rles.append({"size": size, "counts": chars_h[c0:c0 + ln].tobytes()} if ln >= 0 else None)
-                    boxes.append([float(x0), float(y0), float(x1), float(y1)])
-                    areas.append(int(ar))
-            if redo:
-                r2, _, _ = ZutisEngine.encode_masks(self, masks_u8.view(B * Q, H, W), np.array([f for _, f in redo], dtype=np.int32))
-                for (at, _), r in zip(redo, r2):
-                    rles[at] = r
-            return (kept, rles, boxes, areas, range_bad) if paint is None else (kept, rles, boxes, areas, range_bad, slots)
-        # ONE buffer for everything the host needs: [kept triples + categories + count + status (f64) | run counts | boxes + areas | string
-        # lengths | the RLE strings of the kept masks, written by the device (zh_mask_rle_kept) from the packed transition list].  The list
-        # itself (PACK_HEAD ints per image) stays on the device.
-        n1, n2, n3, n4 = B * (4 * Q + 2) * 8, B * Q * 2 * 4, B * Q * 5 * 4, B * Q * 4
-        head = int(min(B * Q * max_runs, B * per_image))
-        small = torch.empty((n1 + n2 + n3 + n4 + 5 * head + 16 * B * Q,), dtype=torch.uint8, device=dev)
-        packed = small[:n1].view(torch.float64).view(B, 4 * Q + 2)
-        nr = small[n1:n1 + n2].view(torch.int32).view(B * Q, 2)
-        ba = small[n1 + n2:n1 + n2 + n3].view(torch.int32).view(B * Q, 5)
-        slen = small[n1 + n2 + n3:n1 + n2 + n3 + n4].view(torch.int32)
-        chars = small[n1 + n2 + n3 + n4:]
-        pos_head = torch.empty((head,), dtype=torch.int32, device=dev)
-        idx, sc, kcat, cnt = ops.mask_nms(inter, uni, scores.contiguous(), category_ids.contiguous(), nms_type, nms_threshold, sigma, threshold,
-                                          packed=packed, range_flag=range_flag)
-        ops.mask_runs_kept(m, idx, cnt, max_runs, pos_head, nr, ba, packed=True)
-        ops.mask_rle_kept(pos_head, nr, cnt, B, Q, max_runs, H * W, chars, slen)
-        if paint is not None:
-            self.paint_kept(m, idx, sc, kcat, cnt, bits=bits, **paint)
-        host = _to_host(small, getattr(self, "_pinned", None))                                       # the one synchronisation of the predict
-        pk = host[:n1].view(np.float64).reshape(B, 4 * Q + 2)
-        nr_h = host[n1:n1 + n2].view(np.int32).reshape(B, Q, 2)
-        ba_h = host[n1 + n2:n1 + n2 + n3].view(np.int32).reshape(B, Q, 5)
-        slen_h = host[n1 + n2 + n3:n1 + n2 + n3 + n4].view(np.int32).reshape(B, Q)
-        chars_h = host[n1 + n2 + n3 + n4:]
-        cnt_l = pk[:, 4 * Q].astype(np.int64).tolist()
-        range_bad = int(pk[:, 4 * Q + 1].max()) if range_flag is not None else 0      # the status word as the NMS kernel read it (ops.STATUS_*)
-        kept, rles, boxes, areas, slots = [], [], [], [], []
-        if B and max(cnt_l) > 0:
-            lens = [np.minimum(nr_h[b, :cnt_l[b], 0], max_runs).tolist() for b in range(B)]          # list length of every kept mask
-            total = sum(sum(l) for l in lens)
-            flat = None
-            if total > head:                                         # the lists outgrew the head: the whole packed list in a second copy,
-                big = torch.empty((total,), dtype=torch.int32, device=dev)                          # strings built on the host
-                ops.mask_runs_kept(m, idx, cnt, max_runs, big, nr, ba, packed=True)
-                flat = big.cpu().numpy()
-            size = [int(H), int(W)]
-            at = rank_all = 0
-            for b in range(B):
-                n = cnt_l[b]
-                if n == 0:
-                    continue
-                if flat is not None:
-                    r = rle.rles_from_transitions(flat[at:], nr_h[b, :n], H, W, packed_max_runs=max_runs)     # image b's lists start at `at`
-                    at += sum(lens[b])
-                else:
-                    r, sl = [], slen_h[b, :n].tolist()
-                    for j in range(n):                               # mask j's string: 5 * (start of its list) + 16 * (kept masks before it)
-                        c0 = 5 * at + 16 * rank_all
-                        r.append({"size": size, "counts": chars_h[c0:c0 + sl[j]].tobytes()} if sl[j] >= 0 else None)
-                        at += lens[b][j]
-                        rank_all += 1
-                # the kernel walks the categories in ascending id; the reference walks `set(category_ids_per_image)` (zutis.py:237-238):
-                # order the per-category groups by that very set (stable inside a category: the kernel's = the reference's selection order)
-                row = pk[b].tolist()
-                rank = {int(c): i for i, c in enumerate(set(pk[b, 3 * Q:4 * Q].astype(np.int64)))}
-                order = sorted(range(n), key=lambda j: rank[int(row[2 * Q + j])])
-                ba_l = ba_h[b, :n].tolist()
-                for j in order:
-                    q = int(row[j])
-                    if r[j] is None:                                 # pathological mask (> max_runs transitions): the host encoder
-                        r[j] = rle.encode(masks_u8[b, q].cpu().numpy())
-                    kept.append((b, int(row[2 * Q + j]), q, float(row[Q + j])))
-                    slots.append(j)
-                    rles.append(r[j])
-                    boxes.append([float(v) for v in ba_l[j][:4]])
-                    areas.append(int(ba_l[j][4]))
-        return (kept, rles, boxes, areas, range_bad) if paint is None else (kept, rles, boxes, areas, range_bad, slots)
+        """instances.nms_encode -> (kept, rles, boxes, areas, status), and slots as a sixth entry when paint is given."""
+        r = instances.nms_encode(masks_u8, scores, category_ids, nms_type, nms_threshold, sigma, threshold, range_flag, max_runs, pack_head,
+                                 fused, paint, pinned=self._pinned, colour_cache=self._slot_colours)
+        return tuple(r) if paint is not None else tuple(r[:5])
 
     def paint_kept(self, masks_u8: torch.Tensor, index: torch.Tensor, score: torch.Tensor, category: torch.Tensor, count: torch.Tensor, *,
                    bits: Optional[torch.Tensor] = None, packed=None, desc=None, desc_host=None, colours=None, palette=None, alpha: int = 128,
                    outline: bool = True, min_score: float = 0.0, id_format: str = "u8", ids_out=None, overlay_out=None):
-        """The picture of a kept list (ops.instance_paint) on the current stream: index / score / category / count as zh_mask_nms writes
-        them ([B,Q] int32 / f64 / int64, [B] int32), on the device.  The colour of slot j of image b: colours[b, j] (u8 [B,Q,3]), or
-        palette[category[b, j]] (palette u8 [n,3] by the network's category index; gathered on the device), or — both None — entry j of
-        instance_paint.instance_colours.  ids_out / overlay_out: the caller's device buffers (ops.instance_paint's shapes)."""
-        B, Q, H, W = masks_u8.shape
-        if overlay_out is not None and colours is None:
-            if palette is not None:
-                colours = palette[category.clamp(0, palette.shape[0] - 1)].contiguous()      # entries past count are not read by the kernel
-            else:
-                from .instance_paint import instance_colours
-                key = (Q, str(masks_u8.device))
-                if getattr(self, "_slot_colours", (None,))[0] != key:
-                    self._slot_colours = (key, torch.from_numpy(instance_colours(Q)).to(masks_u8.device))
-                colours = self._slot_colours[1].unsqueeze(0).expand(B, Q, 3).contiguous()
-        return ops.instance_paint(index, score, count, H, W, masks=masks_u8, bits=bits, colours=colours, alpha=alpha, outline=outline,
-                                  min_score=min_score, packed=packed, desc=desc, desc_host=desc_host, id_format=id_format, ids_out=ids_out,
-                                  overlay_out=overlay_out)
-
-    # ints of the packed transition list that ride along with the small tables, per image (256 KB; a quarter of it per image in batches
-    # above 4): the 17 kept masks of the config-3 fixture (480x640, noisy: ~1750 transitions each) are 29.8 k
-    PACK_HEAD = 65536
+        return instances.paint_kept(masks_u8, index, score, category, count, colour_cache=self._slot_colours, bits=bits, packed=packed, desc=desc,
+                                    desc_host=desc_host, colours=colours, palette=palette, alpha=alpha, outline=outline, min_score=min_score,
+                                    id_format=id_format, ids_out=ids_out, overlay_out=overlay_out)
 
     def encode_masks(self, masks_u8: torch.Tensor, sel: np.ndarray, max_runs: int = 8192):
-        """COCO RLE dicts, xyxy boxes and areas of the masks `sel` (flat indices into [n,H,W]) without moving the masks
-        to the host: zh_mask_runs extracts the column-major run boundaries on the device; only those cross PCIe."""
-        from . import rle
-        n, H, W = masks_u8.shape
-        if len(sel) == 0:
-            return [], [], []
-        sel_dev = torch.from_numpy(np.ascontiguousarray(sel, dtype=np.int32)).to(masks_u8.device)
-        pos, nr, ba = ops.mask_runs(masks_u8.contiguous(), sel_dev, max_runs)
-        nb_h = torch.cat([nr, ba], dim=1).cpu().numpy()           # one copy (= one stream synchronisation) for both small tables
-        nr_h, ba_h = nb_h[:, :2], nb_h[:, 2:]
-        keep = int(min(max_runs, max(1, nr_h[:, 0].max())))
-        pos_h = pos[:, :keep].cpu().numpy()
-        rles = rle.rles_from_transitions(pos_h, nr_h, H, W)      # all strings in one C call (was one numpy diff + ctypes call per mask)
-        for j, q in enumerate(sel):
-            if rles[j] is None:                                  # pathological mask (> max_runs transitions): the host encoder
-                rles[j] = rle.encode(masks_u8[int(q)].cpu().numpy())
-        boxes = [[float(v) for v in row[:4]] for row in ba_h]
-        areas = [int(row[4]) for row in ba_h]
-        return rles, boxes, areas
+        return instances.encode_masks(masks_u8, sel, max_runs)
 
 
 from .engine_clip import ClipImageEncoder, ClipTextEncoder      # noqa: E402,F401  (re-exports)

@@ -149,6 +149,7 @@ class _EngineBase:
         self._graphs: "collections.OrderedDict" = collections.OrderedDict()
         self._bufs: Dict[Tuple, torch.Tensor] = {}
         self._pinned: Dict[int, torch.Tensor] = {}    # pinned staging buffers of the predict's one device -> host copy (per engine instance)
+        self._slot_colours: Dict = {}                 # instances.paint_kept's default colour table on the device (per engine instance)
         self._buf_gen = 0             # bumped on every (re)allocation: launch plans check it
         self._buf_const: Dict[str, torch.Tensor] = {}   # buffers with constant regions: name -> the tensor that was initialised
         self._pt16_of = self._text16_of = None   # which tensors the cached f16 copies "pt16" / "text16" were made from
@@ -164,7 +165,7 @@ class _EngineBase:
         # input-independent tables are shared; captured graphs are not (they replay into the parent's buffers and stream)
         e._geo = dict(self._geo)
         e._graphs = collections.OrderedDict()
-        e._pinned = {}
+        e._pinned, e._slot_colours = {}, {}
         e._pt16_of = e._text16_of = None       # provenance of the f16 copies held in the (new, empty) buffer cache
         e._status = None                       # a status word of its own (it is written on the fork's stream)
         return e

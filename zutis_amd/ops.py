@@ -70,6 +70,16 @@ def _workspace(size_entry: str, device, *dims):
     return torch.empty(need, dtype=torch.uint8, device=device), need
 
 
+def _workspace_or(ws, name: str, size_entry: str, device, *dims):
+    """_workspace, or the caller's own `ws` (any dtype) checked against that size."""
+    if ws is None:
+        return _workspace(size_entry, device, *dims)
+    need = int(getattr(_lib.load(raw=True), size_entry)(*dims))
+    if _nbytes(ws) < need:
+        raise _lib.ZutisHipError(f"{name}: workspace holds {_nbytes(ws)} bytes, {need} needed")
+    return ws, need
+
+
 def _chk(t: torch.Tensor, dtype, name: str):
     if t.dtype != dtype or not t.is_contiguous():
         raise _lib.ZutisHipError(f"{name}: expected contiguous {dtype}, got {t.dtype} contiguous={t.is_contiguous()}")
@@ -423,6 +433,24 @@ def upsample_argmax_score(logits_lo, gt, hist, B, n, h, w, H, W, gt_format: str 
           lin_scale(h, H), lin_scale(w, W), _stream())
 
 
+def _chk_overlay(name: str, overlay_out, packed, desc, desc_host, table_name: str, table, table_shape, alpha, B, H, W):
+    """The overlay arguments of `name` (colour table `table_name`, u8 of `table_shape`) and, on desc_host when given (else on a blocking
+    read of desc), every descriptor row's image of the overlay's size and inside packed: the kernels trust packed / desc."""
+    _chk(overlay_out, torch.uint8, f"{name} overlay_out"); _chk(packed, torch.uint8, f"{name} packed")
+    _chk(desc, torch.int32, f"{name} desc"); _chk(table, torch.uint8, f"{name} {table_name}")
+    if tuple(overlay_out.shape) != (B, H, W, 3) or packed.dim() != 1 or tuple(desc.shape) != (B, 8) or tuple(table.shape) != table_shape:
+        raise _lib.ZutisHipError(f"{name}: overlay_out {(B, H, W, 3)}, packed [bytes], desc {(B, 8)}, {table_name} {table_shape} expected, got "
+                                 f"{tuple(overlay_out.shape)}, {tuple(packed.shape)}, {tuple(desc.shape)}, {tuple(table.shape)}")
+    if int(alpha) != alpha or not 0 <= int(alpha) <= 256:
+        raise _lib.ZutisHipError(f"{name}: alpha {alpha!r} is not an integer in 0..256")
+    rows = (desc if desc_host is None else desc_host).cpu().numpy().reshape(B, 8)
+    for b, (off, iw, ih) in enumerate(rows[:, :3].tolist()):
+        if (iw, ih) != (W, H):
+            raise _lib.ZutisHipError(f"{name}: descriptor row {b} holds a {iw} x {ih} image, the overlay is {W} x {H}")
+        if off < 0 or off * 16 + 3 * W * H > packed.numel():
+            raise _lib.ZutisHipError(f"{name}: descriptor row {b} places its image outside packed ({packed.numel()} bytes)")
+
+
 def upsample_argmax_bytes(logits_lo, B, n, h, w, H, W, label_format: str = "u8", labels_out=None, overlay_out=None, packed=None, desc=None,
                           palette=None, alpha: int = 128, desc_host=None):
     """upsample_argmax with the label leaving as the bytes of the file it becomes (zutis.py:366-372; imagenet_s.py:93 read backwards):
@@ -449,19 +477,7 @@ def upsample_argmax_bytes(logits_lo, B, n, h, w, H, W, label_format: str = "u8",
     if overlay_out is not None:
         if packed is None or desc is None or palette is None:
             raise _lib.ZutisHipError("upsample_argmax_bytes: an overlay needs packed, desc and palette")
-        _chk(overlay_out, torch.uint8, "upsample_argmax_bytes overlay_out"); _chk(packed, torch.uint8, "upsample_argmax_bytes packed")
-        _chk(desc, torch.int32, "upsample_argmax_bytes desc"); _chk(palette, torch.uint8, "upsample_argmax_bytes palette")
-        if tuple(overlay_out.shape) != (B, H, W, 3) or packed.dim() != 1 or tuple(desc.shape) != (B, 8) or tuple(palette.shape) != (n, 3):
-            raise _lib.ZutisHipError(f"upsample_argmax_bytes: overlay_out {(B, H, W, 3)}, packed [bytes], desc {(B, 8)}, palette {(n, 3)} expected, got "
-                                     f"{tuple(overlay_out.shape)}, {tuple(packed.shape)}, {tuple(desc.shape)}, {tuple(palette.shape)}")
-        if int(alpha) != alpha or not 0 <= int(alpha) <= 256:
-            raise _lib.ZutisHipError(f"upsample_argmax_bytes: alpha {alpha!r} is not an integer in 0..256")
-        rows = (desc if desc_host is None else desc_host).cpu().numpy().reshape(B, 8)
-        for b, (off, iw, ih) in enumerate(rows[:, :3].tolist()):
-            if (iw, ih) != (W, H):
-                raise _lib.ZutisHipError(f"upsample_argmax_bytes: descriptor row {b} holds a {iw} x {ih} image, the overlay is {W} x {H}")
-            if off < 0 or off * 16 + 3 * W * H > packed.numel():
-                raise _lib.ZutisHipError(f"upsample_argmax_bytes: descriptor row {b} places its image outside packed ({packed.numel()} bytes)")
+        _chk_overlay("upsample_argmax_bytes", overlay_out, packed, desc, desc_host, "palette", palette, (n, 3), alpha, B, H, W)
     else:
         packed = desc = palette = None
     _call("zh_upsample_argmax_bytes", _p(logits_lo), _p(labels_out), GT_FORMATS[label_format], _p(overlay_out), _p(packed), _p(desc), _p(palette),
@@ -500,10 +516,7 @@ def instance_classify(avg, text, conf, temperature, rows, n, E, category, score)
 def mask_iou_counts(masks_u8, n, pixels, inter, uni, workspace=None):
     """workspace (optional, >= zh_mask_iou_workspace_size bytes, any dtype): kept by the caller, it holds the masks bit-packed afterwards
     (u64 [n][(pixels + 63) // 64]: the `bits` of mask_rle_fused_kept)."""
-    need = _lib.load(raw=True).zh_mask_iou_workspace_size(n, pixels)
-    ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=masks_u8.device)
-    if _nbytes(ws) < need:
-        raise _lib.ZutisHipError(f"mask_iou_counts: workspace holds {_nbytes(ws)} bytes, {need} needed")
+    ws, need = _workspace_or(workspace, "mask_iou_counts", "zh_mask_iou_workspace_size", masks_u8.device, n, pixels)
     _call("zh_mask_iou_counts", _p(masks_u8), n, pixels, _p(inter), _p(uni), _p(ws), need, _stream())
 
 
@@ -620,25 +633,10 @@ def instance_paint(index, score, count, H, W, *, masks=None, bits=None, colours=
     if overlay_out is not None:
         if packed is None or desc is None or colours is None:
             raise _lib.ZutisHipError("instance_paint: an overlay needs packed, desc and colours")
-        _chk(overlay_out, torch.uint8, "instance_paint overlay_out"); _chk(packed, torch.uint8, "instance_paint packed")
-        _chk(desc, torch.int32, "instance_paint desc"); _chk(colours, torch.uint8, "instance_paint colours")
-        if tuple(overlay_out.shape) != (B, H, W, 3) or packed.dim() != 1 or tuple(desc.shape) != (B, 8) or tuple(colours.shape) != (B, Q, 3):
-            raise _lib.ZutisHipError(f"instance_paint: overlay_out {(B, H, W, 3)}, packed [bytes], desc {(B, 8)}, colours {(B, Q, 3)} expected, got "
-                                     f"{tuple(overlay_out.shape)}, {tuple(packed.shape)}, {tuple(desc.shape)}, {tuple(colours.shape)}")
-        if int(alpha) != alpha or not 0 <= int(alpha) <= 256:
-            raise _lib.ZutisHipError(f"instance_paint: alpha {alpha!r} is not an integer in 0..256")
-        rows = (desc if desc_host is None else desc_host).cpu().numpy().reshape(B, 8)
-        for b, (off, iw, ih) in enumerate(rows[:, :3].tolist()):
-            if (iw, ih) != (W, H):
-                raise _lib.ZutisHipError(f"instance_paint: descriptor row {b} holds a {iw} x {ih} image, the overlay is {W} x {H}")
-            if off < 0 or off * 16 + 3 * W * H > packed.numel():
-                raise _lib.ZutisHipError(f"instance_paint: descriptor row {b} places its image outside packed ({packed.numel()} bytes)")
+        _chk_overlay("instance_paint", overlay_out, packed, desc, desc_host, "colours", colours, (B, Q, 3), alpha, B, H, W)
     else:
         packed = desc = colours = None
-    need = instance_paint_workspace_size(B, Q, H, W)
-    ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=index.device)
-    if _nbytes(ws) < need:
-        raise _lib.ZutisHipError(f"instance_paint: workspace holds {_nbytes(ws)} bytes, {need} needed")
+    ws, need = _workspace_or(workspace, "instance_paint", "zh_instance_paint_workspace_size", index.device, B, Q, H, W)
     _call("zh_instance_paint", _p(masks), _p(bits), _p(index), _p(score), _p(count), _p(colours), int(alpha), int(bool(outline)), float(min_score),
           _p(packed), _p(desc), _p(ids_out), GT_FORMATS[id_format], _p(overlay_out), B, Q, H, W, _p(ws), need, _stream())
     return ids_out, overlay_out
