@@ -469,9 +469,10 @@ def test_batch_invariance_full_size(dev, precision, t_mask, t_tok):
     """Size-independent property at the BASELINE geometry (ViT-B/16 @336): images are independent, and every reduction runs over K /
     keys / one image in an order fixed by the shape, so image i's outputs are BITWISE the same at any position of a batch and in
     batches of different sizes that select the same kernels (here 5 and 6 images: what makes rank-sharded evaluation with equal
-    shards reproduce the single-GPU result exactly).  Kernel selection has three thresholds — split-K of the N = D GEMMs up to 2048
-    token rows, the key split of self-attention up to 128 (image, head, query block) items, the few-row GEMM kernel up to 128 rows and 512 workgroups
-    (engine_base._splitk / _vit_blocks, gemm_skinny.h) — and across them (one image alone) the sums are re-associated: fp32-class
+    shards reproduce the single-GPU result exactly).  Kernel selection has four batch-reading rules — split-K of the
+    N = D GEMMs up to 2048 token rows, the key split of self-attention up to 128 (image, head, query block) items, the long-sequence key split
+    (T >= 2048: not at this geometry), the few-row GEMM kernel up to 128 rows and 512 workgroups (shape_rules.gemm_k_split / self_attention_key_split /
+    long_sequence_key_split, gemm_skinny.h) — plus the engine's cross_ksplit setting, which reads the batch only as "auto"; across them (one image alone) the sums are re-associated: fp32-class
     agreement at `exact` (measured 1e-7 tokens / 5e-7 masks), the precision's own rounding level at `fast`."""
     from zutis_amd import detgen
     cfg = detgen.VIT_B16

@@ -125,10 +125,10 @@ def test_label_mismatch_explanation_helper():
 
 
 def test_long_sequence_key_split_model():
-    """engine_base.long_sequence_key_split (round 6): the split is 1 .. 8, never leaves a workgroup without keys, takes 1 when the grid
+    """shape_rules.long_sequence_key_split (round 6): the split is 1 .. 8, never leaves a workgroup without keys, takes 1 when the grid
     already fills whole rounds of the chip, and splits when the launch is one under-filled round (SelfMask at T = 5505: one image = 264
     workgroups on 256 CUs; four images = 1.375 rounds of 768 slots) — the picks measured in profiles/r06_attn_long_split.txt."""
-    from zutis_amd.engine_base import long_sequence_key_split as f
+    from zutis_amd.shape_rules import long_sequence_key_split as f
     T, H, dh = 5505, 6, 64
     nqb = -(-T // 128)
     picks = {B: f(B * H * nqb, -(-T // 32), dh, True, B * T * H * dh) for B in (1, 2, 4, 8)}

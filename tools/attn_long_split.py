@@ -1,12 +1,12 @@
 """Long self-attention (SelfMask's DINO ViT-S/8 @512x683: 6 heads, dh = 64, T = 5505) with the keys split over S workgroups per
 (image, head, query block): us per launch for S = 1 .. 8 at 1 / 2 / 4 / 8 images, split-pair (x3) and plain fp16 operands, next to the
-split the engine's model picks (zutis_amd/engine_base.py::long_sequence_key_split).  usage: attn_long_split.py [T]"""
+split the engine's model picks (zutis_amd/shape_rules.py::long_sequence_key_split).  usage: attn_long_split.py [T]"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from zutis_amd import ops
-from zutis_amd.engine_base import long_sequence_key_split
+from zutis_amd.shape_rules import QUERY_BLOCK, fit_key_split, key_tiles, long_sequence_key_split
 
 dev = torch.device("cuda:0")
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 5505
@@ -23,12 +23,12 @@ for x3 in (True, False):
             return ops.Act(torch.stack([hi, (t - hi.float()).half()]))
         q, k, v = act(mk()), act(mk()), act(mk())
         o = ops.Act(torch.empty((2, B, T, D), device=dev, dtype=torch.float16)) if x3 else torch.empty(B, T, D, device=dev, dtype=torch.float16)
-        ktiles = -(-T // (32 if x3 else 64))
-        pick = long_sequence_key_split(B * H * -(-T // 128), ktiles, dh, x3, B * T * D)
+        ktiles = key_tiles(T, x3)
+        pick = long_sequence_key_split(B * H * -(-T // QUERY_BLOCK), ktiles, dh, x3, B * T * D)
         row = []
         ref = None
         for S in range(1, 9):
-            if S > 1 and (S - 1) * -(-ktiles // S) >= ktiles:
+            if fit_key_split(S, ktiles) != S:
                 row.append("   -  ")
                 continue
             ws = torch.empty((ops.attention_splitk_workspace_size(B, H, T, dh, S),), dtype=torch.uint8, device=dev) if S > 1 else None

@@ -23,9 +23,9 @@ def mk(T):
 q, k, v = mk(Tq), mk(Tk), mk(Tk)
 o = Act.empty((B * Tq, D), x3, dev)
 S, ws = 1, None
-if Tq >= 2048:                                       # the engine's rule for long self-attention (engine_base.long_sequence_key_split)
-    from zutis_amd.engine_base import long_sequence_key_split
-    S = long_sequence_key_split(B * H * -(-Tq // 128), -(-Tk // (32 if x3 else 64)), dh, x3, B * Tq * D)
+if Tq >= 2048:                                       # the engine's rule for long self-attention (shape_rules.long_sequence_key_split)
+    from zutis_amd.shape_rules import QUERY_BLOCK, key_tiles, long_sequence_key_split
+    S = long_sequence_key_split(B * H * -(-Tq // QUERY_BLOCK), key_tiles(Tk, x3), dh, x3, B * Tq * D)
     if S > 1:
         ws = torch.empty((ops.attention_splitk_workspace_size(B, H, Tq, dh, S),), dtype=torch.uint8, device=dev)
 for _ in range(10):

@@ -281,7 +281,7 @@ class ZUTIS(nn.Module):
         self._engine: Optional[ZutisEngine] = None
         # "fast" | "exact" | "f16" (zutis_amd.engine): exact = every contraction in the reference-equivalent f16x3 mode
         self.precision: str = "exact"
-        # engine_base._decoder: this module serves batch-1 evaluation loops (coco20k_eval.py:241-268), where the decoder's cross-attention is
+        # shape_rules.cross_attention_key_split: this module serves batch-1 evaluation loops (coco20k_eval.py:241-268), where the decoder's cross-attention is
         # 8 workgroups per launch unless its keys are split: forward at 480x640 4.25 / 3.56 / 3.21 / 3.04 / 2.97 ms for splits 1 / 2 / 4 / 8 / 16
         self.cross_attention_key_split: int = 12     # round 4, 4800 keys: 36.2 / 31.1 us for splits 8 / 12 (30 ties with 12: the merge grows with it)
         # forward() of batches <= 4 replays a hipGraph captured per input shape (the eager path costs ~11 us of Python + ctypes per launch,
@@ -297,7 +297,7 @@ class ZUTIS(nn.Module):
         if self._engine is None:
             self._engine = ZutisEngine(dict(self.named_parameters()), self.encoder.patch_size, self.n_heads,
                                        precision=self.precision)
-            self._engine.cross_ksplit = self.cross_attention_key_split      # batch-1 evaluation loops: see engine_base._decoder
+            self._engine.cross_ksplit = self.cross_attention_key_split      # batch-1 evaluation loops: see shape_rules.cross_attention_key_split
         return self._engine
 
     def _apply(self, fn, *args, **kwargs):

@@ -28,16 +28,14 @@ Reference call sites are cited per step (paths relative to the reference root).
 from __future__ import annotations
 
 import collections
-
 import math
-import os
 import weakref
 from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib, compose, ops
+from . import _lib, compose, ops, shape_rules
 from ._lib import ZutisHipError
 
 from .ops import Act
@@ -99,37 +97,6 @@ def _rup(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
-
-def long_sequence_key_split(items: int, ktiles: int, head_dim: int, x3: bool, out_elems: int) -> int:
-    """Key split (1 .. 8) of a LONG self-attention (SelfMask's DINO ViT-S/8 at 512x683: T = 5505, networks/selfmask/vision_transformer.py:110-133)
-    from a round-quantisation model of zh_attention_f16's grid: `items` = (image, head, 128-query block) workgroups, each walking `ktiles`
-    key tiles.  A CU holds 3 such workgroups (2 for the pipelined split-pair loop and at dh = 96), so 4 images x 6 heads x 44 blocks = 1056
-    workgroups are 1.375 rounds of the chip's 768 slots — two rounds, the second a third full — and ONE image (264 workgroups) leaves
-    every SIMD a single wave with nothing to overlap its softmax with.  Splitting the keys over S workgroups per item (partials merged by
-    attn_combine_kernel) buys finer rounds for one pass over the fp32 partials.  Cost in key-tile times of a full CU:
-    rounds x (chunk + fixed) + a last partial round at the (faster) per-tile time of its occupancy + the merge traffic."""
-    def wpc_of(n):
-        if x3 and (head_dim == 96 or -(-n // 512) <= -(-n // 768)):
-            return 2                                       # the launcher's rule for the software-pipelined loop (attention.hip)
-        return 3 if head_dim == 64 else 2
-    tile_time = {1: 0.78, 2: 0.89, 3: 1.0}                 # per-tile time of a workgroup with 1 / 2 / 3 resident per CU (stamps, profiles/NOTES.md)
-    tile_us = 1.85 if x3 else 0.95                         # one key tile of a workgroup at full occupancy
-    best, best_cost = 1, None
-    for S in range(1, 9):
-        chunk = -(-ktiles // S)
-        if S > 1 and (S - 1) * chunk >= ktiles:
-            continue
-        n = items * S
-        wpc = wpc_of(n)
-        full, rem = divmod(n, 256 * wpc)
-        cost = full * (chunk + 2) * tile_time[wpc]
-        if rem:
-            cost += (chunk + 2) * tile_time[min(wpc, -(-rem // 256))]
-        if S > 1:
-            cost += S * out_elems * 4 * 2 / 3.0e12 * 1e6 / tile_us      # partials written and read once, ~3 TB/s
-        if best_cost is None or cost < best_cost * 0.97:               # a larger split must win by 3 %
-            best, best_cost = S, cost
-    return best
 
 class _EngineBase:
     """Shared plumbing: fp16 weight packing keyed on parameter versions, shape-keyed buffer cache, and the two
@@ -355,44 +322,26 @@ class _EngineBase:
         QKV = self._abuf("QKV16", (R, 3 * D), xa)
         O = self._abuf("O16", (R, D), self._x3("out"))
         Hh = self._abuf("H16", (R, Fd), self._x3("proj"))
-        q_, k_, v_ = QKV, QKV.view(QKV.hi[:, D:]), QKV.view(QKV.hi[:, 2 * D:])
-        # Few-row regime (batch-1 evaluation: configs/*.yaml val batch_size 1, trainer.py:328-345): the two N = D GEMMs of a block
-        # (out_proj, c_proj) are 60 tiles of 128 x 128 for 256 CUs, so their K is split over S workgroups per tile — a batched GEMM
-        # over K slabs writing fp32 partial planes — and the planes are summed by the LayerNorm that follows (zh_sum_layernorm_f32:
-        # bias + residual + ln_2 / the next block's ln_1 in the same pass).  Same launch count, 4x the workgroups, no LN launch of its own.
+        qkv = self._qkv_views(QKV, D)
+        # Few-row regime (shape_rules.gemm_k_split): out_proj / c_proj as batched GEMMs over K slabs writing fp32 partial planes, summed by
+        # the LayerNorm that follows (zh_sum_layernorm_f32: bias + residual + ln_2 / the next block's ln_1 in the same pass).  Same launch
+        # count, 4x the workgroups, no LN launch of its own.
         st = self.status_word()
-        s_out, s_proj = self._splitk(R, D, D), self._splitk(R, D, Fd)
+        s_out, s_proj = shape_rules.gemm_k_split(R, D), shape_rules.gemm_k_split(R, Fd)
         sk = self._x3("out") and self._x3("proj") and (s_out > 1 or s_proj > 1)
         if X.dtype == f16 and (self._x3("out") or self._x3("proj")):
             raise ZutisHipError("an fp16 residual stream needs the fp16-operand out / proj GEMMs (precision \"half\")")
         parts = self._buf("sk_parts", (max(s_out, s_proj), R, D), f32) if sk else None
-
-        def gemm_parts(site, A, Wt, S):
-            K = A.hi.shape[-1]
-            return self._gemm(site, A, Wt, parts, M=R, N=D, K=K // S, lda=K, ldw=K, ldc=D, batch=S, strideA=K // S, strideW=K // S, strideC=R * D)
-        # Self-attention with few (image, head, 128-query block) items — one image: 12 heads x 10 blocks on 256 CUs — splits the keys
-        # over workgroups as the decoder's cross-attention does (zh_attention_f16_splitk + merge): a function of B * heads and T only
-        eks, ews = 1, None
-        if not causal:
-            per_image = heads * -(-T // 128)
-            eks = max(1, min(8, 256 // per_image)) if B * per_image <= 128 else 1      # the split itself does not depend on B
-            ktiles = -(-T // (32 if xa else 64))
-            if eks == 1 and T >= 2048:
-                eks = long_sequence_key_split(B * per_image, ktiles, D // heads, xa, B * T * D)
-            while eks > 1 and (eks - 1) * -(-ktiles // eks) >= ktiles:
-                eks -= 1
-            if eks > 1:
-                ews = self._buf("enc_attn_ws", (ops.attention_splitk_workspace_size(B, heads, T, D // heads, eks),), torch.uint8)
+        eks = shape_rules.self_attention_key_split(B, T, heads, D // heads, xa, causal)
+        ews = self._buf("enc_attn_ws", (ops.attention_splitk_workspace_size(B, heads, T, D // heads, eks),), torch.uint8) if eks > 1 else None
         for i in range(n_layers):
             pp = f"enc.{i}."
             if not (sk and s_proj > 1 and i > 0):          # split-K regime: ln_1 of block i > 0 came out of block i - 1's last kernel
                 ops.layernorm(X, W_[pp + "ln1.w"], W_[pp + "ln1.b"], eps, R, D, out_f16=Y, status=st)
             self._gemm("qkv", Y, W_[pp + "qkv_w"], QKV, bias=W_[pp + "qkv_b"])
-            ops.attention(q_, k_, v_, O, batch=B, heads=heads, Tq=T, Tk=T, head_dim=D // heads,
-                          ldq=3 * D, ldk=3 * D, ldv=3 * D, ldo=D, strideQ=T * 3 * D, strideK=T * 3 * D, strideV=T * 3 * D,
-                          strideO=T * D, causal=causal, x3=xa, ksplit=eks, workspace=ews)
+            self._attention_packed(qkv, O, B, T, D, heads, causal=causal, x3=xa, ksplit=eks, workspace=ews)
             if sk and s_out > 1:
-                gemm_parts("out", O, W_[pp + "out_w"], s_out)
+                self._gemm_kslabs("out", O, W_[pp + "out_w"], parts, s_out)
                 ops.sum_layernorm(parts, s_out, R, D, bias=W_[pp + "out_b"], residual=X, out_sum=X, gamma=W_[pp + "ln2.w"], beta=W_[pp + "ln2.b"],
                                   eps=eps, out_f16=Y, status=st)
             else:
@@ -400,7 +349,7 @@ class _EngineBase:
                 ops.layernorm(X, W_[pp + "ln2.w"], W_[pp + "ln2.b"], eps, R, D, out_f16=Y, status=st)
             self._gemm("fc", Y, W_[pp + "fc_w"], Hh, bias=W_[pp + "fc_b"], act=act)
             if sk and s_proj > 1:
-                gemm_parts("proj", Hh, W_[pp + "proj_w"], s_proj)
+                self._gemm_kslabs("proj", Hh, W_[pp + "proj_w"], parts, s_proj)
                 nx = f"enc.{i + 1}." if i + 1 < n_layers else None
                 ops.sum_layernorm(parts, s_proj, R, D, bias=W_[pp + "proj_b"], residual=X, out_sum=X,
                                   gamma=W_[nx + "ln1.w"] if nx else None, beta=W_[nx + "ln1.b"] if nx else None, eps=eps, out_f16=Y if nx else None,
@@ -408,24 +357,23 @@ class _EngineBase:
             else:
                 self._gemm("proj", Hh, W_[pp + "proj_w"], X, bias=W_[pp + "proj_b"], residual=X)
 
-    # rows (B * T) up to which the N = D GEMMs of a transformer block run split-K; and the split as a function of the shape only
-    # (never of the data): results are bitwise reproducible for a given (rows, D, K)
-    SPLITK_MAX_ROWS = int(os.environ.get("ZH_SPLITK_MAX_ROWS", "2048"))
+    def _gemm_kslabs(self, site, A, W, parts, S):
+        """A [R, K] x W [N, K]^T as ONE batched GEMM over S K-slabs: slab s writes the fp32 plane parts[s] ([R, N]); the
+        zh_sum_layernorm_f32 launch that follows adds the planes (S = shape_rules.gemm_k_split)."""
+        K, (R, N) = A.hi.shape[-1], parts.shape[1:]
+        return self._gemm(site, A, W, parts, M=R, N=N, K=K // S, lda=K, ldw=K, ldc=N, batch=S, strideA=K // S, strideW=K // S, strideC=R * N)
 
-    def _splitk(self, R: int, N: int, K: int) -> int:
-        """K split of an [R, N] = [R, K] x [N, K]^T GEMM whose partial planes a zh_sum_layernorm_f32 launch adds up.  A function of
-        K alone inside the few-row regime: image i's result does not depend on how many images share its batch there."""
-        if R > self.SPLITK_MAX_ROWS or K % 64:
-            return 1
-        s = 1
-        while 2 * s <= self.SPLITK_MAX and (K // (2 * s)) % 64 == 0 and K // (2 * s) >= self.SPLITK_MIN_K:
-            s *= 2
-        return s
+    @staticmethod
+    def _qkv_views(QKV: Act, D: int):
+        """(q, k, v) of a packed [R, 3D] q|k|v buffer: column slices of the same pair."""
+        return QKV, QKV.view(QKV.hi[:, D:]), QKV.view(QKV.hi[:, 2 * D:])
 
-    SPLITK_MAX = int(os.environ.get("ZH_SPLITK_MAX", "4"))
-    # shortest K slab: c_proj (K = 3072) splits four ways (38.4 -> 25.0 us for the GEMM, + 5 us in the LayerNorm that adds the planes);
-    # out_proj (K = 768) does not — its 228 tiles of 64 x 64 already fill the chip (11.8 us; planes + a longer LayerNorm cost more)
-    SPLITK_MIN_K = int(os.environ.get("ZH_SPLITK_MIN_K", "512"))
+    @staticmethod
+    def _attention_packed(qkv, O, B, T, D, heads, **kw):
+        """Self-attention of B sequences of T rows over _qkv_views of a packed buffer, consumed in place (strided heads) -> O [B*T, D]."""
+        q, k, v = qkv
+        ops.attention(q, k, v, O, batch=B, heads=heads, Tq=T, Tk=T, head_dim=D // heads, ldq=3 * D, ldk=3 * D, ldv=3 * D, ldo=D,
+                      strideQ=T * 3 * D, strideK=T * 3 * D, strideV=T * 3 * D, strideO=T * D, **kw)
 
     def _decoder_kv(self, VIN16, KIN16, B, M, D, L, k_pos=None):
         """Cross-attention K / V of all L layers (transformer.py:281-284) from ONE GEMM each: [B*M, L*D] fp16 (split pairs
@@ -458,27 +406,12 @@ class _EngineBase:
         ff16 = self._abuf("ff16", (R, Ff), xd)
         inter16 = self._abuf("inter16", (B * (L if stack_all else 1) * Q, D), self._x3(*self._dec_out_sites))
         out32 = self._buf("dec_out32", (R, D), f32)
-        # cross-attention: Q <= 128 queries against M keys is ONE workgroup per (image, head): 8 workgroups at batch 1 (the COCO-20K
-        # evaluation's regime), 256 at batch 32 (one per CU, each streaming its K / V with a single tile of prefetch).  The keys can be
-        # split over `self.cross_ksplit` workgroups + a merge launch (zh_attention_f16_splitk).  Measured (round 3): batch-1 forward
-        # + predict 2.99 / 2.73 / 2.60 / 2.54 ms for splits 1 / 2 / 4 / 8; the batch-32 step with three batches in flight loses
-        # 0.3 - 1 % with a split of 2 (2825 / 2842 against 2852 / 2851 images/s, same box: the partials' round trip costs more than
-        # the extra occupancy gives there).  The split is a property of the ENGINE INSTANCE (throughput: 1, the engine's default
-        # and what bench.py runs; the drop-in modules set 8, they serve batch-1 evaluation loops — at the COCO-20K shape, 480x640 = 4800
-        # keys, the forward is 4.25 / 3.56 / 3.04 ms for splits 1 / 2 / 8) and never of the batch — image
-        # i's result is bitwise independent of its position in the batch and of the other images, and bitwise equal across batch sizes that
-        # fall on the same side of the shape thresholds of DESIGN 3b (split-K rows, key-split items, skinny rows); across a threshold the
-        # sums are re-associated: ~1e-7 on tokens, ~5e-7 on masks (tests/test_e2e_gpu.py::test_batch_invariance_full_size).
-        cs = self.cross_ksplit
-        if cs == "auto":
-            # opt-in (round 6; bench.py's config-4 runs: 8 images x 8 heads = 64 workgroups of 171 key tiles on 256 CUs): the split that
-            # puts about one workgroup on every CU.  It depends on the BATCH, so results are re-associated between batch sizes (~1e-7) —
-            # which is why it is not the default: equal rank shards must reproduce the single-GPU batch bit for bit
-            cs = max(1, min(8, 256 // max(1, B * heads)))
-        ksplit = cs if (Q <= 128 and M >= 1024) else 1
-        ktiles = -(-M // (32 if xk else 64))               # key tiles of the kernel (32 keys for split pairs, 64 for fp16)
-        while ksplit > 1 and (ksplit - 1) * -(-ktiles // ksplit) >= ktiles:
-            ksplit -= 1                                    # the largest split that leaves no workgroup without keys (a function of M only)
+        # cross-attention: the keys can be split over workgroups + a merge launch (shape_rules.cross_attention_key_split: by the ENGINE
+        # INSTANCE's `cross_ksplit`, and by the batch only under "auto").  Image i's result is bitwise independent of its position in the
+        # batch and of the other images, and bitwise equal across batch sizes that fall on the same side of every batch-reading rule of
+        # DESIGN 3b (split-K rows, key-split items, the long-sequence split, skinny rows); across one the sums are re-associated: ~1e-7
+        # on tokens, ~5e-7 on masks (tests/test_e2e_gpu.py::test_batch_invariance_full_size).
+        ksplit = shape_rules.cross_attention_key_split(self.cross_ksplit, B, heads, Q, M, xk)
         attn_ws = None
         if ksplit > 1:
             attn_ws = self._buf("attn_ws", (ops.attention_splitk_workspace_size(B, heads, Q, dh, ksplit),), torch.uint8)
@@ -487,11 +420,11 @@ class _EngineBase:
         # accumulator start value (the `pos` form): with large query embeddings the table dwarfs the products and every MFMA
         # then accumulates at the table's ulp — measured 0.05 on the mask proposals of the config-3 fixture (queries x20)
 
+        dqkv = self._qkv_views(qkv16, D)
+
         def self_attention_block(pp, src16, residual, norm_out32, norm_out16):
             self._gemm("dec", src16, W_[pp + "sa_qkv_w"], qkv16, residual=W_[pp + "sa_tab"], res_rows=Q)   # q | k | v in ONE N = 3D GEMM
-            ops.attention(qkv16, qkv16.view(qkv16.hi[:, D:]), qkv16.view(qkv16.hi[:, 2 * D:]), o16, batch=B, heads=heads, Tq=Q, Tk=Q,
-                          head_dim=dh, ldq=3 * D, ldk=3 * D, ldv=3 * D, ldo=D, strideQ=Q * 3 * D, strideK=Q * 3 * D, strideV=Q * 3 * D,
-                          strideO=Q * D, x3=xd)
+            self._attention_packed(dqkv, o16, B, Q, D, heads, x3=xd)
             self._gemm("dec", o16, W_[pp + "sa_o_w"], t1, bias=W_[pp + "sa_o_b"], residual=residual)
             ops.layernorm(t1, W_[pp + "norm1.w"], W_[pp + "norm1.b"], 1e-5, R, D, out_f32=norm_out32, out_f16=norm_out16, status=st)
         # tgt = zeros (zutis.py:164) and query_pos is a parameter, so layer 0's whole self-attention block — projections of
@@ -524,11 +457,10 @@ class _EngineBase:
             self._gemm("dec", tgt16, W_[pp + "l1_w"], ff16, bias=W_[pp + "l1_b"], act=ops.ACT_RELU)
             # linear2 (:289-290; K = 2048): in the few-row regime its K is split over workgroups (a batched GEMM over K slabs) and the
             # planes meet in the LayerNorm below, with the bias and the residual (20.9 -> ~10 us for 100 queries)
-            s_l2 = self._splitk(R, D, Ff) if xd else 1
+            s_l2 = shape_rules.gemm_k_split(R, Ff) if xd else 1
             if s_l2 > 1:
                 l2p = self._buf("dec_l2_parts", (s_l2, R, D), f32)
-                self._gemm("dec", ff16, W_[pp + "l2_w"], l2p, M=R, N=D, K=Ff // s_l2, lda=Ff, ldw=Ff, ldc=D, batch=s_l2, strideA=Ff // s_l2,
-                           strideW=Ff // s_l2, strideC=R * D)
+                self._gemm_kslabs("dec", ff16, W_[pp + "l2_w"], l2p, s_l2)
                 src = dict(parts=l2p, n_parts=s_l2, bias=W_[pp + "l2_b"], residual=tgt)
             else:
                 self._gemm("dec", ff16, W_[pp + "l2_w"], t1, bias=W_[pp + "l2_b"], residual=tgt)
@@ -543,6 +475,6 @@ class _EngineBase:
             ops.sum_layernorm(src.pop("parts"), src.pop("n_parts"), R, D, **src, **n3, status=st)
         return inter16
 
-    cross_ksplit = int(os.environ.get("ZH_CROSS_KSPLIT", "1"))      # class default (env = developer override); instances may set it
+    cross_ksplit = shape_rules.CROSS_KSPLIT_DEFAULT     # class default; instances and the drop-in modules set their own (an int or "auto")
 
     _dec_out_sites = ("ffn2",)   # sites consuming the decoder's normed outputs (ZUTIS: ffn2; SelfMask: mask einsum + objectness MLP)

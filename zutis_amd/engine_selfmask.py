@@ -20,7 +20,7 @@ class SelfMaskEngine(_EngineBase):
 
     _dec_out_sites = ("mask", "ffn2")
     # 20 queries against ~5500 memory tokens, 6 heads, batches of 1 - 8: the cross-attention is 6 .. 48 workgroups of 172 key tiles
-    # each; its keys are split 8 ways (engine_base._decoder: a property of the engine, never of the batch)
+    # each; its keys are split 8 ways (shape_rules.cross_attention_key_split: an integer setting is a property of the engine, never of the batch)
     cross_ksplit = 8
 
     def __init__(self, params: Dict[str, torch.Tensor], patch: int = 8, heads: int = 6, precision="exact"):

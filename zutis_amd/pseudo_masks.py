@@ -85,7 +85,11 @@ def save_rle_json(mask: np.ndarray, path: str) -> Dict:
 def generate_pseudo_masks_batched(engine: SelfMaskEngine, images: Sequence[torch.Tensor], original_sizes: Sequence[Tuple[int, int]],
                                   out_paths: Sequence[str], bilateral_solver: bool = True, batch_size: int = 8) -> List[str]:
     """generate_pseudo_masks with images grouped by shape (consecutive images of one H x W, up to batch_size) so that SelfMask
-    and the solver run batched.  Output files are identical to the batch-1 path (tests/test_bilateral_gpu.py)."""
+    and the solver run batched.  A group's files are bit for bit those of the batch-1 path when the group's size and one image fall on
+    the same side of every batch-reading rule of zutis_amd/shape_rules.py.  They do not at the working shape: at 512x683 (T = 5505)
+    the encoder's key split is 5 / 4 / 2 / 1 for groups of 1 / 2 / 4 / 8 (shape_rules.long_sequence_key_split), so the fp32 sums of an
+    image are re-associated (~1e-7) with the size of its group — the ragged last group included — and a file then equals the batch-1
+    file only while no soft mask value or objectness logit lies that close to its threshold (tests/test_bilateral_gpu.py)."""
     i, n = 0, len(images)
     while i < n:
         j = i + 1
