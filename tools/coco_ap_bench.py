@@ -5,6 +5,13 @@ end (arm D), its three kernels alone by HIP events, and the dense-mask NumPy ref
 The two arms' stats are compared for equality.
 
     python tools/coco_ap_bench.py [--images N] [--rounds R] [--arm D|R ...] [--chunk-mb M ...] [--out profiles/coco_ap_ab.json]
+
+--gt polygons: the ground truth as annotation files carry it — seeded star-shaped polygons (8 - 80 vertices, radius 10 - 120 px, 1 - 3
+per annotation, 1 - 15 annotations per image, default 400 images) — and mask_ap's two routes for them, polygons="host"
+(rle.from_polygons per annotation: the parent's only route) and polygons="device" (zh_polygon_runs for the whole file), alternated in
+one process: mask_ap end to end, the polygon stage alone, the kernel by HIP events, the annotations left to the host.
+
+    python tools/coco_ap_bench.py --gt polygons [--images N] [--rounds R] [--out profiles/coco_polygon_ab.json]
 """
 import argparse
 import json
@@ -74,6 +81,84 @@ def corpus(n_images, seed=0):
     return ann, preds
 
 
+def star(rng):
+    k = int(rng.integers(8, 81))
+    r = float(rng.uniform(10, 120))
+    cx, cy = float(rng.uniform(0, W)), float(rng.uniform(0, H))
+    ang = np.sort(rng.uniform(0, 2 * np.pi, k))
+    rad = r * rng.uniform(.6, 1.0, k)
+    return np.round(np.stack([cx + rad * np.cos(ang), cy + rad * np.sin(ang)], axis=1), 2).reshape(-1).tolist(), (cy, cx, r)
+
+
+def polygon_corpus(n_images, seed=0, n_det=20):
+    """Polygon ground truth (no `area` field: COCOeval's comes from the mask, so does prepare's), RLE detections around it."""
+    rng = np.random.default_rng(seed)
+    import ctypes
+    from zutis_amd import _lib
+    lib, buf = _lib.load(raw=True), ctypes.create_string_buffer(1 << 16)
+    ann = {"images": [{"id": i + 1, "height": H, "width": W} for i in range(n_images)],
+           "categories": [{"id": c + 1, "name": f"c{c}"} for c in range(N_CAT)], "annotations": []}
+    preds = []
+    for i in range(n_images):
+        shapes = []
+        for _ in range(int(rng.integers(1, MAX_GT + 1))):
+            stars = [star(rng) for _ in range(int(rng.integers(1, 4)))]
+            cat = int(rng.integers(1, N_CAT + 1))
+            shapes.append((stars[0][1], cat))
+            ann["annotations"].append({"id": len(ann["annotations"]) + 1, "image_id": i + 1, "category_id": cat,
+                                       "segmentation": [p for p, _ in stars], "iscrowd": 0})
+        for _ in range(n_det):
+            (cy, cx, r), cat = shapes[int(rng.integers(0, len(shapes)))]
+            c = np.ascontiguousarray(blob_counts(rng, int(cy) + int(rng.integers(-6, 7)), int(cx) + int(rng.integers(-6, 7)), max(2, int(.8 * r)), max(2, int(.8 * r))), dtype=np.int64)
+            if c.size < 2:
+                c = np.asarray([0, 1, H * W - 1], dtype=np.int64)
+            n = lib.zh_rle_counts_to_string_host(c.ctypes.data, c.size, ctypes.addressof(buf), len(buf))
+            assert n >= 0
+            preds.append({"image_id": i + 1, "category_id": cat, "score": float(rng.random()), "segmentation": {"size": [H, W], "counts": buf.raw[:n]}})
+    return ann, preds
+
+
+def polygon_main(a):
+    import torch
+    dev = torch.device("cuda:0")
+    t0 = time.perf_counter()
+    ann, preds = polygon_corpus(a.images)
+    n_poly = sum(len(x["segmentation"]) for x in ann["annotations"])
+    print(f"corpus: {a.images} images, {len(ann['annotations'])} polygon annotations of {n_poly} polygons, {len(preds)} detections "
+          f"({time.perf_counter() - t0:.1f} s)", flush=True)
+    coco_eval.mask_ap_route({**ann, "annotations": ann["annotations"][:8]}, [p for p in preds if p["image_id"] == 1], device=dev)     # warm-up
+    rec = {r: {"mask_ap_s": [], "polygon_s": [], "kernel_ms": [], "host_fallback": []} for r in ("host", "device")}
+    stats = {}
+    for r in range(a.rounds):
+        for route in ("host", "device"):
+            tm = {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = coco_eval.mask_ap_route(ann, preds, polygons=route, device=dev, timings=tm)
+            rec[route]["mask_ap_s"].append(time.perf_counter() - t0)
+            rec[route]["polygon_s"].append(tm["polygon_s"])
+            rec[route]["kernel_ms"].append(sum(e0.elapsed_time(e1) for _, e0, e1 in tm["events"]))
+            rec[route]["host_fallback"].append(tm["stats"]["host_fallback"])
+            for k in ("stats", "precision", "recall"):
+                assert np.array_equal(stats.setdefault(k, res[k]), res[k]), (route, r, k)        # both routes, every round: the same bits
+        print(f"round {r}: " + ", ".join(f"{rt} {rec[rt]['mask_ap_s'][-1]:.3f} s (polygons {rec[rt]['polygon_s'][-1]:.3f} s)" for rt in rec), flush=True)
+    assert rec["device"]["host_fallback"] == [0] * a.rounds, rec["device"]["host_fallback"]
+    out = {"tool": "tools/coco_ap_bench.py --gt polygons", "images": a.images, "size": [H, W], "annotations": len(ann["annotations"]),
+           "polygons": n_poly, "detections": len(preds), "rounds": a.rounds, "stats": [float(s) for s in stats["stats"]],
+           "routes_equal_in_every_bit": True}
+    for rt, d in rec.items():
+        out[rt] = {"mask_ap_s": med(d["mask_ap_s"]), "polygon_stage_s": med(d["polygon_s"]), "host_fallback": d["host_fallback"]}
+    out["device"]["zh_polygon_runs_ms"] = med(rec["device"]["kernel_ms"])
+    out["mask_ap_host_over_device"] = out["host"]["mask_ap_s"]["median"] / out["device"]["mask_ap_s"]["median"]
+    out["polygon_stage_host_over_device"] = out["host"]["polygon_stage_s"]["median"] / out["device"]["polygon_stage_s"]["median"]
+    out["device_ahead_in_every_round"] = bool(all(d < h for d, h in zip(rec["device"]["mask_ap_s"], rec["host"]["mask_ap_s"])))
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+
+
 def reference_arm(ann, preds):
     """tests/_cocoeval_ref.py on the corpus: the masks of one image at a time are decoded to pixels (the whole corpus would be 17 GB)."""
     cats = [c["id"] for c in ann["categories"]]
@@ -120,12 +205,17 @@ def med(v):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--images", type=int, default=500)
+    ap.add_argument("--gt", default="rle", choices=["rle", "polygons"])
+    ap.add_argument("--images", type=int, default=None, help="default: 500 (--gt rle), 400 (--gt polygons)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--arm", nargs="+", default=["D", "R"], choices=["D", "R"])
     ap.add_argument("--chunk-mb", type=int, nargs="+", default=[coco_eval.CHUNK_BYTES >> 20])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.gt == "polygons":
+        a.images = 400 if a.images is None else a.images
+        return polygon_main(a)
+    a.images = 500 if a.images is None else a.images
     import torch
     dev = torch.device("cuda:0")
     t0 = time.perf_counter()

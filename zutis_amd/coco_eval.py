@@ -7,6 +7,10 @@ greedy matching per (group, area range, IoU threshold) — runs on the device in
 zh_rle_prefix, zh_rle_pair_iou, zh_coco_match) on the masks' run lengths, which is what the prediction dicts already carry: no mask is
 ever rasterised.  Grouping, the score sorts, accumulate and summarize are NumPy float64 on the host (prepare / accumulate / summarize):
 they touch flags and scores only.  There is no CPU path for the device part: mask_ap needs a GPU.
+
+Polygon segmentations (what annotation files carry for everything but crowds) are converted to run counts for the whole file in one
+more launch before prepare (zutis_amd/polygons.py, csrc/polygon.hip: zh_polygon_runs), with rle.from_polygons' counts exactly;
+mask_ap_route(..., polygons="host") keeps the per-annotation host conversion.
 """
 from __future__ import annotations
 
@@ -54,27 +58,51 @@ def _load(x):
     return x
 
 
-def _segmentation_counts(seg, image):
+def _segmentation_counts(seg, image, counts=None):
     """(run counts, h, w) of a segmentation in any form annotation files carry: compressed RLE (counts bytes / str), uncompressed RLE
-    (counts a list), or a list of polygons (rasterised by rle.from_polygons at the image's size)."""
+    (counts a list), or a list of polygons (rasterised by rle.from_polygons at the image's size, unless the caller already holds its
+    `counts`: zutis_amd/polygons.py converts a file's polygons in one launch)."""
     if isinstance(seg, dict):
         h, w = (int(v) for v in seg["size"])
         return rle.counts_np(seg["counts"]), h, w
     if image is None:
         raise ValueError("a polygon segmentation needs its image's height and width")
     h, w = int(image["height"]), int(image["width"])
+    if counts is not None:
+        return np.asarray(counts, dtype=np.int64), h, w
     return rle.counts_np(rle.from_polygons(seg, h, w)["counts"]), h, w
 
 
+def polygon_segmentations(ground_truth, predictions, image_ids: Optional[Sequence] = None):
+    """The polygon segmentations prepare() would rasterise: ([key], [(polygons, h, w)]) with key = ("annotation", j) or ("prediction",
+    j), j the position in the annotations' / predictions' list — the keys of prepare's polygon_counts.  One whose image is not listed
+    is left out (prepare raises for it if it is ever read)."""
+    gt, preds = _load(ground_truth), _load(predictions)
+    images = {im["id"]: im for im in gt["images"]}
+    chosen = None if image_ids is None else set(np.asarray(list(image_ids)).tolist())
+    keys, items = [], []
+    for kind, rows in (("annotation", gt["annotations"]), ("prediction", preds)):
+        for j, a in enumerate(rows):
+            im = images.get(a["image_id"])
+            if isinstance(a["segmentation"], dict) or im is None or (chosen is not None and a["image_id"] not in chosen):
+                continue
+            keys.append((kind, j))
+            items.append((a["segmentation"], int(im["height"]), int(im["width"])))
+    return keys, items
+
+
 def prepare(ground_truth, predictions, *, use_categories: bool = True, max_dets: Sequence[int] = (1, 10, 100),
-            image_ids: Optional[Sequence] = None) -> Problem:
+            image_ids: Optional[Sequence] = None, polygon_counts: Optional[Dict] = None) -> Problem:
     """COCO.loadRes + COCOeval._prepare + the per-group ordering of computeIoU / evaluateImg, on the host.
 
     Groups are (image, category) with use_categories, else (image) with its annotations in category order, as COCOeval gathers them.
     Detections get the ids 1, 2, ... in input order (loadRes); a group's detections are ordered by -score (stable) and cut to
     max_dets[-1]; a ground truth is ignored in an area range when it is a crowd, when its `ignore` is set, or when its `area` field lies
-    outside the range; per range the ground truths are ordered ignored-last (stable)."""
+    outside the range; per range the ground truths are ordered ignored-last (stable).  polygon_counts: {("annotation", j) / ("prediction",
+    j): run counts} of polygon segmentations converted beforehand (polygon_segmentations' keys); any other polygon goes through
+    rle.from_polygons here."""
     gt, preds = _load(ground_truth), _load(predictions)
+    polygon_counts = polygon_counts or {}
     max_dets = tuple(int(m) for m in max_dets)
     if len(max_dets) < 3:
         raise ValueError("max_dets: the summary reads three entries (AR at max_dets[0], [1], [2]; every AP row at max_dets[2])")
@@ -105,14 +133,14 @@ def prepare(ground_truth, predictions, *, use_categories: bool = True, max_dets:
             g.det_id = np.asarray([d_idx[o] + 1 for o in order], dtype=np.int64)
             g.det_mask = []
             for o in order:
-                c, h, w = _segmentation_counts(preds[d_idx[o]]["segmentation"], images.get(i))
+                c, h, w = _segmentation_counts(preds[d_idx[o]]["segmentation"], images.get(i), polygon_counts.get(("prediction", d_idx[o])))
                 g.det_mask.append(len(prob.masks))
                 prob.masks.append((c, h * w))
                 prob.mask_names.append(f"prediction {d_idx[o]}")
             g.gt_mask, crowd, base, area = [], [], [], []
             for j in a_idx:
                 a = gt["annotations"][j]
-                c, h, w = _segmentation_counts(a["segmentation"], images.get(i))
+                c, h, w = _segmentation_counts(a["segmentation"], images.get(i), polygon_counts.get(("annotation", j)))
                 g.gt_mask.append(len(prob.masks))
                 prob.masks.append((c, h * w))
                 prob.mask_names.append(f"annotation {a.get('id', j)}")
@@ -366,17 +394,44 @@ def mask_ap(ground_truth, predictions, *, use_categories: bool = True, max_dets:
     evaluate / accumulate / summarize.
 
     ground_truth: a COCO annotation dict (images, annotations, categories) or the path of its JSON; an annotation's segmentation may be
-    a compressed RLE, an uncompressed RLE or a list of polygons.  predictions: the dicts predict(mask_type="instance") /
-    predict_from_files produce, or the path of the JSON trainer.py:393-398 dumps (image_id, category_id, score, segmentation
+    a compressed RLE, an uncompressed RLE or a list of polygons (converted on the device: mask_ap_route).  predictions: the dicts
+    predict(mask_type="instance") / predict_from_files produce, or the path of the JSON trainer.py:393-398 dumps (image_id, category_id, score, segmentation
     {"size", "counts" bytes or str}; anything else, bbox included, is not read).  device: the GPU to run on (None: the current one).
     Returns the twelve entries of trainer.compute_coco_metrics under its key names, "stats" float64 [12], "precision" float64
     [T = 10, R = 101, K, A = 4, M] and "recall" float64 [T, K, A, M] (K categories, or 1 without; M = len(max_dets))."""
+    return mask_ap_route(ground_truth, predictions, polygons="device", use_categories=use_categories, max_dets=max_dets,
+                         image_ids=image_ids, device=device)
+
+
+def mask_ap_route(ground_truth, predictions, *, polygons: str = "device", use_categories: bool = True,
+                  max_dets: Sequence[int] = (1, 10, 100), image_ids: Optional[Sequence] = None, device=None, timings=None) -> dict:
+    """mask_ap with the route of its polygon segmentations spelled out.  polygons="device" (what mask_ap takes): every polygon
+    segmentation of the annotations, and of the predictions should any carry one, is converted to run counts in ONE
+    polygons.runs_device call on `device` and handed to prepare; polygons="host": prepare rasterises each with rle.from_polygons.  The
+    two return the same dict, bit for bit.  timings (a dict, tools/coco_ap_bench.py): gets "polygon_s", the polygon stage's
+    "stats" and its launch's HIP "events"."""
+    import time
     import torch
+    if polygons not in ("device", "host"):
+        raise ValueError(f"polygons = {polygons!r}: \"device\" or \"host\"")
     if device is None:
         if not torch.cuda.is_available():
             raise _lib.ZutisHipError("mask_ap runs its IoU and matching kernels on the GPU (no CPU fallback)")
         device = torch.device("cuda", torch.cuda.current_device())
-    prob = prepare(ground_truth, predictions, use_categories=use_categories, max_dets=max_dets, image_ids=image_ids)
+    gt, preds = _load(ground_truth), _load(predictions)
+    t0 = time.perf_counter()
+    keys, items = polygon_segmentations(gt, preds, image_ids)
+    if polygons == "device" and items:
+        from . import polygons as _polygons
+        events = [] if timings is not None else None
+        counts, stats = _polygons.runs_device(items, device, events=events)
+        polygon_counts = dict(zip(keys, counts))
+    else:                                                    # the host route converts here what prepare would, to be timed alike
+        stats, events = {"annotations": len(items), "polygons": None, "host_fallback": len(items)}, []
+        polygon_counts = {k: rle.counts_np(rle.from_polygons(*it)["counts"]) for k, it in zip(keys, items)} if timings is not None else None
+    if timings is not None:
+        timings.update(polygon_s=time.perf_counter() - t0, stats=stats, events=events)
+    prob = prepare(gt, preds, use_categories=use_categories, max_dets=max_dets, image_ids=image_ids, polygon_counts=polygon_counts)
     precision, recall = accumulate(prob, match_on_device(prob, device))
     return result_dict(precision, recall, prob.max_dets)
 

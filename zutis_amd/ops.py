@@ -897,6 +897,24 @@ def mask_runs(masks_u8, sel, max_runs=8192):
     return pos, nr, ba
 
 
+POLYGON_LDS_CROSSINGS = 4096     # zh_polygon_lds_crossings(): crossings of one annotation's polygons the kernel sorts in LDS
+
+
+def polygon_runs(xs, ys, step_pref, vert_off, poly_off, hw, out_off, flags, counts, n_runs):
+    """zutis_amd/polygons.pack's arrays as int32 device tensors (xs, ys [V]; step_pref [V + P]; vert_off [P + 1]; poly_off, out_off
+    [A + 1]; hw [A, 2] or [2 A]; flags [A]) -> counts int32 [>= out_off[-1], the caller's figure] and n_runs int32 [A] (-1: left to
+    the host), written in place."""
+    for name, t in (("xs", xs), ("ys", ys), ("step_pref", step_pref), ("vert_off", vert_off), ("poly_off", poly_off), ("hw", hw),
+                    ("out_off", out_off), ("flags", flags), ("counts", counts), ("n_runs", n_runs)):
+        _chk(t, torch.int32, f"polygon_runs {name}")
+    A, P, V = n_runs.numel(), vert_off.numel() - 1, xs.numel()
+    if (P < 0 or ys.numel() != V or step_pref.numel() != V + P or poly_off.numel() != A + 1 or out_off.numel() != A + 1
+            or hw.numel() != 2 * A or flags.numel() != A):
+        raise _lib.ZutisHipError("polygon_runs: the arrays' lengths do not describe one packed batch (zutis_amd/polygons.pack)")
+    _call("zh_polygon_runs", _p(xs), _p(ys), _p(step_pref), _p(vert_off), _p(poly_off), _p(hw), _p(flags), _p(out_off), A, _p(counts),
+          _p(n_runs), _stream())
+
+
 # ---- training criterion (criterion.py::Criterion): zutis_amd/criterion.py
 
 def mask_match_cost(proposals, gt_u8, inst_off, n_max, H, W, costs, stat_p, stat_pg, stat_g, skip, status, weight_dice=1.0, weight_bce=1.0):
