@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 236 /* 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 237 /* 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -574,6 +574,27 @@ int zh_coco_match(const double* iou, const int* groups, int n_groups, const int*
 int zh_polygon_lds_crossings(void);
 int zh_polygon_runs(const int* xs, const int* ys, const int* step_pref, const int* vert_off, const int* poly_off, const int* hw,
                     const int* flags, const int* out_off, int n_annotations, int* counts, int* n_runs, zh_stream_t stream);
+/* Semantic ground truth from annotations (zutis_amd/annotation_labels.py): the label maps the COCO datasets open at
+ * {dir_dataset}/annotations/semantic_segmentation_masks/{stem}.png (datasets/coco2017.py:134, datasets/coco20k.py:178; the labels
+ * are the ranks of datasets/coco2017.py:152-244) for B images in one launch.  run_end / run_off / status: n_masks masks exactly as
+ * zh_rle_prefix leaves them (n_runs = run_off[n_masks]: the length of run_end).  Image b's paint list is list_mask / list_label
+ * [list_off[b] .. list_off[b + 1]) (list_off int32 [B + 1], the lists n_list entries long in all): the index of a mask and the label
+ * byte it paints, in paint order; hw int32 [B, 2] = (h, w); image b's map is u8 row-major [h, w] at out + out_off[b] (out_off int64
+ * [B + 1]; a same-size batch laid back to back is a [B, H, W] tensor), out_bytes the length of out.  A gather, one lane per pixel of
+ * a ZH_LABEL_TILE_W x ZH_LABEL_TILE_H tile: the pixel's column-major position x * h + y is searched in each entry's run ends, the last
+ * entry first, and is covered when the index of the first run end greater than it is odd.  ZH_OVERLAP_LAST: the label of the last
+ * entry that covers the pixel; ZH_OVERLAP_IGNORE: that label when exactly one entry covers it, ignore_value when two or more do; 0
+ * when none does.  No atomics: the bytes are the same every time.  No cap on a list's length or on a mask's runs.  A mask
+ * zh_rle_prefix flagged, an index outside 0 .. n_masks - 1 and a mask of fewer than two runs paint nothing; an image that does not
+ * lie inside out is not written.  max_tiles: at least ceil(w / ZH_LABEL_TILE_W) * ceil(h / ZH_LABEL_TILE_H) of every image (the
+ * grid's width: an image's pixels past it are not written); B <= 65535; B = 0 or max_tiles = 0 launches nothing. */
+#define ZH_OVERLAP_LAST 0
+#define ZH_OVERLAP_IGNORE 1
+#define ZH_LABEL_TILE_W 32
+#define ZH_LABEL_TILE_H 8
+int zh_runs_label_maps(const int* run_end, const int* run_off, const int* status, int n_masks, long n_runs, const int* list_off,
+                       const int* list_mask, const unsigned char* list_label, int n_list, const int* hw, const long long* out_off,
+                       int B, int max_tiles, int overlap, int ignore_value, unsigned char* out, long out_bytes, zh_stream_t stream);
 
 /* Native launch plans (zutis_amd/plan.py): replay n recorded calls of the entry points above (op id + 32 argument words
  * each; dispatcher generated from this header) in one C loop; zh_plan_run2 alternates two plans on two streams. */

@@ -76,12 +76,27 @@ def evaluate_from_files(network, p_images: Sequence[str], p_gts: Sequence[str], 
     p_images, p_gts = list(p_images), list(p_gts)
     if len(p_images) != len(p_gts):
         raise ValueError("evaluate_from_files: one ground-truth file per image")
+
+    def source(dev):
+        loader = preprocess.EvalBatchLoader(p_images, p_gts, max_size, batch_size, max(1, min(int(n_workers), MAX_THREADS)), window=window,
+                                            gt_format=gt_format)
+        return loader, lambda batch, views: views[2]                                    # the PNG's bytes, as they arrived with the images
+
+    return _evaluate(network, "evaluate_from_files", p_images, n_categories, source, gt_format=gt_format, mean=mean, std=std,
+                     instance=instance, image_ids=image_ids, new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type,
+                     return_labels=return_labels, coco_annotations=coco_annotations)
+
+
+def _evaluate(network, who: str, p_images: List[str], n_categories: int, source, *, gt_format, mean, std, instance, image_ids,
+              new_label_id_to_old_label_id, nms_type, return_labels, coco_annotations) -> dict:
+    """The loop evaluate_from_files and evaluate_from_annotations share.  source(dev) -> (the batch loader, ground_truth(batch, views) ->
+    the batch's ground truth on the device: u8 [B, H, W], or [B, H, W, 3] with gt_format "rg16"); it is called only when there are images."""
     if image_ids is not None and len(image_ids) != len(p_images):
-        raise ValueError("evaluate_from_files: one image id per image")
-    _require_dropin(network, "evaluate_from_files")
+        raise ValueError(f"{who}: one image id per image")
+    _require_dropin(network, who)
     n = int(n_categories)
     if network.text_embeddings.shape[0] != n:
-        raise ValueError(f"evaluate_from_files: the network holds {network.text_embeddings.shape[0]} text embeddings, n_categories is {n}")
+        raise ValueError(f"{who}: the network holds {network.text_embeddings.shape[0]} text embeddings, n_categories is {n}")
     eng = network._get_engine()
     dev = eng._device()
     hist = torch.zeros((n * n,), dtype=torch.int64, device=dev)
@@ -89,14 +104,14 @@ def evaluate_from_files(network, p_images: Sequence[str], p_gts: Sequence[str], 
     labels_out: Optional[Dict[int, np.ndarray]] = {} if return_labels else None
     if p_images:
         lut = torch.from_numpy(preprocess.normalise_table(mean, std)).to(dev)
-        loader = preprocess.EvalBatchLoader(p_images, p_gts, max_size, batch_size, max(1, min(int(n_workers), MAX_THREADS)), window=window,
-                                            gt_format=gt_format)
+        loader, ground_truth = source(dev)
         with preprocess.device_batches(loader, dev, preprocess.resize_normalize_of(lut)) as steps:
-            for batch, (_, _, gt), x in steps:
+            for batch, views, x in steps:
                 B, (H, W) = len(batch.paths), batch.size_hw
                 out = network(x)                                                       # the module's forward: its hipGraph replay applies
                 labels = torch.empty((B, H, W), dtype=torch.int64, device=dev) if return_labels else None
-                eng.score_semantic(out["patch_tokens"], network.text_embeddings, gt, hist, gt_format=gt_format, size=(H, W), labels=labels)
+                eng.score_semantic(out["patch_tokens"], network.text_embeddings, ground_truth(batch, views), hist, gt_format=gt_format,
+                                   size=(H, W), labels=labels)
                 if instance:
                     collect_instance_predictions(network, out, batch, image_ids, per_image,
                                                  new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type)
@@ -112,6 +127,46 @@ def evaluate_from_files(network, p_images: Sequence[str], p_gts: Sequence[str], 
         from . import coco_eval
         res["coco_metrics"] = coco_eval.mask_ap(coco_annotations, res["instance_predictions"], image_ids=image_ids, device=dev)
     return res
+
+
+@torch.no_grad()
+def evaluate_from_annotations(network, p_images: Sequence[str], coco_annotations, n_categories: int, *, image_ids: Sequence,
+                              max_size: Optional[int] = None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), batch_size: int = 4,
+                              n_workers: int = 16, window: int = 512, instance: bool = False,
+                              new_label_id_to_old_label_id: Optional[Dict[int, int]] = None, nms_type: Optional[str] = "hard",
+                              return_labels: bool = False, label_of: Optional[Dict[int, int]] = None, order: str = "file",
+                              overlap: str = "last", crowd: str = "label", ignore_value: int = 255) -> dict:
+    """evaluate_from_files without ground-truth files: the semantic ground truth of each batch is painted on the device from the COCO
+    annotation file (annotation_labels.LabelPainter.paint: one launch per batch) where the PNG's bytes used to arrive — no ground-truth
+    PNG, decode or host-to-device copy.  coco_annotations: the annotation dict or the path of its JSON (`instances_*.json`); image_ids:
+    the COCO id of every image of p_images (the `images` entry gives the size the file must have); label_of / order / overlap / crowd /
+    ignore_value: annotation_labels.paint_plan's; the other keywords and the result are evaluate_from_files'.  The segmentations are
+    converted once, before the first batch.  The batches are the ones evaluate_from_files forms for the same files, batch_size and window
+    (preprocess.PredictBatchLoader), so the scores are those of evaluate_from_files over annotation_labels.write_semantic_masks' PNGs,
+    count for count.  instance=True: the same annotation dict goes to coco_eval.mask_ap and the result gains "coco_metrics"."""
+    from . import annotation_labels, coco_eval
+    p_images = list(p_images)
+    if image_ids is None or len(image_ids) != len(p_images):
+        raise ValueError("evaluate_from_annotations: one image id per image")
+    image_ids = list(image_ids)
+    gt = coco_eval._load(coco_annotations)
+    plan = annotation_labels.paint_plan(gt, image_ids, label_of=label_of, order=order, overlap=overlap, crowd=crowd, ignore_value=ignore_value)
+
+    def source(dev):
+        painter = annotation_labels.LabelPainter(plan, dev)
+        loader = preprocess.PredictBatchLoader(p_images, max_size, batch_size, max(1, min(int(n_workers), MAX_THREADS)), window=window)
+
+        def ground_truth(batch, views):
+            for i in batch.indices:
+                if (plan.images[i]["h"], plan.images[i]["w"]) != tuple(batch.size_hw):
+                    raise ValueError(f"{p_images[i]}: a file of {tuple(batch.size_hw)} pixels, the annotations give image "
+                                     f"{plan.images[i]['id']!r} as {(plan.images[i]['h'], plan.images[i]['w'])}")
+            return painter.paint(batch.indices)
+        return loader, ground_truth
+
+    return _evaluate(network, "evaluate_from_annotations", p_images, n_categories, source, gt_format="u8", mean=mean, std=std,
+                     instance=instance, image_ids=image_ids, new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type,
+                     return_labels=return_labels, coco_annotations=gt if instance else None)
 
 
 def eval_files_of(dataset):
@@ -138,3 +193,15 @@ def eval_files_of(dataset):
         raise TypeError("eval_files_of: coca's __getitem__ maps the mask's 255 to the label of the file's directory (datasets/coca.py:42-43): "
                         "its ground truth is not one of the two file formats")
     raise TypeError(f"eval_files_of: no path rules for the dataset {name!r} ({type(dataset).__name__})")
+
+
+def eval_annotations_of(dataset):
+    """(p_images, p_annotations, image_ids) for evaluate_from_annotations from one of the reference's COCO validation dataset objects, by
+    its `name` and the attributes its __init__ / __getitem__ use: get_image_path(image_id) over image_ids (datasets/coco2017.py:124-126,
+    coco20k.py:168-170) and p_annotations, the file its COCO object was read from (coco2017.py:22, coco20k.py:20).  TypeError for
+    anything else, as eval_files_of."""
+    name = getattr(dataset, "name", None)
+    if name not in ("coco2017", "coco20k"):
+        raise TypeError(f"eval_annotations_of: no annotation file rules for the dataset {name!r} ({type(dataset).__name__})")
+    image_ids = list(dataset.image_ids)
+    return [dataset.get_image_path(i) for i in image_ids], str(dataset.p_annotations), image_ids

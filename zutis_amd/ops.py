@@ -915,6 +915,59 @@ def polygon_runs(xs, ys, step_pref, vert_off, poly_off, hw, out_off, flags, coun
           _p(n_runs), _stream())
 
 
+def rle_prefix(counts, run_off, hw, run_end, run_fg, area, status):
+    """zh_rle_prefix of n masks whose run counts lie on the device: counts int32 [R] (mask m's at run_off[m] .. run_off[m + 1] - 1,
+    run_off int32 [n + 1]), hw int32 [n] = h * w -> run_end, run_fg int32 [R], area int32 [n], and the masks' bits ORed into status int32
+    [(n + 31) // 32] (zeroed by the caller), written in place."""
+    for name, t in (("counts", counts), ("run_off", run_off), ("hw", hw), ("run_end", run_end), ("run_fg", run_fg), ("area", area),
+                    ("status", status)):
+        _chk(t, torch.int32, f"rle_prefix {name}")
+    n = hw.numel()
+    if (run_off.numel() != n + 1 or area.numel() != n or status.numel() < (n + 31) // 32 or run_end.numel() != counts.numel()
+            or run_fg.numel() != counts.numel()):
+        raise _lib.ZutisHipError("rle_prefix: the arrays' lengths do not describe n masks and their runs")
+    if n:
+        _call("zh_rle_prefix", _p(counts), _p(run_off), _p(hw), n, _p(run_end), _p(run_fg), _p(area), _p(status), _stream())
+
+
+OVERLAP_MODES = {"last": 0, "ignore": 1}      # ZH_OVERLAP_LAST / ZH_OVERLAP_IGNORE
+LABEL_TILE_W, LABEL_TILE_H = 32, 8            # ZH_LABEL_TILE_W / ZH_LABEL_TILE_H
+
+
+def label_tiles(h: int, w: int) -> int:
+    """Workgroups zh_runs_label_maps spends on an h x w image."""
+    return -(-int(w) // LABEL_TILE_W) * -(-int(h) // LABEL_TILE_H) if h > 0 and w > 0 else 0
+
+
+def runs_label_maps(run_end, run_off, status, list_off, list_mask, list_label, hw, out_off, out, max_tiles, overlap="last",
+                    ignore_value=255):
+    """The label maps of B images in one launch (zh_runs_label_maps).  run_end int32 [R], run_off int32 [n + 1], status int32 [>= (n + 31)
+    // 32]: n masks as rle_prefix leaves them; list_off int32 [B + 1], list_mask int32 [N], list_label u8 [N]: the images' paint lists;
+    hw int32 [B, 2] = (h, w); out_off int64 [B + 1]; out u8 (any shape, contiguous): image b's [h, w] map at out_off[b] of its bytes;
+    max_tiles: the largest label_tiles(h, w) of the batch (the caller holds hw on the host).  Everything on the device; nothing is
+    copied.  Returns out."""
+    for name, t in (("run_end", run_end), ("run_off", run_off), ("status", status), ("list_off", list_off), ("list_mask", list_mask),
+                    ("hw", hw)):
+        _chk(t, torch.int32, f"runs_label_maps {name}")
+    _chk(list_label, torch.uint8, "runs_label_maps list_label")
+    _chk(out_off, torch.int64, "runs_label_maps out_off")
+    _chk(out, torch.uint8, "runs_label_maps out")
+    if overlap not in OVERLAP_MODES:
+        raise _lib.ZutisHipError(f"runs_label_maps: overlap {overlap!r} is not one of {sorted(OVERLAP_MODES)}")
+    if not 0 <= int(ignore_value) <= 255:
+        raise _lib.ZutisHipError(f"runs_label_maps: ignore_value {ignore_value!r} is not a byte")
+    B, n, N = list_off.numel() - 1, run_off.numel() - 1, list_mask.numel()
+    if B < 0 or n < 0 or hw.numel() != 2 * B or out_off.numel() != B + 1 or list_label.numel() != N or status.numel() < (n + 31) // 32:
+        raise _lib.ZutisHipError("runs_label_maps: the arrays' lengths do not describe B images, their lists and n masks")
+    if B > 65535:
+        raise _lib.ZutisHipError(f"runs_label_maps: {B} images in one launch, at most 65535")
+    if B and int(max_tiles) > 0:
+        _call("zh_runs_label_maps", _p(run_end) if run_end.numel() else None, _p(run_off), _p(status), n, run_end.numel(), _p(list_off),
+              _p(list_mask) if N else None, _p(list_label) if N else None, N, _p(hw), _p(out_off), B, int(max_tiles), OVERLAP_MODES[overlap],
+              int(ignore_value), _p(out), out.numel(), _stream())
+    return out
+
+
 # ---- training criterion (criterion.py::Criterion): zutis_amd/criterion.py
 
 def mask_match_cost(proposals, gt_u8, inst_off, n_max, H, W, costs, stat_p, stat_pg, stat_g, skip, status, weight_dice=1.0, weight_bce=1.0):

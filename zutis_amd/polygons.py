@@ -214,8 +214,9 @@ def runs_device(annotations: Sequence[Tuple], device=None, events=None):
     return res, stats
 
 
-def _runs_chunk(annotations, device, events, res, stats):
-    """One launch of runs_device: appends the chunk's counts to `res` and adds to `stats`."""
+def _launch_chunk(annotations, device, events, stats):
+    """pack() of one chunk, ONE host-to-device copy of its arrays and zh_polygon_runs: (pk, out) with out int32 [cap + A] on the device,
+    the counts in out[:cap] at pk["out_off"], n_runs in out[cap:].  Adds the chunk's polygons to `stats`."""
     import torch
     from . import ops
     from .coco_eval import _sections
@@ -236,7 +237,14 @@ def _runs_chunk(annotations, device, events, res, stats):
         if events is not None:
             e1.record()
             events.append(("zh_polygon_runs", e0, e1))
-        h_out = out.cpu().numpy()                                                        # the one copy back
+    return pk, out
+
+
+def _runs_chunk(annotations, device, events, res, stats):
+    """One launch of runs_device: appends the chunk's counts to `res` and adds to `stats`."""
+    pk, out = _launch_chunk(annotations, device, events, stats)
+    A, cap = len(annotations), int(pk["out_off"][-1])
+    h_out = out.cpu().numpy()                                                            # the one copy back
     n_runs, off = h_out[cap:], pk["out_off"]
     for a in range(A):
         if n_runs[a] < 0:
@@ -244,6 +252,41 @@ def _runs_chunk(annotations, device, events, res, stats):
             res.append(_host_counts(annotations[a]))
         else:
             res.append(h_out[off[a]:off[a] + n_runs[a]].astype(np.int64))
+
+
+def runs_resident(annotations: Sequence[Tuple], device=None, events=None):
+    """runs_device with the counts left on the device: ([(counts int32 [R_c] on the device, n_runs int64 [A_c] on the host)] per chunk of
+    CHUNK_ANNOTATIONS annotations, {chunk-wide annotation index: int64 host counts} of those left to the host, stats).  Per chunk pack()
+    and the launch of runs_device, then only n_runs crosses to the host (4 bytes an annotation) and the capacity-sized output is
+    compacted to the runs actually written — annotation a's n_runs[a] counts follow those of a - 1, an annotation left to the host
+    (n_runs -1, filled from rle.from_polygons in the dict) takes no place — so what stays resident is the runs, not out_off[-1] slots."""
+    import torch
+    from . import _lib
+    if device is None:
+        if not torch.cuda.is_available():
+            raise _lib.ZutisHipError("polygons.runs_resident runs on the GPU (rle.from_polygons is the host form)")
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.ZutisHipError("polygons.runs_resident runs on the GPU (rle.from_polygons is the host form)")
+    annotations = list(annotations)
+    chunks, host, stats = [], {}, {"annotations": len(annotations), "polygons": 0, "host_fallback": 0}
+    for lo in range(0, len(annotations), CHUNK_ANNOTATIONS):
+        part = annotations[lo:lo + CHUNK_ANNOTATIONS]
+        pk, out = _launch_chunk(part, device, events, stats)
+        A, cap = len(part), int(pk["out_off"][-1])
+        n_runs = out[cap:].cpu().numpy().astype(np.int64)                                # 4 bytes an annotation: the counts stay
+        for a in np.flatnonzero(n_runs < 0):
+            stats["host_fallback"] += 1
+            host[lo + int(a)] = _host_counts(part[a])
+        kept = np.maximum(n_runs, 0)
+        start = np.concatenate(([0], np.cumsum(kept)))[:-1]
+        with torch.cuda.device(device):                                                  # the gather that compacts: index plumbing, no arithmetic on the counts
+            shift = torch.repeat_interleave(torch.from_numpy(pk["out_off"][:-1].astype(np.int64) - start).to(device),
+                                            torch.from_numpy(kept).to(device), output_size=int(kept.sum()))
+            src = torch.arange(shift.numel(), dtype=torch.int64, device=device) + shift
+            chunks.append((out[:cap][src] if src.numel() else torch.zeros(0, dtype=torch.int32, device=device), n_runs))
+    return chunks, host, stats
 
 
 def to_rles(annotations: Sequence[Tuple], device=None) -> List[Dict]:
