@@ -912,7 +912,10 @@ extern "C" int zh_mask_rle_fused_kept(const unsigned char* masks, const unsigned
 //                   else 1; gaussian: exp(-IoU^2 / sigma); drop those with s <= score_threshold
 //     emitted entries whose mask is empty are skipped (zutis.py:281-282).
 // Scores are carried in float64: the reference's float32 scores are promoted by the first float64 weight (linear / gaussian)
-// and stay float32 under hard NMS, where the only products are x1 / x0 — both representations agree exactly.
+// and stay float32 under hard NMS, where the only products are x1 / x0 — both representations hold the same values, and every
+// comparison agrees except one: a score equal to float32(score_threshold).  float32(0.001) is 0.0010000000475 as a double, so
+// `s > score_thr` here, in float64, KEEPS such a candidate; the reference's float32 score against a Python float drops it under
+// NumPy 2 promotion (both sides become float32(0.001)) and keeps it under NumPy 1 (value-based: compared in float64).
 #define NMS_MAXQ 1024
 __global__ __launch_bounds__(256) void mask_nms_kernel(const int* inter, const int* uni, const float* scores, const long long* cats,
                                                        int Q, int nms_type, double thr, double sigma, double score_thr,
