@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 237 /* 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 238 /* 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -56,6 +56,18 @@ const char* zh_last_error(void);
  * 5122 / 5124 = the planeW = 0 form of 512 on two slots / as 2 x 4 waves of 128 x 64, 4484 = of 448 as 4 x 2 waves of 48 x 128), 0 = the cost model's choice; tile_small = the same, applied to M <= 4096 only.  Process-wide;
  * the initial values come from ZH_GEMM_GROUP_M / ZH_GEMM_TILE / ZH_GEMM_TILE_SMALL, read once. */
 int zh_dev_set_gemm_overrides(int group_m, int tile, int tile_small);
+
+/* DEVELOPER entry: what the GEMM dispatcher (csrc/gemm_dispatch.h) decides for a call, without launching; it is the function the three
+ * GEMM entries below ask, under the overrides in force (zh_dev_set_gemm_overrides).  Nothing is dereferenced: it runs without a GPU.
+ * mode: 0 = zh_gemm_f16, 1 = zh_gemm_f16_res16, 2 = zh_gemm_f16x3, 3 = zh_gemm_f16x3 with planeW = 0; out_kind: 0 f32, 1 f16, 2 split pair
+ * (modes 0 / 1: out_f16); C / bias / residual: the pointer VALUES of the call (alignment only, NULL = absent); has_pos: pos tables given.
+ * plan (HOST int[6]) = {family (0 LDS ring, 1 few-row kernel), tile code as launched (0 = the base tile of the scalar / direct paths,
+ * 32 = the few-row kernel), tile_m, tile_n, store path (ring: 0 scalar, 1 direct, 2 wide; few-row: 0 scalar, 1 vec), peel rows M'
+ * (0 = one launch; else the call runs as rows [0, M') and [M', M), each with a plan of its own)}.  Returns what the entry's tile-related
+ * argument checks return (grid too large; zh_gemm_f16: a forced code that is no tile code). */
+int zh_dev_gemm_plan(int mode, int M, int N, int K, int batch, long lda, long ldw, long ldc, long strideC, long planeC,
+                     long ldr, long strideR, int res_rows, int out_kind, int act, int flags,
+                     const void* C, const void* bias, const void* residual, int has_pos, int* plan);
 
 /* DEVELOPER entry: the big plain-fp16 GEMM tiles (256 x 256 / 256 x 192) are persistent — `workgroups` of them walk a launch's tiles and
  * request the next tile's first K slices under the current tile's epilogue (csrc/gemm_kernel.h PERS; bitwise the one-workgroup-per-

@@ -167,9 +167,15 @@ def test_gemm_tail_peel_is_bitwise_one_launch(dev):
         h = torch.empty((M, N), dtype=f16, device=dev)
         ops.gemm(A, W, h, bias=bias, act=ops.ACT_QUICKGELU)
         return o, h
+    from tests import _gemm_plan_case as PC
+    # (the dispatcher's own word, zh_dev_gemm_plan: fresh torch allocations are aligned as `res` is)
+    plan_kw = dict(out_kind=0, C=res.data_ptr(), ldc=N, bias=bias.data_ptr(), residual=res.data_ptr(), ldr=N, res_rows=M)
+    p = PC.ask_call(L, "f16", M, N, K, **plan_kw)
+    assert (p.code, p.peel) == (256, 256 * 256), p
     o_p, h_p = run()                                    # cost model: 256 x 256 tiles, 1028 of them -> peeled
     try:
         _lib.check(L.zh_dev_set_gemm_overrides(0, 256, 0), "zh_dev_set_gemm_overrides")
+        assert PC.ask_call(L, "f16", M, N, K, **plan_kw).peel == 0
         o_1, h_1 = run()                                # forced tile: one launch, no peel
     finally:
         L.zh_dev_set_gemm_overrides(0, 0, 0)

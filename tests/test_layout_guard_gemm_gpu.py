@@ -6,8 +6,9 @@ direct test of the same kernel and output type, (3) proves with assert_untouched
 output (row padding, inter-batch and inter-plane space, 4 KiB in front, 256 rows behind) was written.  Operands are column slices of
 wider buffers (lda, ldw > K) whose other bytes are 0xFF (NaN), with padded batch strides and plane offsets.
 
-Store paths.  The launch records do not say which epilogue ran, so the launcher's rule (gemm.hip / gemm_x3.hip) is restated in
-_store_path() and every case asserts the path it was built to reach:
+Store paths.  The launch records do not say which epilogue ran, so the launcher's rule (csrc/gemm_dispatch.h) is restated in
+_store_path() and every case asserts the path it was built to reach — and that the library's own dispatcher, asked through
+zh_dev_gemm_plan for the very arguments of the call, plans that path (the restatement stays the independent statement):
   scalar  N % 4 != 0, or ldc / strideC / ldr / strideR % 4 != 0, or C not aligned to four elements, or bias / fp32 residual not 16-byte
           aligned (fp16 residual: 8-byte) -> the element-wise epilogue of the fallback tile (fp16 operands: 128 x 128; split: 128 x 64);
   direct  vector-legal, but rows that are not 16-byte multiples or not 16-byte aligned (fp16 / split outputs with N % 8 == 4 or
@@ -24,6 +25,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import _gemm_plan_case as PC
 from tests._guard import IN_FILL, OUT_FILL, Arena, assert_close, assert_untouched, assert_within
 
 pytestmark = pytest.mark.gpu
@@ -31,16 +33,21 @@ pytestmark = pytest.mark.gpu
 f16, f32, f64 = torch.float16, torch.float32, torch.float64
 U16, U32, SUB16 = 2.0 ** -11, 2.0 ** -24, 2.0 ** -25
 
-# tile code -> (tile_m, tile_n), read from the launch_gemm<WM, WN, TM, TN, ...> lines of gemm.hip (rows = WM * TM * 16, cols = WN * TN * 16)
+# tile code -> (tile_m, tile_n), read from the plain-fp16 tile table of csrc/gemm_dispatch.h (rows = WM * TM * 16, cols = WN * TN * 16);
+# test_tile_dicts_are_the_librarys_tables holds the three dicts to the library
 F16_TILES = {0: (128, 128), 256: (256, 256), 192: (256, 192), 128: (128, 128), 64: (128, 64), 2128: (128, 128), 2064: (128, 64),
              3064: (64, 64), 7032: (64, 64), 7096: (128, 96), 7128: (128, 128)}
-# ... and of gemm_x3.hip (code 32: the few-row kernel's 32 x 32 blocks, forced for any M)
+# ... and from the split-pair table (code 32: the few-row kernel's 32 x 32 blocks, forced for any M)
 X3_TILES = {0: (128, 64), 64: (128, 64), 96: (128, 96), 192: (192, 128), 256: (256, 128), 512: (256, 256), 448: (192, 256), 3064: (64, 64),
             3066: (64, 64), 32: (32, 32), 1288: (128, 128), 6496: (128, 96), 6464: (128, 64), 7096: (128, 96), 7128: (128, 128)}
 # the one-plane weight form has its own big tiles (test_gemm_x2_is_bitwise_the_x3_kernel_on_fp16_valued_weights)
 X2_TILES = {0: (128, 64), 64: (128, 64), 96: (128, 96), 192: (192, 128), 256: (256, 128), 512: (256, 256), 448: (192, 256), 3064: (64, 64),
             5122: (256, 256), 5124: (256, 256), 4484: (192, 256), 1288: (128, 128), 32: (32, 32), 6496: (128, 96), 3066: (64, 64),
             6464: (128, 64)}
+
+# zh_dev_gemm_plan's (family, store path) in the words of _store_path()
+PLAN_PATHS = {(0, 0): "scalar", (0, 1): "direct", (0, 2): "wide", (1, 0): "skinny-scalar", (1, 1): "skinny-vec"}
+
 
 def _randn(shape, seed, scale=1.0):
     return torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale
@@ -89,7 +96,7 @@ def gemm_case(dev, mode, kind, M, N, K, *, path, forced=0, batch=1, stride_a0=Fa
     """One guarded GEMM.  mode: 'f16' | 'res16' | 'x3' | 'x2'; kind: 'f32' | 'f16' | 'split'; residual: None | 'periodic' | 'full' |
     'inplace'; bias: None | 'exact' (N elements, NaN behind) | 'long' (the tensor handed over is 5 elements longer: they are NaN);
     pos: (h, w) of the separable tables.  Returns the store path that ran."""
-    from zutis_amd import ops
+    from zutis_amd import _lib, ops
     from zutis_amd.ops import Act
     x3 = mode in ("x3", "x2")
     ba = 1 if stride_a0 else batch
@@ -174,6 +181,12 @@ def gemm_case(dev, mode, kind, M, N, K, *, path, forced=0, batch=1, stride_a0=Fa
     if pos:
         kw["pos"] = (vy.m2, vx.m2)
     out = vc.act() if kind == "split" else vc.hi
+    # ... and the library's own dispatcher, asked for the very arguments about to be passed, plans that path
+    plan = PC.ask_call(_lib.load(raw=True), mode, M, N, K, out_kind=("f32", "f16", "split").index(kind), C=ops._hp(out)[0].data_ptr(),
+                       ldc=ldc, batch=batch, lda=lda, ldw=ldw, strideC=strideC, planeC=ops._hp(out)[1],
+                       bias=bias_t.data_ptr() if bias_t is not None else 0, residual=vr.hi.data_ptr() if vr is not None else 0,
+                       ldr=kw.get("ldr", 0), strideR=kw.get("strideR", 0), res_rows=kw.get("res_rows", 0), act=act, has_pos=pos is not None)
+    assert PLAN_PATHS[plan.family, plan.path] == got_path, (mode, kind, M, N, got_path, plan)
     (ops.gemm_x3 if x3 else ops.gemm)(Aop, Wop, out, **kw)
     # ---- float64 reference from the logical operands
     a64, w64 = A32.double(), W32.double()
@@ -229,6 +242,20 @@ def _forced(tile):
     L = _lib.load(raw=True)
     _lib.check(L.zh_dev_set_gemm_overrides(0, int(tile), 0), "zh_dev_set_gemm_overrides")
     return L
+
+
+@pytest.mark.parametrize("mode,tiles", [("f16", F16_TILES), ("x3", X3_TILES), ("x2", X2_TILES)])
+def test_tile_dicts_are_the_librarys_tables(mode, tiles):
+    """The *_TILES dicts above against the library's own tile_m x tile_n per code (host calls only): every code forced on a wide-path
+    shape (600 x 768, fp32 rows) reports itself and the dict's shape; code 0 is the base tile of a scalar-path call (N = 81)."""
+    for code, shape in tiles.items():
+        L = _forced(code)
+        try:
+            p = PC.ask_call(L, mode, 600, 768 if code else 81, 64, out_kind=0, C=1 << 20, ldc=776 if code else 89)
+            assert (p.code, p.tile_m, p.tile_n) == (code,) + shape, (mode, code, p)
+            assert PLAN_PATHS[p.family, p.path] == ("wide" if code not in (0, 32) else ("scalar" if code == 0 else "skinny-vec"))
+        finally:
+            L.zh_dev_set_gemm_overrides(0, 0, 0)
 
 
 @pytest.mark.parametrize("kind", ["f32", "f16", "res16"])
@@ -360,3 +387,10 @@ def test_gemm_tail_peel_inside_guards(dev):
     the last m-tile row) with ldc = N + 24: the peeled call starts at row M1 of a PADDED output, and the last tile is ragged."""
     M, N, K = 257 * 256 - 37, 1024, 128
     assert gemm_case(dev, "f16", "f32", M, N, K, path="wide", residual="full", seed=5) == "wide"
+    # the dispatcher's word for it: this layout is peeled at the last m-tile row, and not under the forced tile
+    kw = dict(out_kind=0, C=1 << 20, ldc=N + 24, residual=1 << 21, ldr=N + 8, res_rows=M)
+    assert PC.ask_call(_forced(0), "f16", M, N, K, **kw).peel == 256 * 256
+    try:
+        assert PC.ask_call(_forced(256), "f16", M, N, K, **kw).peel == 0
+    finally:
+        _forced(0)

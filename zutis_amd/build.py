@@ -46,6 +46,7 @@ def needs_build() -> bool:
         return True
     t = os.path.getmtime(LIB)
     deps = sources() + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_kernel.h"), os.path.join(CSRC, "gemm_skinny.h"),
+                        os.path.join(CSRC, "gemm_dispatch.h"),
                         os.path.join(CSRC, "rcn.h"), os.path.join(os.path.dirname(HERE), "include", "zutis_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -65,6 +66,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if os.path.basename(src).startswith("gemm"):
             deps.append(os.path.join(CSRC, "gemm_kernel.h"))
             deps.append(os.path.join(CSRC, "gemm_skinny.h"))
+        if os.path.basename(src).startswith("gemm") or os.path.basename(src) == "capi.hip":     # the tile choice; capi.hip: zh_dev_gemm_plan
+            deps.append(os.path.join(CSRC, "gemm_dispatch.h"))
         if os.path.basename(src) in ("preprocess.hip", "synth.hip"):
             deps.append(os.path.join(CSRC, "rcn.h"))
         if os.path.basename(src) in ("plan.hip", "capi.hip"):       # the dispatcher generated from the header / ZH_ABI_VERSION

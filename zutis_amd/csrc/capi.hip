@@ -16,10 +16,10 @@ extern "C" const char* zh_last_error(void) { return g_err; }
 extern "C" int zh_version(void) { return ZH_ABI_VERSION; }   // include/zutis_hip.h
 extern "C" const char* zh_arch(void) { return "gfx950"; }
 
-// ---- developer overrides of the GEMM tile choice (gemm_kernel.h): one process-wide instance, initialised from the environment
+// ---- developer overrides of the GEMM tile choice (gemm_dispatch.h): one process-wide instance, initialised from the environment
 //      once, changed only through zh_dev_set_gemm_overrides (tests force every tile variant with it)
 #include <stdlib.h>
-struct GemmDevOverrides { int group_m; int tile; int tile_small; };
+#include "gemm_dispatch.h"
 static GemmDevOverrides& gemm_dev_state() {
   static GemmDevOverrides o = [] {
     GemmDevOverrides v{4, 0, 0};
@@ -37,6 +37,25 @@ extern "C" int zh_dev_set_gemm_overrides(int group_m, int tile, int tile_small) 
   o.group_m = group_m >= 1 ? group_m : 4;
   o.tile = tile;
   o.tile_small = tile_small;
+  return ZH_OK;
+}
+
+// What the dispatcher decides for a GEMM, asked without launching: the plan functions the three entries call, under the process's
+// current overrides.  Pointer VALUES only (alignment); runs without a GPU.
+extern "C" int zh_dev_gemm_plan(int mode, int M, int N, int K, int batch, long lda, long ldw, long ldc, long strideC, long planeC,
+                                long ldr, long strideR, int res_rows, int out_kind, int act, int flags,
+                                const void* C, const void* bias, const void* residual, int has_pos, int* plan) {
+  ZH_CHECK_ARG(plan && mode >= GEMM_F16 && mode <= GEMM_X2, "zh_dev_gemm_plan: null plan or mode %d not in {0 f16, 1 res16, 2 x3, 3 x2}", mode);
+  ZH_CHECK_ARG(M > 0 && N > 0 && K > 0 && batch > 0, "zh_dev_gemm_plan: bad shape M=%d N=%d K=%d batch=%d", M, N, K, batch);
+  const GemmProblem q = {mode, M, N, K, batch, lda, ldw, ldc, strideC, planeC, ldr, strideR, res_rows, out_kind, act, flags,
+                         (uintptr_t)C, (uintptr_t)bias, (uintptr_t)residual, has_pos != 0, mode == GEMM_RES16};
+  GemmPlan g;
+  const int rc = mode <= GEMM_RES16 ? gemm_plan_f16(q, gemm_dev_overrides(), &g) : gemm_plan_x3(q, gemm_dev_overrides(), &g);
+  if (rc != ZH_OK) return rc;
+  const GemmTile* t = gemm_plan_tile(mode, g.code);
+  ZH_CHECK_ARG(t || g.family == GEMM_SKINNY, "zh_dev_gemm_plan: the plan's tile code %d has no table row", g.code);
+  plan[0] = g.family; plan[1] = g.code; plan[2] = t ? gemm_tile_m(*t) : 32; plan[3] = t ? gemm_tile_n(*t) : 32;   // few-row kernel: 32 x 32 blocks
+  plan[4] = g.path; plan[5] = (int)g.peel_rows;
   return ZH_OK;
 }
 

@@ -1094,25 +1094,4 @@ static void launch_one(GemmArgs p, int batch, hipStream_t stream) {
   hipLaunchKernelGGL((gemm_f16_kernel<WM, WN, TM, TN, STAGES, OUT, ACT, VEC, SPLIT>), dim3(nblk), dim3(64 * WM * WN), 0, stream, p);
 }
 
-// Relative time estimate of a tiling: rounds of the 256-CU chip x time of one round.  With `bpc` blocks resident
-// per CU a round takes bpc x the tile's own time; `eff` is the measured relative speed of the tile shape at
-// K=768 (256x256: 1.0, 256x192: 0.95, 128x128: 0.8 — tools/gemm_bench.py on MI355X).
-// host-side check of the optional pos tables (both or neither)
-static inline bool zh_pos_tables_ok(const void* pos_y, const void* pos_x, long ld_pos, int pos_h, int pos_w, int N) {
-  if (!pos_y && !pos_x) return true;
-  return pos_y && pos_x && pos_h > 0 && pos_w > 0 && ld_pos >= N && ld_pos % 8 == 0 && N % 4 == 0 &&
-         (((uintptr_t)pos_y | (uintptr_t)pos_x) & 15) == 0;
-}
-
-static inline double tiling_cost(long M, long N, int batch, int BM, int BN, int bpc, double eff) {
-  const long tiles = (long)zh_cdiv(M, BM) * zh_cdiv(N, BN) * batch;
-  const long slots = 256L * bpc;
-  const long rounds = (tiles + slots - 1) / slots;
-  return (double)rounds * BM * BN * bpc / eff;
-}
-
-// Developer overrides (defined once, in capi.hip): initialised ONCE per process from ZH_GEMM_GROUP_M (super-tile height),
-// ZH_GEMM_TILE (forced tile code; unknown codes are an argument error) and ZH_GEMM_TILE_SMALL (applied to M <= 4096 only) —
-// never read per launch — and settable at run time through zh_dev_set_gemm_overrides() (tests / tools).
-struct GemmDevOverrides { int group_m; int tile; int tile_small; };
-const GemmDevOverrides& gemm_dev_overrides();
+// (the host-side checks, the cost model of the tile choice and the developer overrides: gemm_dispatch.h)

@@ -147,12 +147,7 @@ __global__ __launch_bounds__(256, 2) void gemm_skinny_x3_kernel(GemmArgs p, int 
   }
 }
 
-// Host side: is this GEMM one for the few-row kernel?  Shape only (never alignment): the K order of a row's sum — and with it the bits of
-// the result — must not depend on how many columns a caller asks for (sharded retrieval merges shards of any width).
-static inline bool gemm_skinny_ok(const GemmArgs& p, int batch, bool vec_ok, int max_rows) {
-  (void)vec_ok;                                              // the epilogue has an element-wise form: every few-row GEMM takes this kernel
-  return !p.pos_y && p.M <= max_rows && (long)zh_cdiv(p.N, 32) * zh_cdiv(p.M, 32) * batch <= 65535L * 8;
-}
+// Host side (which GEMMs take this kernel: gemm_plan_x3, gemm_dispatch.h; the epilogue has an element-wise form, so alignment never decides)
 
 template <int SPW>
 static void launch_skinny(const GemmArgs& p, int batch, int out_kind, hipStream_t stream) {
