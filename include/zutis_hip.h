@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 238 /* 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 239 /* 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -607,6 +607,25 @@ int zh_polygon_runs(const int* xs, const int* ys, const int* step_pref, const in
 int zh_runs_label_maps(const int* run_end, const int* run_off, const int* status, int n_masks, long n_runs, const int* list_off,
                        const int* list_mask, const unsigned char* list_label, int n_list, const int* hw, const long long* out_off,
                        int B, int max_tiles, int overlap, int ignore_value, unsigned char* out, long out_bytes, zh_stream_t stream);
+
+/* ---- device PNG encoder (zutis_amd/png_device.py is the definition; csrc/png.hip) ---- */
+/* The zlib stream of the PNG of B u8 images, byte for byte png_device.deflate_np: every row filtered with type 2 (Up), the filtered
+ * bytes cut into segments of ZH_PNG_SEGMENT_BYTES, each one fixed-Huffman deflate block of literals and distance-1 matches over its runs
+ * of equal bytes followed by an empty stored block, 78 01 in front, 03 00 and the Adler-32 behind.  What is left for the host is the
+ * chunk framing (png_device.frame: signature, IHDR, PLTE, the IDAT's CRC-32, IEND).
+ * images u8 [image_bytes]: image b is [h, w, c] row-major at img_off[b] (int64 [B]), (h, w) = hw[2 b], hw[2 b + 1] (int32 [B, 2]); c = 1 or
+ * 3 for the whole call.  out u8 [out_bytes]: image b's stream starts at out_off[b] (int64 [B]) and is lengths[b] (int32 [B]) bytes long,
+ * at most png_device.stream_bound(h, w, c) = 2 + full * 18438 + (rest ? (9 rest + 20) / 8 + 4 : 0) + 6 with full, rest = divmod(h * (w c + 1),
+ * ZH_PNG_SEGMENT_BYTES) — the stride the caller lays the streams out at; bytes past the length are not written.  max_segments: at least
+ * ceil(h (w c + 1) / ZH_PNG_SEGMENT_BYTES) of every image (the grid's width).  An image that does not fit — h or w below 1, more than
+ * 0x6fffffff filtered bytes, bytes outside images, more segments than max_segments, a bound that does not fit behind out_off[b] — is
+ * not read and not written: lengths[b] = -1.  Two launches; workspace >= zh_png_deflate_workspace_size bytes, 16-byte aligned: a
+ * fixed-stride slot and (bytes, Adler pair) per segment.  B <= 65535; B = 0 launches nothing.  The bytes are the same every time. */
+#define ZH_PNG_SEGMENT_BYTES 16384
+size_t zh_png_deflate_workspace_size(int B, int max_segments);
+int zh_png_deflate(const unsigned char* images, long image_bytes, const long long* img_off, const int* hw, int c, int B, int max_segments,
+                   const long long* out_off, unsigned char* out, long out_bytes, int* lengths, void* workspace, size_t workspace_bytes,
+                   zh_stream_t stream);
 
 /* Native launch plans (zutis_amd/plan.py): replay n recorded calls of the entry points above (op id + 32 argument words
  * each; dispatcher generated from this header) in one C loop; zh_plan_run2 alternates two plans on two streams. */

@@ -177,6 +177,7 @@ class LabelPainter:
         if self.device.type != "cuda":
             raise _lib.ZutisHipError("LabelPainter paints on the GPU (labels_np is the host form)")
         self.plan, self.events = plan, events
+        self.last_launch = None                                          # (hw int32 [B, 2], out_off int64 [B + 1]) of the last launch, on the device
         anns = plan.ground_truth["annotations"]
         size_of = {}                                                     # annotation index -> (h, w) of the image that paints it
         for im, entries in zip(plan.images, plan.lists):
@@ -292,6 +293,7 @@ class LabelPainter:
         with torch.cuda.device(self.device):
             dbuf = torch.from_numpy(host).to(self.device)                                   # the batch's lists: a few bytes an entry
             view = lambda n, dt: dbuf[lay[n][0]:lay[n][0] + max(lay[n][1].nbytes, 16)].view(dt)[:lay[n][1].size]
+            self.last_launch = (view("hw", torch.int32), view("out_off", torch.int64))      # the batch's sizes and offsets, as the launch read them
             e = self._event()
             ops.runs_label_maps(self.run_end, self.run_off, self.status, view("list_off", torch.int32), view("list_mask", torch.int32),
                                 view("list_label", torch.uint8), view("hw", torch.int32), view("out_off", torch.int64), out, max_tiles,
@@ -340,16 +342,24 @@ def _write_png(path: str, a: np.ndarray, compress_level: int):
 
 def write_semantic_masks(ground_truth, out_dir: str, *, image_ids: Optional[Sequence] = None, route: str = "device", n_workers: int = 16,
                          compress_level: int = 1, device=None, paint_bytes: int = PAINT_BYTES, label_of: Optional[Dict[int, int]] = None,
-                         order: str = "file", overlap: str = "last", crowd: str = "label", ignore_value: int = 255, events=None) -> dict:
+                         order: str = "file", overlap: str = "last", crowd: str = "label", ignore_value: int = 255, events=None,
+                         png_encoder: str = "host") -> dict:
     """Write {out_dir}/{file_name without .jpg}.png, mode L, for the plan's images: the files coco2017.py:134 / coco20k.py:178 open and
     evaluate_from_files(gt_format="u8") reads.
 
     route "device": LabelPainter, ragged launches of at most paint_bytes output bytes (a larger image goes alone); per launch ONE copy
     back into a pinned buffer of a preprocess.WriterRing, whose n_workers (at most 16) threads encode launch k's PNGs while launch k + 1
     is painted.  route "host": labels_np and Image.save in this thread; needs no GPU.  label_of / order / overlap / crowd / ignore_value:
-    paint_plan's.  Returns {"paths": one per image, in the plan's order, "stats"}."""
+    paint_plan's.  png_encoder "host": the writer threads encode with Pillow (compress_level).  "device" (route "device" only: ValueError
+    with route "host"): zh_png_deflate behind each ragged launch turns the maps into the zlib streams of their PNGs (png_device.py); the
+    copy back carries the streams at their worst-case strides and their lengths, a writer frames a stream and writes the file;
+    compress_level is unused.  The files decode to the same maps.  Returns {"paths": one per image, in the plan's order, "stats"}."""
+    from . import png_device
     if route not in ("device", "host"):
         raise ValueError(f"write_semantic_masks: route {route!r} is not 'device' or 'host'")
+    on_device = png_device.check_encoder("write_semantic_masks", png_encoder) == "device"
+    if on_device and route == "host":
+        raise ValueError("write_semantic_masks: png_encoder=\"device\" encodes behind the device's paint: it needs route=\"device\"")
     plan = paint_plan(ground_truth, image_ids, label_of=label_of, order=order, overlap=overlap, crowd=crowd, ignore_value=ignore_value)
     os.makedirs(out_dir, exist_ok=True)
     paths = [os.path.join(out_dir, stem_of(im["file_name"]) + ".png") for im in plan.images]
@@ -360,7 +370,7 @@ def write_semantic_masks(ground_truth, out_dir: str, *, image_ids: Optional[Sequ
             _write_png(p, m, int(compress_level))
         return {"paths": paths, "stats": {"images": len(plan), "annotations": sum(len(e) for e in plan.lists), "launches": 0}}
     import torch
-    from . import preprocess
+    from . import ops, preprocess
     painter = LabelPainter(plan, device, events)
     dev = painter.device
     groups, cur, used = [], [], 0
@@ -379,6 +389,14 @@ def write_semantic_masks(ground_truth, out_dir: str, *, image_ids: Optional[Sequ
     def hand_to_writers(slot, host, idx, off):
         ring.events[slot].synchronize()                                            # the bytes are in the pinned buffer
         a = host.numpy()
+        if on_device:                                                              # off: the streams' offsets; the length words lie behind them
+            lengths = a[len(a) - 4 * len(idx):].view(np.int32)
+            for k, i in enumerate(idx):
+                im, n = plan.images[i], int(lengths[k])
+                if not 0 < n <= off[k + 1] - off[k]:
+                    raise RuntimeError(f"write_semantic_masks: the device encoder left no stream for {paths[i]} ({im['h']} x {im['w']})")
+                ring.submit(slot, png_device.write_stream, paths[i], a[off[k]:off[k] + n], im["h"], im["w"], "L", None)
+            return
         for k, i in enumerate(idx):
             im = plan.images[i]
             ring.submit(slot, _write_png, paths[i], a[off[k]:off[k + 1]].reshape(im["h"], im["w"]), int(compress_level))
@@ -388,8 +406,23 @@ def write_semantic_masks(ground_truth, out_dir: str, *, image_ids: Optional[Sequ
             for k, idx in enumerate(groups):
                 slot = k & 1
                 total = sum(plan.images[i]["h"] * plan.images[i]["w"] for i in idx)
-                host, dev_out = ring.take(slot, total)                             # waits for the writers of launch k - 2
-                _, off = painter.paint_ragged(idx, out=dev_out)
+                if on_device:
+                    sizes = [(plan.images[i]["h"], plan.images[i]["w"]) for i in idx]
+                    if min(min(s) for s in sizes) < 1:
+                        raise ValueError("write_semantic_masks: an image without pixels has no PNG")
+                    off = np.concatenate(([0], np.cumsum([png_device.stream_bound(h, w, 1) for h, w in sizes]))).astype(np.int64)
+                    n_streams = (int(off[-1]) + 3) // 4 * 4
+                    host, dev_out = ring.take(slot, n_streams + 4 * len(idx))      # waits for the writers of launch k - 2
+                    raw, _ = painter.paint_ragged(idx)
+                    hw_dev, raw_off = painter.last_launch
+                    out_off = torch.from_numpy(off[:-1].copy()).to(dev)
+                    e = painter._event()
+                    ops.png_deflate(raw, raw_off[:len(idx)], hw_dev, 1, dev_out[:n_streams], out_off, dev_out[n_streams:].view(torch.int32),
+                                    max(png_device.segments(h, w, 1) for h, w in sizes))
+                    painter._event(e, "zh_png_deflate")
+                else:
+                    host, dev_out = ring.take(slot, total)                         # waits for the writers of launch k - 2
+                    _, off = painter.paint_ragged(idx, out=dev_out)
                 host.copy_(dev_out, non_blocking=True)                             # the one copy back of the launch
                 ring.events[slot].record()
                 if waiting is not None:

@@ -17,7 +17,7 @@ EXTRA_FLAGS = {"bilateral.hip": ["-ffp-contract=off"], "preprocess.hip": ["-ffp-
                "synth.hip": ["-ffp-contract=off"],   # synth.hip: Pillow's blend and HSV arithmetic, one IEEE operation at a time
                "polygon.hip": ["-ffp-contract=off"]}  # polygon.hip: rleFrPoly's double arithmetic, bit-compared with the host's
 # the MFMA kernels live at the register budget of their occupancy: a spill is a 2-3x slowdown, so it is a build error
-NO_SCRATCH = {"gemm.hip", "gemm_x3.hip", "attention.hip", "preprocess.hip", "synth.hip", "resample.hip", "label_paint.hip"}
+NO_SCRATCH = {"gemm.hip", "gemm_x3.hip", "attention.hip", "preprocess.hip", "synth.hip", "resample.hip", "label_paint.hip", "png.hip"}
 MAX_SCRATCH = int(os.environ.get("ZH_BUILD_MAX_SCRATCH", "0"))    # bytes per lane tolerated: the MFMA loops must not spill (developer builds may raise it)
 # waves per SIMD the design of a kernel relies on (source -> mangled-name substring -> minimum), checked against the compiler's
 # remarks; a key that matches no kernel of its source is a build error (a renamed template would otherwise drop its guard)
@@ -27,7 +27,7 @@ MIN_OCCUPANCY = {"attention.hip": {"attn_f16_kernelILi64ELi4ELi1ELi0EE": 3, "att
                  # the byte epilogue (zh_upsample_argmax_bytes) must not cost the arg-max kernels the occupancy of their int64 form (UaStore)
                  "resample.hip": {"upsample_argmax_pk_kernelI7UaBytes": 3, "upsample_argmax_lds_kernelI7UaBytes": 6,
                                   "upsample_argmax_kernelI7UaBytes": 8}}
-SOURCES = ["capi.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "instance_paint.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "assign.hip", "cocoeval.hip", "polygon.hip", "label_paint.hip", "synth.hip", "plan.hip"]
+SOURCES = ["capi.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "instance_paint.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "assign.hip", "cocoeval.hip", "polygon.hip", "label_paint.hip", "png.hip", "synth.hip", "plan.hip"]
 
 
 def _hipcc() -> str:

@@ -968,6 +968,34 @@ def runs_label_maps(run_end, run_off, status, list_off, list_mask, list_label, h
     return out
 
 
+PNG_SEGMENT_BYTES = 16384                     # ZH_PNG_SEGMENT_BYTES
+
+
+def png_deflate(images, img_off, hw, c, out, out_off, lengths, max_segments, workspace=None):
+    """The zlib streams of the PNGs of B images in one call (zh_png_deflate; png_device.deflate_np byte for byte).  images u8 (any shape,
+    contiguous): image b is [h, w, c] at img_off[b] of its bytes; img_off int64 [B], hw int32 [B, 2] = (h, w), c 1 or 3; out u8: image b's
+    stream at out_off[b] (int64 [B]), laid out by the caller at png_device.stream_bound strides; lengths int32 [B]: the streams' lengths
+    (-1: the image does not fit, see zutis_hip.h); max_segments: the largest png_device.segments(h, w, c) of the batch (the caller holds
+    the sizes on the host).  Everything on the device; nothing is copied.  Returns lengths."""
+    _chk(images, torch.uint8, "png_deflate images"); _chk(out, torch.uint8, "png_deflate out")
+    _chk(img_off, torch.int64, "png_deflate img_off"); _chk(out_off, torch.int64, "png_deflate out_off")
+    _chk(hw, torch.int32, "png_deflate hw"); _chk(lengths, torch.int32, "png_deflate lengths")
+    if c not in (1, 3):
+        raise _lib.ZutisHipError(f"png_deflate: c {c!r} is not 1 or 3")
+    B = img_off.numel()
+    if hw.numel() != 2 * B or out_off.numel() != B or lengths.numel() != B:
+        raise _lib.ZutisHipError("png_deflate: img_off [B], hw [B, 2], out_off [B] and lengths [B] do not describe one batch")
+    if B > 65535:
+        raise _lib.ZutisHipError(f"png_deflate: {B} images in one call, at most 65535")
+    if B and int(max_segments) < 1:
+        raise _lib.ZutisHipError(f"png_deflate: max_segments {max_segments!r} for {B} images")
+    if B:
+        ws, need = _workspace_or(workspace, "png_deflate", "zh_png_deflate_workspace_size", images.device, B, int(max_segments))
+        _call("zh_png_deflate", _p(images), images.numel(), _p(img_off), _p(hw), int(c), B, int(max_segments), _p(out_off), _p(out), out.numel(),
+              _p(lengths), _p(ws), need, _stream())
+    return lengths
+
+
 # ---- training criterion (criterion.py::Criterion): zutis_amd/criterion.py
 
 def mask_match_cost(proposals, gt_u8, inst_off, n_max, H, W, costs, stat_p, stat_pg, stat_g, skip, status, weight_dice=1.0, weight_bce=1.0):

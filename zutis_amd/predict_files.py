@@ -8,7 +8,8 @@ reads as ground truth.  The same launch can blend a palette colour over the deco
 of the batch's staging buffer.  The file pipeline of preprocess.py: decoding threads fill a pinned staging buffer one batch ahead
 (PredictBatchLoader: batches of one file size); per batch (device_batches) ONE host-to-device copy and ops.resize_normalize; then the
 module's forward, the byte kernel, ONE device-to-host copy into one of the two pinned output buffers of a WriterRing, whose threads
-encode and write batch k's PNGs while batch k + 1 is on the device.
+encode and write batch k's PNGs while batch k + 1 is on the device.  png_encoder="device": the pictures stay on the device, zh_png_deflate
+(png_device.py) turns each into the zlib stream of its PNG, and the one copy back carries the streams: a writer frames and writes.
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import preprocess
+from . import png_device, preprocess
 from .evaluate import _require_dropin, collect_instance_predictions
 from .preprocess import MAX_THREADS
 LABEL_LIMIT = {"u8": 256, "rg16": 65536}
@@ -208,7 +209,8 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
                        image_ids: Optional[Sequence] = None, new_label_id_to_old_label_id: Optional[Dict[int, int]] = None,
                        label_id_to_category: Optional[Dict[int, str]] = None, nms_type: Optional[str] = "hard",
                        predictions_json: Optional[str] = None, instance_map: bool = False, instance_overlay: bool = False,
-                       instance_colours="instance", instance_min_score: float = 0.0, instance_outline: bool = True) -> dict:
+                       instance_colours="instance", instance_min_score: float = 0.0, instance_outline: bool = True,
+                       png_encoder: str = "host") -> dict:
     """The segmenter over a list of image files: label PNGs (and overlays) on disk, and / or the instance predictions.
 
     network: the drop-in ZUTIS (zutis_amd/dropin/networks/zutis.py) on a GPU; its text embeddings are the n categories.
@@ -238,11 +240,19 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     the palette), or an array [>= queries, 3] with one colour per id.  The bytes share the batch's device buffer, its one copy back and the
     writer slot with the semantic outputs.  The result gains "instance_map_paths", "instance_overlay_paths" and "instance_ids": parallel to
     "instance_predictions", the id of each prediction in its image's map.
+    png_encoder "host": the writer threads encode with Pillow (compress_level).  "device": every picture of the call — label map in any
+    format, overlay, id map, instance overlay — is encoded on the device behind the kernels that made it (one zh_png_deflate per kind of
+    picture and batch: png_device.py defines the stream — Up filter, run-length deflate with the fixed Huffman code); the batch's one copy
+    back carries the streams at their worst-case stride and their lengths, and a writer only frames a stream (chunk CRCs) and writes the
+    file.  The files decode to the same pixels, mode and palette; label and id maps come out at 1.14 - 1.19 x Pillow's level-1 size,
+    photographic overlays at 2.0 x (1.05 of their raw bytes against 0.52; profiles/NOTES.md), which is why "host" is the default.
+    compress_level is unused with "device".  Any other value: ValueError before any work.
     Returns {"label_paths": [...] | None, "overlay_paths": [...] | None, "instance_predictions": the dicts predict gave (with "bbox"),
     in input-path order, "n_images": int}.
     A missing or unreadable image (FileNotFoundError / OSError / ValueError) and a directory or file that cannot be written (OSError)
     are raised here; no decoding or writing thread outlives the call and the device stays usable."""
     p_images = [os.fspath(p) for p in p_images]
+    on_device = png_device.check_encoder("predict_from_files", png_encoder) == "device"
     _require_dropin(network, "predict_from_files")
     n = int(network.text_embeddings.shape[0])
     pal = _validate(n, len(p_images), semantic, instance, label_format, palette, overlay, alpha, image_ids, compress_level)
@@ -261,6 +271,7 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     per_image: List[List[dict]] = [[] for _ in p_images]
     per_image_ids: List[List[int]] = [[] for _ in p_images]
     if p_images:
+        from . import ops
         eng = network._get_engine()
         dev = eng._device()
         n_decode, n_write = thread_split(n_workers, semantic or paint)
@@ -278,6 +289,17 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
             a = host.numpy()
             B = len(indices)
             at = 0
+            if on_device:                                                                  # streams at their bound's stride, then the length words
+                lengths = a[len(a) - 4 * B * len(parts):].view(np.int32)
+                for k, (paths, c, md, pb) in enumerate(parts):
+                    bound = png_device.stream_bound(H, W, c)
+                    for b, i in enumerate(indices):
+                        n = int(lengths[k * B + b])
+                        if not 0 < n <= bound:
+                            raise RuntimeError(f"predict_from_files: the device encoder left no stream for {paths[i]} ({H} x {W} x {c})")
+                        ring.submit(slot, png_device.write_stream, paths[i], a[at + b * bound:at + b * bound + n], H, W, md, pb)
+                    at += B * bound
+                return
             for paths, c, md, pb in parts:                                                 # the byte ranges of the buffer, in the order they were laid out
                 view = a[at:at + B * H * W * c].reshape((B, H, W) if c == 1 else (B, H, W, c))
                 at += B * H * W * c
@@ -286,6 +308,18 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
 
         def copy_back(slot, host, dev_out, batch, H, W, parts):
             nonlocal waiting
+            if on_device:                                                                  # the pictures become their streams where they lie
+                B, at, raw = len(batch.indices), 0, 0
+                dev_streams = torch.empty((host.numel(),), dtype=torch.uint8, device=dev)
+                lengths = dev_streams[host.numel() - 4 * B * len(parts):].view(torch.int32)
+                for k, (_, c, _, _) in enumerate(parts):
+                    img_off, hw, out_off = png_device.uniform_descriptors(B, H, W, c, dev)
+                    bound = png_device.stream_bound(H, W, c)
+                    ops.png_deflate(dev_out[raw:raw + B * H * W * c], img_off, hw, c, dev_streams[at:at + B * bound], out_off,
+                                    lengths[k * B:(k + 1) * B], png_device.segments(H, W, c))
+                    raw += B * H * W * c
+                    at += B * bound
+                dev_out = dev_streams
             host.copy_(dev_out, non_blocking=True)                                         # labels + overlay + instance pictures: one D2H
             ring.events[slot].record()
             if waiting is not None:
@@ -313,8 +347,11 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
                         ni = 3 * B * H * W if instance_overlay else 0
                         parts += ([(map_paths, LABEL_CHANNELS[id_format], "L" if id_format == "u8" else "RGB", None)] if instance_map else []) + \
                                  ([(iovl_paths, 3, "RGB", None)] if instance_overlay else [])
-                    host, _ = ring.take(slot, nl + no + nm + ni)                           # waits for the writers of batch k - 2
-                    dev_out = torch.empty((host.numel(),), dtype=torch.uint8, device=dev)
+                    n_host = nl + no + nm + ni
+                    if on_device:                                                          # the streams' strides, 4-byte aligned, one length word per picture
+                        n_host = (sum(B * png_device.stream_bound(H, W, c) for _, c, _, _ in parts) + 3) // 4 * 4 + 4 * B * len(parts)
+                    host, _ = ring.take(slot, n_host)                                      # waits for the writers of batch k - 2
+                    dev_out = torch.empty((nl + no + nm + ni,), dtype=torch.uint8, device=dev)
                     if semantic:
                         eng.label_bytes(out["patch_tokens"], network.text_embeddings, (H, W), label_format=label_format,
                                         labels_out=dev_out[:nl].view((B, H, W) if ch == 1 else (B, H, W, ch)), palette=pal_dev,
