@@ -1,8 +1,10 @@
 // Per-row top-k selection for the retrieval step of the index-dataset pipeline (datasets/index_dataset.py:163-167):
 // the reference argsorts every category's N similarities (N ~ 2.7 M) and keeps the first 500.  Here: one workgroup per
 // row does an exact radix SELECT of the k-th largest (score, index) pair — 8 histogram passes over the row, no sort of N
-// elements — then compacts the k survivors and bitonic-sorts only those in LDS.  Ordering: score descending, ties by
-// ascending index (torch.argsort(descending=True) leaves tie order unspecified).  HBM-bound: 9 reads of the row.
+// elements — then compacts the k survivors and bitonic-sorts only those in LDS.  Ordering: every NaN first (either sign,
+// any payload), then score descending with -0.0 == +0.0, ties by ascending index — torch.sort(descending=True, stable=True);
+// torch.argsort(descending=True) leaves tie order unspecified.  Values are returned as stored (the zero's sign, the NaN's
+// payload).  HBM-bound: 9 reads of the row.
 // Reported index of column i: idx_map ? idx_map[row*ld + i] : i + idx_add — chunk offsets and the merge of per-chunk /
 // per-rank candidates (whose columns carry global image indices) need no separate gather.  Ties are always broken by
 // ascending COLUMN, so candidate lists must be laid out in ascending-index order of equal scores (chunk-major / rank-major
@@ -13,7 +15,9 @@ typedef unsigned long long u64;
 
 __device__ __forceinline__ u64 topk_key(float v, unsigned idx) {
   unsigned u = __float_as_uint(v);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);           // unsigned order == float order (NaN sorts above +inf)
+  const unsigned mag = u & 0x7FFFFFFFu, neg = (unsigned)((int)u >> 31);      // neg: all ones under a set sign bit
+  u = ((mag ^ neg) - neg) ^ 0x80000000u;                    // 2^31 +- mag: unsigned order == float order, -0.0 and +0.0 share a key
+  if (mag > 0x7F800000u) u = 0xFFFFFFFFu;                   // any NaN (either sign, any payload): the top key, above +inf
   return ((u64)u << 32) | (u64)(0xFFFFFFFFu - idx);         // equal scores: smaller index = larger key
 }
 

@@ -865,7 +865,8 @@ def resize_nearest_u8(x_u8, H, W, out=None):
 
 
 def topk_rows(scores, k, N=None, with_values=False, idx_map=None, idx_add=0, out_idx=None, out_val=None):
-    """scores f32 [R, ld] on the GPU -> int64 [R,k] indices of the k largest of the first N columns (score desc, column asc).
+    """scores f32 [R, ld] on the GPU -> int64 [R,k] indices of the k largest of the first N columns: NaNs of either sign first, then
+    score descending with -0.0 == +0.0, ties by ascending column (torch.sort(descending=True, stable=True)); values as stored.
     Reported index of column i = idx_map[r, i] (int64 [R, ld]) if given, else i + idx_add.  out_idx / out_val may be column
     blocks [R, k] of wider row-major tables (same row stride for both)."""
     _chk(scores, f32, "topk scores")

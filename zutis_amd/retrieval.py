@@ -69,7 +69,7 @@ def retrieve_topk(text_embeddings: torch.Tensor, image_embeddings: torch.Tensor,
 
 def merge_topk(cand_idx: torch.Tensor, cand_val: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Exact top-k over candidate lists: cand_idx int64 [C,n] (global image indices, -1 = padding with score -inf),
-    cand_val f32 [C,n] -> (indices [C,k], scores [C,k]), score descending, ties by ascending column.  The lists must be
+    cand_val f32 [C,n] -> (indices [C,k], scores [C,k]), NaNs first, score descending (-0.0 == +0.0), ties by ascending column.  The lists must be
     concatenations, in ascending index-range order (chunk-major / rank-major), of lists sorted by (score desc, index asc):
     then equal scores appear in ascending image-index order and the result is what retrieve_topk gives over the union."""
     return ops.topk_rows(cand_val.contiguous(), k, with_values=True, idx_map=cand_idx.contiguous())
