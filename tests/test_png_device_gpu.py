@@ -108,13 +108,16 @@ def _pixels(path):
         return im.mode, np.asarray(im).copy(), (im.getpalette() if im.mode == "P" else None)
 
 
-def _same_pictures(host_paths, device_paths, mode):
+def _same_pictures(host_paths, device_paths, mode, palette_bytes=None):
+    """... and every device-encoded file is the definition's file of the host arm's pixels, byte for byte: a stream cut too long still
+    decodes, only this pins the lengths."""
     assert len(host_paths) == len(device_paths) > 0
     for a, b in zip(host_paths, device_paths):
         (ma, pa, la), (mb, pb, lb) = _pixels(a), _pixels(b)
         assert ma == mb == mode and pa.shape == pb.shape and np.array_equal(pa, pb), b
         assert la == lb or (la[:3 * N_CAT] == lb[:3 * N_CAT] and len(lb) >= 3 * N_CAT), b          # the palette as given (Pillow pads its own to 256)
         assert os.path.basename(a) == os.path.basename(b)
+        assert open(b, "rb").read() == P.encode_np(pa, mode, palette_bytes), b
 
 
 @pytest.fixture(scope="module")
@@ -153,7 +156,7 @@ def test_every_picture_of_a_call_decodes_to_the_host_encoders_pixels(dev, nets, 
     kw = dict(overlay=True, alpha=96, instance=True, image_ids=list(range(len(images))), instance_map=True, instance_overlay=True)
     host = _predict(nets, images, tmp_path / "host", "u8-palette", "host", **kw)
     device = _predict(nets, images, tmp_path / "device", "u8-palette", "device", **kw)
-    _same_pictures(host["label_paths"], device["label_paths"], "P")
+    _same_pictures(host["label_paths"], device["label_paths"], "P", bytes(v for k in range(N_CAT) for v in PALETTE[k]))
     with Image.open(device["label_paths"][0]) as im:
         assert im.getpalette()[:3 * N_CAT] == [v for k in range(N_CAT) for v in PALETTE[k]]
     _same_pictures(host["overlay_paths"], device["overlay_paths"], "RGB")

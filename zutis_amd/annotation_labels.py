@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import rle
+from . import picture_out, rle
 from .coco_eval import _load
 
 ORDERS = ("file", "area")
@@ -177,7 +177,6 @@ class LabelPainter:
         if self.device.type != "cuda":
             raise _lib.ZutisHipError("LabelPainter paints on the GPU (labels_np is the host form)")
         self.plan, self.events = plan, events
-        self.last_launch = None                                          # (hw int32 [B, 2], out_off int64 [B + 1]) of the last launch, on the device
         anns = plan.ground_truth["annotations"]
         size_of = {}                                                     # annotation index -> (h, w) of the image that paints it
         for im, entries in zip(plan.images, plan.lists):
@@ -293,7 +292,6 @@ class LabelPainter:
         with torch.cuda.device(self.device):
             dbuf = torch.from_numpy(host).to(self.device)                                   # the batch's lists: a few bytes an entry
             view = lambda n, dt: dbuf[lay[n][0]:lay[n][0] + max(lay[n][1].nbytes, 16)].view(dt)[:lay[n][1].size]
-            self.last_launch = (view("hw", torch.int32), view("out_off", torch.int64))      # the batch's sizes and offsets, as the launch read them
             e = self._event()
             ops.runs_label_maps(self.run_end, self.run_off, self.status, view("list_off", torch.int32), view("list_mask", torch.int32),
                                 view("list_label", torch.uint8), view("hw", torch.int32), view("out_off", torch.int64), out, max_tiles,
@@ -335,11 +333,6 @@ class LabelPainter:
         return out, out_off
 
 
-def _write_png(path: str, a: np.ndarray, compress_level: int):
-    from PIL import Image
-    Image.fromarray(a, "L").save(path, format="PNG", compress_level=compress_level)
-
-
 def write_semantic_masks(ground_truth, out_dir: str, *, image_ids: Optional[Sequence] = None, route: str = "device", n_workers: int = 16,
                          compress_level: int = 1, device=None, paint_bytes: int = PAINT_BYTES, label_of: Optional[Dict[int, int]] = None,
                          order: str = "file", overlap: str = "last", crowd: str = "label", ignore_value: int = 255, events=None,
@@ -367,10 +360,10 @@ def write_semantic_masks(ground_truth, out_dir: str, *, image_ids: Optional[Sequ
         raise ValueError("write_semantic_masks: two images of the plan share a file name")
     if route == "host":
         for p, m in zip(paths, labels_np(plan)):
-            _write_png(p, m, int(compress_level))
+            picture_out.write_png(p, m, "L", None, int(compress_level))
         return {"paths": paths, "stats": {"images": len(plan), "annotations": sum(len(e) for e in plan.lists), "launches": 0}}
     import torch
-    from . import ops, preprocess
+    from . import preprocess
     painter = LabelPainter(plan, device, events)
     dev = painter.device
     groups, cur, used = [], [], 0
@@ -384,53 +377,16 @@ def write_semantic_masks(ground_truth, out_dir: str, *, image_ids: Optional[Sequ
     if cur:
         groups.append(cur)
     n_write = max(1, min(int(n_workers), preprocess.MAX_THREADS))
-    waiting = None
-
-    def hand_to_writers(slot, host, idx, off):
-        ring.events[slot].synchronize()                                            # the bytes are in the pinned buffer
-        a = host.numpy()
-        if on_device:                                                              # off: the streams' offsets; the length words lie behind them
-            lengths = a[len(a) - 4 * len(idx):].view(np.int32)
-            for k, i in enumerate(idx):
-                im, n = plan.images[i], int(lengths[k])
-                if not 0 < n <= off[k + 1] - off[k]:
-                    raise RuntimeError(f"write_semantic_masks: the device encoder left no stream for {paths[i]} ({im['h']} x {im['w']})")
-                ring.submit(slot, png_device.write_stream, paths[i], a[off[k]:off[k] + n], im["h"], im["w"], "L", None)
-            return
-        for k, i in enumerate(idx):
-            im = plan.images[i]
-            ring.submit(slot, _write_png, paths[i], a[off[k]:off[k + 1]].reshape(im["h"], im["w"]), int(compress_level))
-
-    with torch.cuda.device(dev), preprocess.WriterRing(True, n_write, "zutis-write", device=dev) as ring:
+    with torch.cuda.device(dev):
         try:
-            for k, idx in enumerate(groups):
-                slot = k & 1
-                total = sum(plan.images[i]["h"] * plan.images[i]["w"] for i in idx)
-                if on_device:
+            with picture_out.PictureStage(png_encoder, True, n_write, dev, compress_level=compress_level, events=events,
+                                          error="write_semantic_masks: the device encoder left no stream for {path} ({h} x {w})") as stage:
+                for k, idx in enumerate(groups):
                     sizes = [(plan.images[i]["h"], plan.images[i]["w"]) for i in idx]
-                    if min(min(s) for s in sizes) < 1:
+                    if on_device and min(min(s) for s in sizes) < 1:
                         raise ValueError("write_semantic_masks: an image without pixels has no PNG")
-                    off = np.concatenate(([0], np.cumsum([png_device.stream_bound(h, w, 1) for h, w in sizes]))).astype(np.int64)
-                    n_streams = (int(off[-1]) + 3) // 4 * 4
-                    host, dev_out = ring.take(slot, n_streams + 4 * len(idx))      # waits for the writers of launch k - 2
-                    raw, _ = painter.paint_ragged(idx)
-                    hw_dev, raw_off = painter.last_launch
-                    out_off = torch.from_numpy(off[:-1].copy()).to(dev)
-                    e = painter._event()
-                    ops.png_deflate(raw, raw_off[:len(idx)], hw_dev, 1, dev_out[:n_streams], out_off, dev_out[n_streams:].view(torch.int32),
-                                    max(png_device.segments(h, w, 1) for h, w in sizes))
-                    painter._event(e, "zh_png_deflate")
-                else:
-                    host, dev_out = ring.take(slot, total)                         # waits for the writers of launch k - 2
-                    _, off = painter.paint_ragged(idx, out=dev_out)
-                host.copy_(dev_out, non_blocking=True)                             # the one copy back of the launch
-                ring.events[slot].record()
-                if waiting is not None:
-                    hand_to_writers(*waiting)
-                waiting = (slot, host, idx, off)
-            if waiting is not None:
-                hand_to_writers(*waiting)
-            ring.drain()
+                    painter.paint_ragged(idx, out=stage.take(k, picture_out.Layout(sizes, [(1, "L", None)]), [paths[i] for i in idx]))
+                    stage.commit()                                                 # the one copy back of the launch
         finally:
             torch.cuda.synchronize(dev)
     return {"paths": paths, "stats": dict(painter.stats, launches=len(groups))}

@@ -193,25 +193,6 @@ def header_segment_bytes(header_text: str) -> int:
     return int(re.search(r"^#define\s+ZH_PNG_SEGMENT_BYTES\s+(\d+)", header_text, re.M).group(1))
 
 
-# ---- the device side (torch from here on, imported when used) --------------------------------------------------------------------------
-
-_UNIFORM = {}
-
-
-def uniform_descriptors(B: int, H: int, W: int, c: int, device):
-    """(img_off int64 [B], hw int32 [B, 2], out_off int64 [B]) on `device` for B images of one size back to back, their streams at
-    stream_bound(H, W, c) strides; made once per shape."""
-    import torch
-    key = (int(B), int(H), int(W), int(c), str(device))
-    if key not in _UNIFORM:
-        if len(_UNIFORM) > 64:
-            _UNIFORM.clear()
-        up = lambda a: torch.from_numpy(a).to(device)          # noqa: E731
-        _UNIFORM[key] = (up(np.arange(B, dtype=np.int64) * (H * W * c)), up(np.tile(np.asarray([H, W], np.int32), (B, 1))),
-                         up(np.arange(B, dtype=np.int64) * stream_bound(H, W, c)))
-    return _UNIFORM[key]
-
-
 def write_stream(path: str, stream, H: int, W: int, mode: str, palette_bytes: Optional[bytes]):
     """What a writer thread does with a finished stream: frame it (the IDAT CRC is the work) and write the file."""
     data = frame(stream, H, W, mode, palette_bytes)

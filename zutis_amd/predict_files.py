@@ -19,9 +19,8 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
-from PIL import Image
 
-from . import png_device, preprocess
+from . import picture_out, png_device, preprocess
 from .evaluate import _require_dropin, collect_instance_predictions
 from .preprocess import MAX_THREADS
 LABEL_LIMIT = {"u8": 256, "rg16": 65536}
@@ -192,15 +191,6 @@ def thread_split(n_workers: int, writers_needed: bool):
     return preprocess.thread_split(n_workers, 0.5)
 
 
-def _write_png(path: str, a: np.ndarray, mode: str, palette_bytes: Optional[bytes], compress_level: int):
-    im = Image.fromarray(a)                     # u8 [H, W] -> L, u8 [H, W, 3] -> RGB
-    if palette_bytes is not None:
-        im.putpalette(palette_bytes)            # L -> P: the bytes stay, the palette travels with them
-    if im.mode != mode:
-        raise ValueError(f"{path}: a mode {im.mode} image where {mode} was meant")
-    im.save(path, format="PNG", compress_level=compress_level)
-
-
 @torch.no_grad()
 def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[str] = None, out_paths: Optional[Sequence[str]] = None,
                        semantic: bool = True, label_format: str = "u8", palette=None, overlay: bool = False, alpha: int = 128,
@@ -271,7 +261,6 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     per_image: List[List[dict]] = [[] for _ in p_images]
     per_image_ids: List[List[int]] = [[] for _ in p_images]
     if p_images:
-        from . import ops
         eng = network._get_engine()
         dev = eng._device()
         n_decode, n_write = thread_split(n_workers, semantic or paint)
@@ -282,83 +271,32 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
         pal_dev = torch.from_numpy(pal).to(dev) if (overlay and pal is not None) else None
         colour_dev = torch.from_numpy(colour_table).to(dev) if colour_table is not None else None
         loader = preprocess.PredictBatchLoader(p_images, max_size, batch_size, n_decode, window=window)
-        waiting = None                                                                     # (slot, host bytes, indices, (H, W), parts) of the batch whose copy back is in flight
-
-        def hand_to_writers(slot, host, indices, H, W, parts):
-            ring.events[slot].synchronize()                                                # the bytes are in the pinned buffer
-            a = host.numpy()
-            B = len(indices)
-            at = 0
-            if on_device:                                                                  # streams at their bound's stride, then the length words
-                lengths = a[len(a) - 4 * B * len(parts):].view(np.int32)
-                for k, (paths, c, md, pb) in enumerate(parts):
-                    bound = png_device.stream_bound(H, W, c)
-                    for b, i in enumerate(indices):
-                        n = int(lengths[k * B + b])
-                        if not 0 < n <= bound:
-                            raise RuntimeError(f"predict_from_files: the device encoder left no stream for {paths[i]} ({H} x {W} x {c})")
-                        ring.submit(slot, png_device.write_stream, paths[i], a[at + b * bound:at + b * bound + n], H, W, md, pb)
-                    at += B * bound
-                return
-            for paths, c, md, pb in parts:                                                 # the byte ranges of the buffer, in the order they were laid out
-                view = a[at:at + B * H * W * c].reshape((B, H, W) if c == 1 else (B, H, W, c))
-                at += B * H * W * c
-                for b, i in enumerate(indices):
-                    ring.submit(slot, _write_png, paths[i], view[b], md, pb, int(compress_level))
-
-        def copy_back(slot, host, dev_out, batch, H, W, parts):
-            nonlocal waiting
-            if on_device:                                                                  # the pictures become their streams where they lie
-                B, at, raw = len(batch.indices), 0, 0
-                dev_streams = torch.empty((host.numel(),), dtype=torch.uint8, device=dev)
-                lengths = dev_streams[host.numel() - 4 * B * len(parts):].view(torch.int32)
-                for k, (_, c, _, _) in enumerate(parts):
-                    img_off, hw, out_off = png_device.uniform_descriptors(B, H, W, c, dev)
-                    bound = png_device.stream_bound(H, W, c)
-                    ops.png_deflate(dev_out[raw:raw + B * H * W * c], img_off, hw, c, dev_streams[at:at + B * bound], out_off,
-                                    lengths[k * B:(k + 1) * B], png_device.segments(H, W, c))
-                    raw += B * H * W * c
-                    at += B * bound
-                dev_out = dev_streams
-            host.copy_(dev_out, non_blocking=True)                                         # labels + overlay + instance pictures: one D2H
-            ring.events[slot].record()
-            if waiting is not None:
-                hand_to_writers(*waiting)                                                  # batch k - 1 is encoded while batch k is on the device
-            waiting = (slot, host, list(batch.indices), H, W, parts)
-
-        with preprocess.WriterRing(loader.pin, n_write, "zutis-write") as ring, \
-                preprocess.device_batches(loader, dev, preprocess.resize_normalize_of(lut)) as steps:
+        # name -> (paths, (c, mode, palette bytes)) of the kinds of picture the call writes, in layout order; the id map's once Q is known
+        kinds = {name: kind for name, kind in (("labels", (label_paths, (ch, mode, pal_bytes))), ("overlay", (overlay_paths, (3, "RGB", None))),
+                                               ("ids", (map_paths, None)), ("instance_overlay", (iovl_paths, (3, "RGB", None)))) if kind[0] is not None}
+        with preprocess.device_batches(loader, dev, preprocess.resize_normalize_of(lut)) as steps, \
+                picture_out.PictureStage(png_encoder, loader.pin, n_write, dev, compress_level=compress_level,
+                                         error="predict_from_files: the device encoder left no stream for {path} ({h} x {w} x {c})") as stage:
             for k, (batch, (packed, desc), x) in enumerate(steps):
                 B, (H, W) = len(batch.paths), batch.size_hw
                 if (overlay or instance_overlay) and batch.n_host:
                     raise NotImplementedError(f"predict_from_files: {batch.host_paths[0]} was resized on the host (a side more than 75 times its "
                                               f"target): its decoded image is not on the device at file size, no overlay can be made")
                 out = network(x)                                                           # the module's forward: its hipGraph replay applies
-                if semantic or paint:
-                    slot = k % 2
-                    nl = B * H * W * ch if semantic else 0
-                    no = 3 * B * H * W if overlay else 0
-                    parts = ([(label_paths, ch, mode, pal_bytes)] if semantic else []) + ([(overlay_paths, 3, "RGB", None)] if overlay else [])
-                    nm = ni = 0
-                    if paint:
-                        Q = int(out["mask_proposals"].shape[-3])
-                        id_format = "u8" if Q <= 255 else "rg16"
-                        nm = B * H * W * LABEL_CHANNELS[id_format] if instance_map else 0
-                        ni = 3 * B * H * W if instance_overlay else 0
-                        parts += ([(map_paths, LABEL_CHANNELS[id_format], "L" if id_format == "u8" else "RGB", None)] if instance_map else []) + \
-                                 ([(iovl_paths, 3, "RGB", None)] if instance_overlay else [])
-                    n_host = nl + no + nm + ni
-                    if on_device:                                                          # the streams' strides, 4-byte aligned, one length word per picture
-                        n_host = (sum(B * png_device.stream_bound(H, W, c) for _, c, _, _ in parts) + 3) // 4 * 4 + 4 * B * len(parts)
-                    host, _ = ring.take(slot, n_host)                                      # waits for the writers of batch k - 2
-                    dev_out = torch.empty((nl + no + nm + ni,), dtype=torch.uint8, device=dev)
-                    if semantic:
-                        eng.label_bytes(out["patch_tokens"], network.text_embeddings, (H, W), label_format=label_format,
-                                        labels_out=dev_out[:nl].view((B, H, W) if ch == 1 else (B, H, W, ch)), palette=pal_dev,
-                                        packed=packed if overlay else None, desc=desc if overlay else None, alpha=int(alpha),
-                                        overlay_out=dev_out[nl:nl + no].view(B, H, W, 3) if overlay else None, desc_host=batch.desc)
-                    if not paint:
-                        copy_back(slot, host, dev_out, batch, H, W, parts)
+                if paint:
+                    Q = int(out["mask_proposals"].shape[-3])
+                    id_format = "u8" if Q <= 255 else "rg16"
+                    if instance_map:
+                        kinds["ids"] = (map_paths, (LABEL_CHANNELS[id_format], "L" if id_format == "u8" else "RGB", None))
+                if kinds:
+                    layout = picture_out.Layout([(H, W)] * B, [kind for _, kind in kinds.values()])
+                    view = dict(zip(kinds, layout.views(stage.take(k, layout, [paths[i] for paths, _ in kinds.values() for i in batch.indices]))))
+                if semantic:
+                    eng.label_bytes(out["patch_tokens"], network.text_embeddings, (H, W), label_format=label_format, labels_out=view["labels"],
+                                    palette=pal_dev, packed=packed if overlay else None, desc=desc if overlay else None, alpha=int(alpha),
+                                    overlay_out=view.get("overlay"), desc_host=batch.desc)
+                if kinds and not paint:
+                    stage.commit()                                                         # labels + overlay: one D2H
                 if instance and not paint:
                     collect_instance_predictions(network, out, batch, image_ids, per_image, label_id_to_category=label_id_to_category,
                                                  new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type)
@@ -372,19 +310,14 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
                         new_label_id_to_old_label_id=new_label_id_to_old_label_id, nms_type=nms_type, packed=packed, desc=desc, desc_host=batch.desc,
                         colours=colour_dev[:Q].unsqueeze(0).expand(B, Q, 3).contiguous() if colour_mode == "array" else None,
                         palette=colour_dev if colour_mode == "category" else None, alpha=int(alpha), outline=bool(instance_outline),
-                        min_score=float(instance_min_score), id_format=id_format,
-                        ids_out=dev_out[nl + no:nl + no + nm].view((B, H, W) if id_format == "u8" else (B, H, W, 3)) if instance_map else None,
-                        overlay_out=dev_out[nl + no + nm:].view(B, H, W, 3) if instance_overlay else None)
+                        min_score=float(instance_min_score), id_format=id_format, ids_out=view.get("ids"), overlay_out=view.get("instance_overlay"))
                     for p, pid in zip(preds, ids):
                         i = p["image_id"]
                         p["image_id"] = image_ids[i] if image_ids is not None else 0
                         per_image[i].append(p)
                         per_image_ids[i].append(pid)
-                    copy_back(slot, host, dev_out, batch, H, W, parts)
-            if waiting is not None:
-                hand_to_writers(*waiting)
-            ring.drain()
-            eng.check_finite()                                                             # the forwards' status word: one read for the whole run
+                    stage.commit()                                                         # labels + overlay + instance pictures: one D2H
+        eng.check_finite()                                                                 # the forwards' status word: one read for the whole run
     predictions = [p for ps in per_image for p in ps]
     if predictions_json is not None:
         d = os.path.dirname(os.fspath(predictions_json))

@@ -21,6 +21,7 @@ is also what crosses PCIe (3 bytes per source pixel instead of 12 per output pix
   PredictBatchLoader    its constructor for prediction: EvalBatchLoader's batches without the ground truth
   device_batches        the per-batch device sequence of every driver: H2D, event, views, the resize kernel, clean-up
   WriterRing            two output slots (pinned buffer, event, writer futures) over a pool of writer threads; thread_split beside it
+  (picture_out.py)      over WriterRing, the output side of the drivers that write pictures: Layout and PictureStage (take, fill, commit)
 
 Threads, not processes: no child ever holds the device open, nothing is pickled, a worker's exception is raised by the caller.
 """
