@@ -458,8 +458,9 @@ int zh_mask_rle_fused_kept(const unsigned char* masks, const unsigned long long*
  * image byte where there is no top; else with c = colours[b, top(p)]: c itself when outline != 0 and a 4-neighbour INSIDE the image has
  * another top (another slot, or none), otherwise (img * (256 - alpha) + c * alpha + 128) >> 8 per channel, alpha in 0..256 — the integers
  * of zh_upsample_argmax_bytes.  Pixels without a top are never outline pixels; the image border alone makes no outline.  img: packed +
- * desc under the contract of zh_upsample_argmax_bytes (NOT checked here; read only with an overlay).  Q <= 1024 (the rank table lives in
- * LDS).  workspace >= zh_instance_paint_workspace_size bytes, 16-byte aligned: the rank table and a u16 id per pixel for the outline. */
+ * desc under the contract of zh_upsample_argmax_bytes (NOT checked here; read only with an overlay).  Q <= ZH_PAINT_MAX_Q (the rank table
+ * lives in LDS).  workspace >= zh_instance_paint_workspace_size bytes, 16-byte aligned: the rank table and a u16 id per pixel for the outline. */
+#define ZH_PAINT_MAX_Q 1024
 size_t zh_instance_paint_workspace_size(int B, int Q, int H, int W);
 int zh_instance_paint(const unsigned char* masks, const unsigned long long* bits, const int* index, const double* score, const int* count,
                       const unsigned char* colours, int alpha, int outline, double min_score, const unsigned char* packed, const int* desc,
@@ -521,8 +522,10 @@ int zh_gemm_f32_strided(const float* A, long sAb, long sAm, long sAk, const floa
  * sum_b L * min(n_b, Q) rows), *n_pairs, *mask_loss = f32(float64 sum of the matched costs in that order / B).  An image with
  * skip[b] != 0 or no instance gives no pairs.  A problem with a non-finite cost gives no pairs and ORs ZH_STATUS_NONFINITE into
  * *status — unlike scipy, which accepts +inf entries, every cost must be finite (zh_mask_match_cost cannot produce a non-finite cost
- * without having set ZH_STATUS_RANGE).  Limit: max(n_max, Q) <= zh_linear_assignment_max_dim() = 1024 (32 bytes of LDS state per
- * column, 16 per row: 48 KB at the cap), ZH_ERR_ARG above it.  workspace >= zh_linear_assignment_workspace_size. */
+ * without having set ZH_STATUS_RANGE).  Limit: max(n_max, Q) <= ZH_ASSIGN_MAX_DIM (32 bytes of LDS state per column, 16 per row:
+ * 48 KB at the cap; zh_linear_assignment_max_dim() = the value the library was built with), ZH_ERR_ARG above it.
+ * workspace >= zh_linear_assignment_workspace_size. */
+#define ZH_ASSIGN_MAX_DIM 1024
 int zh_linear_assignment_max_dim(void);
 size_t zh_linear_assignment_workspace_size(int B, int L, int n_tot);
 int zh_linear_assignment(const float* costs, const int* inst_off, const int* skip, int B, int L, int Q, int n_max, int n_tot,

@@ -65,7 +65,7 @@ def test_header_declares_both_entries_and_their_argument_types(lib):
 
 
 def test_cap_and_argument_checks_without_gpu(lib):
-    assert lib.zh_linear_assignment_max_dim() == ops.ASSIGN_MAX_DIM == 1024
+    assert lib.zh_linear_assignment_max_dim() == _lib.constants()["ZH_ASSIGN_MAX_DIM"] == ops.ASSIGN_MAX_DIM == 1024
     assert lib.zh_linear_assignment_workspace_size(8, 6, 80) == 8 * 6 * 8 + 6 * 80 * 4
     ok = (16, 16, 16, 1, 1)                                 # non-null dummies: the checks come before any launch
     rc = lib.zh_linear_assignment(*ok, ops.ASSIGN_MAX_DIM + 1, 2, 2, 16, 16, 16, 16, 16, 1 << 20, None)

@@ -71,6 +71,75 @@ def test_unreadable_header_is_an_error():
         _lib.parse_declarations(ok + "int zh_c(int, zh_stream_t stream);\n")
 
 
+def test_header_constants():
+    """_lib.constants(): every `#define ZH_<NAME> <integer>` of the header, parenthesised negatives included; strict, and blind
+    to comments."""
+    c = _lib.constants()
+    assert c["ZH_ERR_WORKSPACE"] == -3 and c["ZH_RCN_KMAX"] == 152 and c["ZH_PNG_SEGMENT_BYTES"] == 16384 and c["ZH_FILTER_BICUBIC"] == 3
+    assert c["ZH_OK"] == 0 and c["ZH_ABI_VERSION"] == _lib.header_abi_version() and all(type(v) is int for v in c.values())
+    ok = "#define ZH_A 7 /* seven */\n#define ZH_B (-2)\n  #  define ZH_C ( - 3 )\n#define OTHER foo\n"
+    assert _lib.parse_constants(ok) == {"ZH_A": 7, "ZH_B": -2, "ZH_C": -3}
+    for bad in ("#define ZH_X foo\n", "#define ZH_X\n", "#define ZH_X 1 + 2\n", "#define ZH_X(a) 3\n"):
+        with pytest.raises(_lib.ZutisHipError, match="ZH_X"):
+            _lib.parse_constants(ok + bad)
+    assert _lib.parse_constants(ok + "/* #define ZH_X foo */\n/* text\n#define ZH_Y 5\n*/\n") == _lib.parse_constants(ok)
+
+
+def test_kernel_sources_compile_against_the_header():
+    """The header is the one definition on the C side too: csrc/common.h includes it and every source reaches common.h (so the
+    compiler checks each entry point against its prototype), no file under csrc/ defines a name the header defines, and every
+    extern "C" zh_* definition is a declared entry point."""
+    import re
+    csrc = build.CSRC
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    includes = {f: set(re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', t, re.M)) for f, t in text.items()}
+    assert os.path.samefile(os.path.join(csrc, "../../include/zutis_hip.h"), _lib.HEADER)
+    assert "../../include/zutis_hip.h" in includes["common.h"]
+
+    def reaches_common(f, seen=()):
+        return f == "common.h" or any(reaches_common(g, seen + (f,)) for g in includes.get(f, ()) if g not in seen)
+    hips = [f for f in text if f.endswith(".hip")]
+    assert sorted(hips) == sorted(build.SOURCES) and not [f for f in hips if not reaches_common(f)]
+    for f, t in text.items():
+        redefined = set(re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)", t, re.M)) & set(_lib.constants())
+        assert not redefined, (f, sorted(redefined))
+    defined = [n for t in text.values() for n in re.findall(r'extern\s+"C"\s+[^(){};]*?\b(zh_[a-z0-9_]+)\s*\(', t)]
+    assert len(defined) >= 90 and len(set(defined)) == len(defined)
+    assert not [n for n in defined if n not in _lib.entries()]
+
+
+def test_depfile_reader_and_staleness(tmp_path):
+    """build.read_depfile reads what the compiler's -MD -MF writes (continuation lines, `\\ ` for a space in a path); build.stale:
+    an object is stale when it or its depfile is missing, or when a file the depfile names is newer or gone."""
+    a, b, c = tmp_path / "a.hip", tmp_path / "dir with space" / "b.h", tmp_path / "c.h"
+    b.parent.mkdir()
+    for i, f in enumerate((a, b, c)):
+        f.write_text("")
+        os.utime(f, (1000 + i, 1000 + i))
+    obj, dep = tmp_path / "a.o", tmp_path / "a.d"
+    esc = lambda p: str(p).replace(" ", "\\ ")
+    text = f"{esc(obj)}: {esc(a)} \\\n  {esc(b)} \\\n  {esc(c)}\n"
+    assert build.stale(str(obj), str(dep))                       # neither exists
+    dep.write_text(text)
+    assert build.read_depfile(str(dep)) == [str(a), str(b), str(c)]
+    assert build.stale(str(obj), str(dep))                       # no object
+    obj.write_text("")
+    os.utime(obj, (2000, 2000))
+    assert not build.stale(str(obj), str(dep))
+    os.utime(b, (2000, 2000))
+    assert not build.stale(str(obj), str(dep))                   # as old as the object: not newer
+    os.utime(b, (2001, 2001))
+    assert build.stale(str(obj), str(dep))                       # the header behind the escaped space is newer
+    os.utime(obj, (2002, 2002))
+    assert not build.stale(str(obj), str(dep))
+    c.unlink()
+    assert build.stale(str(obj), str(dep))                       # a named file is gone
+    dep.write_text(f"{esc(obj)}: {esc(a)}\n{esc(obj)}: {esc(b)}\n")          # one rule per compilation of the same source
+    assert build.read_depfile(str(dep)) == [str(a), str(b)] and not build.stale(str(obj), str(dep))
+    dep.unlink()
+    assert build.stale(str(obj), str(dep))                       # no depfile
+
+
 def test_version_arch_and_error_text(lib):
     assert lib.zh_version() == _lib.header_abi_version() >= 210        # a stale build is refused by _lib.load()
     assert lib.zh_arch() == b"gfx950"

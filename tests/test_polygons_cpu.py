@@ -141,9 +141,9 @@ def test_header_declares_the_polygon_entries():
     assert (e["zh_polygon_runs"].restype, e["zh_polygon_runs"].argtypes) == (i, [vp] * 8 + [i, vp, vp, vp]) and e["zh_polygon_runs"].plannable
     assert (e["zh_polygon_lds_crossings"].restype, e["zh_polygon_lds_crossings"].argtypes) == (i, [])
     assert _lib.header_abi_version() >= 236
-    limit = int(re.search(r"^#define\s+ZH_POLYGON_LDS_CROSSINGS\s+(\d+)", open(_lib.HEADER).read(), re.M).group(1))
+    limit = _lib.constants()["ZH_POLYGON_LDS_CROSSINGS"]
     from zutis_amd import ops
-    assert lib.zh_polygon_lds_crossings() == limit == polygons.LDS_CROSSINGS == ops.POLYGON_LDS_CROSSINGS
+    assert lib.zh_polygon_lds_crossings() == limit == polygons.LDS_CROSSINGS == ops.POLYGON_LDS_CROSSINGS == 4096   # the library was compiled with the header's value
     assert 4 * limit + 2 * limit + 4 * limit + 64 <= 64 * 1024                    # keys, coverage, boundaries: inside one workgroup's 64 KB
     assert lib.zh_polygon_runs(None, None, None, None, None, None, None, None, 0, None, None, None) == 0          # an empty call launches nothing
     assert lib.zh_polygon_runs(None, 16, 16, 16, 16, 16, 16, 16, 1, 16, 16, None) == -1 and b"null" in lib.zh_last_error()

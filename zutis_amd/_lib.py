@@ -82,12 +82,29 @@ def declared_symbols():
     return sorted(entries())
 
 
+def parse_constants(text: str) -> dict:
+    """{name: int} for every `#define ZH_<NAME> <integer>` of `text` (the header) outside comments; a negative value stands in
+    parentheses.  Strict like parse_declarations: a `#define ZH_...` whose value is not such an integer is an error."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    out = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(ZH_\w*)(.*)$", text, re.M):
+        m = re.fullmatch(r"\s+(\d+|\(\s*-\s*\d+\s*\))\s*", value)
+        if not m:
+            raise ZutisHipError(f"include/zutis_hip.h: cannot read `#define {name}{value.rstrip()}` as an integer constant")
+        out[name] = int(re.sub(r"[()\s]", "", m.group(1)))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def constants() -> dict:
+    """parse_constants() of include/zutis_hip.h: the values the kernels were compiled with (csrc/common.h includes the same header),
+    read by every Python module that names one."""
+    return parse_constants(_header_text())
+
+
 def header_abi_version() -> int:
     """ZH_ABI_VERSION of include/zutis_hip.h (the header travels with the package: bindings and library must agree on it)."""
-    m = re.search(r"^#define\s+ZH_ABI_VERSION\s+(\d+)", _header_text(), re.M)
-    if not m:
-        raise ZutisHipError(f"{HEADER}: ZH_ABI_VERSION not found")
-    return int(m.group(1))
+    return constants()["ZH_ABI_VERSION"]
 
 
 RECORDER = None   # zutis_amd.plan.Recorder while a launch plan is being recorded

@@ -5,6 +5,7 @@
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 import sys
 
@@ -41,14 +42,34 @@ def sources():
     return [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
 
 
+def _obj(src: str) -> str:
+    return os.path.join(HERE, "_obj", os.path.basename(src)[:-4] + ".o")
+
+
+def read_depfile(path: str) -> list:
+    """The prerequisites a compiler-written depfile (-MD -MF) names: `target: dep dep \\<newline> dep`, a space inside a path
+    written `\\ `.  It lists the source and every file the translation unit read."""
+    deps = []
+    for rule in open(path).read().replace("\\\n", " ").splitlines():
+        m = re.match(r"(?:\\ |\S)+?:(?:\s|$)", rule)
+        if m:
+            deps += [d.replace("\\ ", " ") for d in re.findall(r"(?:\\ |\S)+", rule[m.end():])]
+    return deps
+
+
+def stale(obj: str, depfile: str) -> bool:
+    """An object is stale when it or its depfile is missing, or when a file the depfile names is newer (or gone)."""
+    if not (os.path.exists(obj) and os.path.exists(depfile)):
+        return True
+    t = os.path.getmtime(obj)
+    return any(not os.path.exists(d) or os.path.getmtime(d) > t for d in read_depfile(depfile))
+
+
 def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
-    t = os.path.getmtime(LIB)
-    deps = sources() + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_kernel.h"), os.path.join(CSRC, "gemm_skinny.h"),
-                        os.path.join(CSRC, "gemm_dispatch.h"),
-                        os.path.join(CSRC, "rcn.h"), os.path.join(os.path.dirname(HERE), "include", "zutis_hip.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+    objs = [_obj(s) for s in sources()]
+    return any(stale(o, o[:-2] + ".d") for o in objs) or any(os.path.getmtime(o) > os.path.getmtime(LIB) for o in objs)
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
@@ -57,25 +78,16 @@ def build(force: bool = False, verbose: bool = True) -> str:
     objs = []
     os.makedirs(os.path.join(HERE, "_obj"), exist_ok=True)
     from . import plan
-    plan.generate_dispatch(os.path.join(CSRC, "plan_gen.inc"))      # launch-plan dispatcher, generated from the header
+    plan.generate_dispatch(os.path.join(CSRC, "plan_gen.inc"))      # launch-plan dispatcher, generated from the header (rewritten only when its text changes)
     procs = []
     for src in sources():
-        obj = os.path.join(HERE, "_obj", os.path.basename(src)[:-4] + ".o")
+        obj = _obj(src)
+        dep = obj[:-2] + ".d"
         objs.append(obj)
-        deps = [src, os.path.join(CSRC, "common.h")]
-        if os.path.basename(src).startswith("gemm"):
-            deps.append(os.path.join(CSRC, "gemm_kernel.h"))
-            deps.append(os.path.join(CSRC, "gemm_skinny.h"))
-        if os.path.basename(src).startswith("gemm") or os.path.basename(src) == "capi.hip":     # the tile choice; capi.hip: zh_dev_gemm_plan
-            deps.append(os.path.join(CSRC, "gemm_dispatch.h"))
-        if os.path.basename(src) in ("preprocess.hip", "synth.hip"):
-            deps.append(os.path.join(CSRC, "rcn.h"))
-        if os.path.basename(src) in ("plan.hip", "capi.hip"):       # the dispatcher generated from the header / ZH_ABI_VERSION
-            deps.append(os.path.join(os.path.dirname(HERE), "include", "zutis_hip.h"))
-        if not force and os.path.exists(obj) and all(os.path.getmtime(obj) > os.path.getmtime(d) for d in deps):
+        if not force and not stale(obj, dep):
             continue
         cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17"] + EXTRA_FLAGS.get(os.path.basename(src), []) + \
-              ["-c", src, "-o", obj]
+              ["-MD", "-MF", dep, "-c", src, "-o", obj]
         if os.path.basename(src) in NO_SCRATCH:
             cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         if verbose:

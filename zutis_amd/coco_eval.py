@@ -27,7 +27,7 @@ REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=
 AREA_RANGES = np.array([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], dtype=np.float64)
 AREA_LABELS = ("all", "small", "medium", "large")
 CHUNK_BYTES = 64 << 20        # device bytes one chunk of groups may take (match_on_device's default)
-LDS_RUNS = 1024               # ZH_RLE_IOU_LDS_RUNS: ground truths of up to this many runs are searched in LDS
+LDS_RUNS = _lib.constants()["ZH_RLE_IOU_LDS_RUNS"]               # ground truths of up to this many runs are searched in LDS
 GROUP_WORDS = 8
 
 

@@ -17,8 +17,7 @@
 // stays in cache).  __syncthreads() of a one-wave workgroup is no s_barrier, only the LDS ordering the compiler must keep.
 #include "common.h"
 
-#define ZH_STATUS_NONFINITE 2
-#define AS_MAX_DIM 1024   // cap on max(n_b, Q): 32 bytes per column + 16 per row of LDS state = 48 KB at the cap (64 KB per workgroup)
+// ZH_ASSIGN_MAX_DIM caps max(n_b, Q): 32 bytes per column + 16 per row of LDS state = 48 KB at the cap (64 KB per workgroup)
 #define AS_COL_BYTES 32   // v f64, shortest f64, path i32, row4col i32, remaining i32, SC i32
 #define AS_ROW_BYTES 16   // u f64, col4row i32, SR i32
 
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(64) void linear_assignment_kernel(const float* cost
         const double r = min_val + (double)c[i * rs + j * cs] - ui - v[j];
         double s = shortest[j];
         if (r < s) { path[j] = i; shortest[j] = r; s = r; }
-        const int score = row4col[j] < 0 ? AS_MAX_DIM + it : -it;
+        const int score = row4col[j] < 0 ? ZH_ASSIGN_MAX_DIM + it : -it;
         if (as_better(s, score, bv, bs)) { bv = s; bs = score; bpos = it; }
       }
 #pragma unroll
@@ -175,7 +174,7 @@ __global__ __launch_bounds__(256) void assignment_finish_kernel(const int* match
   }
 }
 
-extern "C" int zh_linear_assignment_max_dim(void) { return AS_MAX_DIM; }
+extern "C" int zh_linear_assignment_max_dim(void) { return ZH_ASSIGN_MAX_DIM; }
 
 extern "C" size_t zh_linear_assignment_workspace_size(int B, int L, int n_tot) {
   return (size_t)B * L * sizeof(double) + (size_t)L * (n_tot > 0 ? n_tot : 0) * sizeof(int);
@@ -188,8 +187,8 @@ extern "C" int zh_linear_assignment(const float* costs, const int* inst_off, con
   ZH_CHECK_ARG(B > 0 && L > 0 && Q > 0 && n_max >= 0 && n_tot >= 0 && n_max <= n_tot, "zh_linear_assignment: bad shape");
   ZH_CHECK_ARG(n_tot == 0 || (costs && pairs), "zh_linear_assignment: null costs / pairs");
   ZH_CHECK_ARG(((uintptr_t)pairs & 15) == 0, "zh_linear_assignment: pairs must be 16-byte aligned");
-  ZH_CHECK_ARG(Q <= AS_MAX_DIM && n_max <= AS_MAX_DIM, "zh_linear_assignment: max(n_max = %d, Q = %d) exceeds the cap of %d (LDS state)",
-               n_max, Q, AS_MAX_DIM);
+  ZH_CHECK_ARG(Q <= ZH_ASSIGN_MAX_DIM && n_max <= ZH_ASSIGN_MAX_DIM, "zh_linear_assignment: max(n_max = %d, Q = %d) exceeds the cap of %d (LDS state)",
+               n_max, Q, ZH_ASSIGN_MAX_DIM);
   ZH_CHECK_ARG(workspace_bytes >= zh_linear_assignment_workspace_size(B, L, n_tot), "zh_linear_assignment: workspace too small");
   double* psum = (double*)workspace;
   int* match = (int*)(psum + (long)B * L);

@@ -1,6 +1,5 @@
 // C-ABI plumbing for libzutis_hip: version + thread-local error text.
 #include "common.h"
-#include "../../include/zutis_hip.h"
 #include <stdarg.h>
 
 static thread_local char g_err[512] = "";

@@ -16,7 +16,7 @@
 // IoU is ONE float64 division of two integers, so it is NumPy's bit for bit.
 #include "common.h"
 
-#define ZH_RLE_IOU_LDS_RUNS 1024   // include/zutis_hip.h: 8 KB of LDS per wave, 20 waves a CU
+// ZH_RLE_IOU_LDS_RUNS = 1024 runs: 8 KB of LDS per wave, 20 waves a CU
 #define CM_MAX_PROBLEMS 64         // T * A problems of a group = lanes of its wave
 #define GROUP_WORDS 8              // det_off, D, gt_off, G, pair_off, 0, 0, 0
 

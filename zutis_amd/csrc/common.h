@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include "../../include/zutis_hip.h"   // the ABI: every entry point's prototype (checked against its definition here) and every ZH_* constant
 
 typedef _Float16 half_t;
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
@@ -10,11 +11,6 @@ typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define ZH_OK 0
-#define ZH_ERR_ARG (-1)
-#define ZH_ERR_HIP (-2)
-#define ZH_ERR_WORKSPACE (-3)
 
 // thread-local last-error text, returned by zh_last_error()
 void zh_set_error(const char* fmt, ...);
@@ -107,13 +103,7 @@ __device__ __forceinline__ LinW lin_weights(int dst, int in_size, int out_size, 
   return r;
 }
 
-// activation codes shared by the GEMM epilogue (include/zutis_hip.h ZH_ACT_*)
-#define ZH_ACT_NONE 0
-#define ZH_ACT_QUICKGELU 1   // x * sigmoid(1.702 x)      networks/clip_arch.py:295-297
-#define ZH_ACT_RELU 2        // networks/zutis.py:546-549, networks/transformer.py:289
-#define ZH_ACT_SIGMOID 3     // networks/zutis.py:209
-#define ZH_ACT_GELU_ERF 4    // nn.GELU, networks/selfmask/vision_transformer.py:79
-
+// the GEMM epilogue's activations (ZH_ACT_* of include/zutis_hip.h)
 __device__ __forceinline__ float zh_act(float x, int act) {
   // v_exp_f32 / v_rcp_f32 (1 ulp) instead of IEEE expf + division: the epilogue of the 14144x3072 c_fc GEMM spends
   // 43 M activations per call; results differ from the libm form by < 2e-7 relative (tests: 2e-4 abs on O(1) values).

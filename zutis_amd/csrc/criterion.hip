@@ -12,9 +12,6 @@
 //            thread and summed in a fixed order, so the gradients are bitwise reproducible (no float atomics).
 #include "common.h"
 
-#define ZH_STATUS_RANGE 1
-#define ZH_STATUS_LABEL 4
-
 // ---- adjoint window: the full-resolution indices d whose bilinear weights touch low-res index i (a superset; the caller
 //      weighs each d with adj_weight, which is 0 outside the true support)
 __device__ __forceinline__ void adj_window(int i, int n_in, int n_out, float scale, int& lo, int& hi) {

@@ -261,7 +261,7 @@ static inline int gemm_plan_x3(const GemmProblem& q, const GemmDevOverrides& ov,
   // family only, whose K order is the same for every tile.  Otherwise: few rows AND a grid small enough that the kernel's re-reads of
   // the row block (once per 32 output columns) do not matter — the class-logit GEMM of a 32-image batch (81 x 1764 x 512 x 32 =
   // 5376 workgroups) took 113 us here against ~20 on the ring.
-  const int max_rows = forced == 32 ? (1 << 30) : ((forced || (q.flags & 1)) ? 0 : ZH_SKINNY_MAX_ROWS);
+  const int max_rows = forced == 32 ? (1 << 30) : ((forced || (q.flags & ZH_GEMM_FIXED_K_ORDER)) ? 0 : ZH_SKINNY_MAX_ROWS);
   const long sk_blocks = gemm_tiles(q, 32, 32);
   if (!q.has_pos && M <= max_rows && sk_blocks <= 65535L * 8 && (forced == 32 || sk_blocks <= ZH_SKINNY_MAX_BLOCKS)) {
     *plan = {GEMM_SKINNY, 32, gemm_vec_ok(q) ? 1 : 0, 0};

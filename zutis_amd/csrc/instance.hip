@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void instance_stats_kernel(const float* mp, lo
   cnt = stats_block_sum(cnt, red);
   s = stats_block_sum(s, red);
   if (threadIdx.x == 0) { sizes[r] = cnt; conf[r] = s / (cnt + 1e-7f); }
-  if (range_flag && __ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(range_flag, 1);
+  if (range_flag && __ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(range_flag, ZH_STATUS_RANGE);
 }
 
 extern "C" int zh_instance_mask_stats(const float* mask_proposals, long stride_image, float threshold, int B, int Q, int M,

@@ -13,10 +13,6 @@
 //                        neighbours cannot come from the wave's own word), outline or blend.
 #include "common.h"
 
-#define ZH_GT_U8 0
-#define ZH_GT_RG16 1
-#define PAINT_MAX_Q 1024
-
 struct PaintArgs {
   const unsigned char* masks;           // u8 [B,Q,H,W] (read when bits is NULL)
   const unsigned long long* bits;       // u64 [B*Q][W64] or NULL
@@ -34,8 +30,8 @@ struct PaintArgs {
 
 __global__ __launch_bounds__(256) void paint_rank_kernel(const int* index, const double* score, const int* count, double min_score, int Q,
                                                          int2* order, int* npaint) {
-  __shared__ double sc[PAINT_MAX_Q];
-  __shared__ unsigned char on[PAINT_MAX_Q];
+  __shared__ double sc[ZH_PAINT_MAX_Q];
+  __shared__ unsigned char on[ZH_PAINT_MAX_Q];
   __shared__ int n_on;
   const int b = blockIdx.x;
   const int c = min(max(count[b], 0), Q);                    // entries past the count are uninitialised: never read
@@ -150,7 +146,7 @@ extern "C" int zh_instance_paint(const unsigned char* masks, const unsigned long
   ZH_CHECK_ARG((masks || bits) && index && score && count && (ids_out || overlay_out) && B > 0 && B <= 65535 && Q > 0 && H > 0 && W > 0 &&
                (long)H * W < (1L << 31) && (id_format == ZH_GT_U8 || id_format == ZH_GT_RG16) && (outline == 0 || outline == 1),
                "zh_instance_paint: bad arguments");
-  ZH_CHECK_ARG(Q <= PAINT_MAX_Q, "zh_instance_paint: at most %d slots per image (the rank table lives in LDS)", PAINT_MAX_Q);
+  ZH_CHECK_ARG(Q <= ZH_PAINT_MAX_Q, "zh_instance_paint: at most %d slots per image (the rank table lives in LDS)", ZH_PAINT_MAX_Q);
   ZH_CHECK_ARG(!ids_out || id_format == ZH_GT_RG16 || Q <= 255, "zh_instance_paint: ids up to %d do not fit one byte: use the rg16 format", Q);
   ZH_CHECK_ARG(!overlay_out || (colours && packed && desc && alpha >= 0 && alpha <= 256),
                "zh_instance_paint: an overlay needs colours, packed, desc and alpha in 0..256");

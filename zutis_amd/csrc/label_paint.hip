@@ -15,12 +15,8 @@
 // Every loop is bounded by a count the launch checks against the arrays' lengths, every search by 32 steps.
 #include "common.h"
 
-#define LP_TW 32          // ZH_LABEL_TILE_W x ZH_LABEL_TILE_H of include/zutis_hip.h: a wave stores two 32-byte row segments
-#define LP_TH 8
-#define LP_THREADS (LP_TW * LP_TH)
+#define LP_THREADS (ZH_LABEL_TILE_W * ZH_LABEL_TILE_H)    // a 32 x 8 tile: a wave stores two 32-byte row segments
 #define LP_STAGE 256      // list entries staged per pass: one per thread, 3 KB of LDS
-#define ZH_OVERLAP_LAST 0
-#define ZH_OVERLAP_IGNORE 1
 
 __global__ __launch_bounds__(LP_THREADS) void runs_label_maps_kernel(const int* run_end, const int* run_off, const int* status, int n_masks,
                                                                       long n_runs, const int* list_off, const int* list_mask,
@@ -32,15 +28,15 @@ __global__ __launch_bounds__(LP_THREADS) void runs_label_maps_kernel(const int* 
   const int b = blockIdx.y, tid = threadIdx.x;
   const int h = hw[2 * b], w = hw[2 * b + 1];
   if (h < 1 || w < 1 || (long)h * w > 0x7fffffffL) return;                     // block-uniform, as every exit in front of a barrier
-  const int tiles_x = (w + LP_TW - 1) / LP_TW, tiles_y = (h + LP_TH - 1) / LP_TH;
+  const int tiles_x = (w + ZH_LABEL_TILE_W - 1) / ZH_LABEL_TILE_W, tiles_y = (h + ZH_LABEL_TILE_H - 1) / ZH_LABEL_TILE_H;
   if ((long)blockIdx.x >= (long)tiles_x * tiles_y) return;
   const long long base = out_off[b];
   if (base < 0 || base + (long long)h * w > (long long)out_bytes) return;       // an image that does not fit its buffer is not written
-  const int x0 = ((int)blockIdx.x % tiles_x) * LP_TW, y0 = ((int)blockIdx.x / tiles_x) * LP_TH;
-  const int x = x0 + (tid & (LP_TW - 1)), y = y0 + tid / LP_TW;
+  const int x0 = ((int)blockIdx.x % tiles_x) * ZH_LABEL_TILE_W, y0 = ((int)blockIdx.x / tiles_x) * ZH_LABEL_TILE_H;
+  const int x = x0 + (tid & (ZH_LABEL_TILE_W - 1)), y = y0 + tid / ZH_LABEL_TILE_W;
   const bool inb = x < w && y < h;
   const int p = inb ? x * h + y : 0;                                           // < h * w <= 2^31 - 1
-  const int c_lo = x0, c_hi = min(x0 + LP_TW, w) - 1;                          // the tile's columns
+  const int c_lo = x0, c_hi = min(x0 + ZH_LABEL_TILE_W, w) - 1;                          // the tile's columns
   const int l0 = list_off[b], l1 = (l0 < 0 || list_off[b + 1] > n_list) ? l0 : list_off[b + 1];    // a list outside the arrays: empty
   int hits = 0, label = 0;
   bool done = !inb;

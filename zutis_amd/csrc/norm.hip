@@ -9,12 +9,11 @@ struct LnRow {
   f32x4 v[LN_MAXV];
 };
 
-// The engine's status word (optional `status` argument of the LayerNorm family): bit 1 is OR-ed in when a row's variance is not a finite
+// The engine's status word (optional `status` argument of the LayerNorm family): ZH_STATUS_NONFINITE is OR-ed in when a row's variance is not a finite
 // number — an inf or a NaN reached the residual stream.  That is how an fp16 split pair leaving its range shows: |activation| >= 65504
 // stores hi = inf, lo = -inf / NaN, the next product is a NaN, and every path of the model (residual adds, attention over an image's
 // tokens) leads into a LayerNorm.  One compare per row here, nothing in the GEMM / attention epilogues; the host reads the word at its
 // next synchronisation and raises (no fallback).
-#define ZH_STATUS_NONFINITE 2
 
 // y = (x - mean) * rstd, in place in registers. nv = D/4 float4 per row.  Returns false when the variance is inf / NaN.
 __device__ __forceinline__ bool ln_normalize(LnRow& r, int nv, int lane, int D, float eps) {

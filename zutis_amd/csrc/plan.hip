@@ -1,7 +1,6 @@
 // Native launch-plan executor: replays a recorded sequence of C-ABI calls (include/zutis_hip.h) in one C loop, optionally
 // two plans round-robin on two streams.  The per-op dispatch is generated from the header (plan_gen.inc).
 #include "common.h"
-#include "../../include/zutis_hip.h"
 #include <string.h>
 
 struct ZhCmd { int op; int pad; unsigned long long a[32]; };

@@ -20,10 +20,9 @@
 // inside its stride are never written.  Every index is derived from checked sizes; every loop is bounded by them.
 #include "common.h"
 
-#define PNG_SEG 16384                            // ZH_PNG_SEGMENT_BYTES of include/zutis_hip.h
 #define PNG_THREADS 256
-#define PNG_PER_LANE (PNG_SEG / PNG_THREADS)     // 64: one bit of a 64-bit head mask per byte
-#define PNG_SEG_BOUND ((9 * PNG_SEG + 13 + 7) / 8 + 4)      // png_device.segment_bound(PNG_SEG) = 18438
+#define PNG_PER_LANE (ZH_PNG_SEGMENT_BYTES / PNG_THREADS)     // 64: one bit of a 64-bit head mask per byte
+#define PNG_SEG_BOUND ((9 * ZH_PNG_SEGMENT_BYTES + 13 + 7) / 8 + 4)      // png_device.segment_bound(ZH_PNG_SEGMENT_BYTES) = 18438
 #define PNG_SLOT ((PNG_SEG_BOUND + 15) / 16 * 16)           // a segment's slot in the workspace: 18448 bytes
 #define PNG_OUT_WORDS (PNG_SLOT / 4)
 #define PNG_META 4                               // int32 per slot: bytes, s1, s2, 0
@@ -52,9 +51,9 @@ __device__ __forceinline__ PngImage png_image(const long long* img_off, const in
   if (im.off < 0 || im.off + (rowb - 1) * im.h > (long long)image_bytes) return im;
   im.rowb = (int)rowb;
   im.n = (int)n;
-  im.nseg = (int)((n + PNG_SEG - 1) / PNG_SEG);
-  const int rest = im.n % PNG_SEG;
-  im.bound = 2 + (long long)(im.n / PNG_SEG) * PNG_SEG_BOUND + (rest ? png_segment_bound(rest) : 0) + 6;
+  im.nseg = (int)((n + ZH_PNG_SEGMENT_BYTES - 1) / ZH_PNG_SEGMENT_BYTES);
+  const int rest = im.n % ZH_PNG_SEGMENT_BYTES;
+  im.bound = 2 + (long long)(im.n / ZH_PNG_SEGMENT_BYTES) * PNG_SEG_BOUND + (rest ? png_segment_bound(rest) : 0) + 6;
   if (im.nseg > max_segments || im.bound > 0x7fffffffLL) return im;
   const long long oo = out_off[b];
   if (oo < 0 || oo + im.bound > (long long)out_bytes) return im;
@@ -133,14 +132,14 @@ __device__ __forceinline__ unsigned png_lane_tokens(const unsigned char* s_d, un
 __global__ __launch_bounds__(PNG_THREADS) void png_segments_kernel(const unsigned char* images, long image_bytes, const long long* img_off,
                                                                    const int* hw, int c, int max_segments, const long long* out_off,
                                                                    long out_bytes, int* meta, unsigned char* slots) {
-  __shared__ unsigned char s_d[PNG_SEG + PNG_THREADS * 4];
+  __shared__ unsigned char s_d[ZH_PNG_SEGMENT_BYTES + PNG_THREADS * 4];
   __shared__ unsigned s_out[PNG_OUT_WORDS];
   __shared__ int s_a[PNG_THREADS];
   __shared__ int s_b[PNG_THREADS];
   const int b = blockIdx.y, seg = blockIdx.x, tid = threadIdx.x;
   const PngImage im = png_image(img_off, hw, out_off, b, c, image_bytes, out_bytes, max_segments);
   if (!im.ok || seg >= im.nseg) return;                                      // block-uniform, in front of every barrier
-  const int g0 = seg * PNG_SEG, len = min(PNG_SEG, im.n - g0);
+  const int g0 = seg * ZH_PNG_SEGMENT_BYTES, len = min(ZH_PNG_SEGMENT_BYTES, im.n - g0);
   const unsigned char* img = images + im.off;
 
   for (int w = tid; w < PNG_OUT_WORDS; w += PNG_THREADS) s_out[w] = 0u;
@@ -247,7 +246,7 @@ __global__ __launch_bounds__(PNG_THREADS) void png_gather_kernel(long image_byte
     if (j < seg) front += (unsigned)mt[j * PNG_META];
     if (last) {
       const unsigned long long e1 = (unsigned)mt[j * PNG_META + 1], e2 = (unsigned)mt[j * PNG_META + 2];
-      const long long end = min((long long)(j + 1) * PNG_SEG, (long long)im.n);
+      const long long end = min((long long)(j + 1) * ZH_PNG_SEGMENT_BYTES, (long long)im.n);
       a += e1;                                                               // < 65521 each, at most 2^31 / 16384 segments
       bb = (bb + e2 + e1 * (unsigned long long)((im.n - end) % PNG_ADLER)) % PNG_ADLER;
     }

@@ -19,7 +19,7 @@
 // gets n_runs = -1 and is left to the host.
 #include "common.h"
 
-#define ZH_POLYGON_LDS_CROSSINGS 4096   // include/zutis_hip.h: 16 KB keys + 8 KB coverage + 16 KB boundaries, 3 workgroups a CU
+// ZH_POLYGON_LDS_CROSSINGS = 4096: 16 KB keys + 8 KB coverage + 16 KB boundaries, 3 workgroups a CU
 #define PG_THREADS 256
 #define PG_WAVES (PG_THREADS / 64)
 #define PG_MAX_STEPS (1 << 22)          // points of one polygon's walk (zutis_amd/polygons.py MAX_STEPS)

@@ -92,9 +92,9 @@ extern "C" int zh_resize_crop_normalize_u8(const unsigned char* packed, long pac
   ZH_CHECK_ARG(B > 0 && B <= 65535 && n_px > 0 && n_px <= 16384 && packed_bytes > 0,
                "zh_resize_crop_normalize_u8: bad sizes (B=%d n_px=%d packed_bytes=%ld)", B, n_px, packed_bytes);
   ZH_CHECK_ARG(((uintptr_t)packed & 15) == 0, "zh_resize_crop_normalize_u8: packed must be 16-byte aligned");
-  ZH_CHECK_ARG(kmax >= 5 && kmax <= RCN_KMAX, "zh_resize_crop_normalize_u8: kmax %d outside [5, %d] (taps per output pixel: resize such an image on the host)",
-               kmax, RCN_KMAX);
-  rcn_launch<RCN_BICUBIC>(packed, packed_bytes, desc, B, n_px, n_px, kmax, lut, out, 0, stream);
+  ZH_CHECK_ARG(kmax >= 5 && kmax <= ZH_RCN_KMAX, "zh_resize_crop_normalize_u8: kmax %d outside [5, %d] (taps per output pixel: resize such an image on the host)",
+               kmax, ZH_RCN_KMAX);
+  rcn_launch<ZH_FILTER_BICUBIC>(packed, packed_bytes, desc, B, n_px, n_px, kmax, lut, out, 0, stream);
   ZH_CHECK_LAUNCH("zh_resize_crop_normalize_u8");
   return ZH_OK;
 }
@@ -106,12 +106,12 @@ extern "C" int zh_resize_normalize_u8(const unsigned char* packed, long packed_b
   ZH_CHECK_ARG(B > 0 && B <= 65535 && out_h > 0 && out_h <= 16384 && out_w > 0 && out_w <= 16384 && packed_bytes > 0,
                "zh_resize_normalize_u8: bad sizes (B=%d out_h=%d out_w=%d packed_bytes=%ld)", B, out_h, out_w, packed_bytes);
   ZH_CHECK_ARG(((uintptr_t)packed & 15) == 0, "zh_resize_normalize_u8: packed must be 16-byte aligned");
-  ZH_CHECK_ARG(filter == RCN_BILINEAR || filter == RCN_BICUBIC, "zh_resize_normalize_u8: filter %d is neither ZH_FILTER_BILINEAR nor ZH_FILTER_BICUBIC", filter);
-  const int kmin = filter == RCN_BILINEAR ? 3 : 5;
-  ZH_CHECK_ARG(kmax >= kmin && kmax <= RCN_KMAX, "zh_resize_normalize_u8: kmax %d outside [%d, %d] (taps per output pixel: resize such an image on the host)",
-               kmax, kmin, RCN_KMAX);
-  if (filter == RCN_BILINEAR) rcn_launch<RCN_BILINEAR>(packed, packed_bytes, desc, B, out_h, out_w, kmax, lut, out, 1, stream);
-  else rcn_launch<RCN_BICUBIC>(packed, packed_bytes, desc, B, out_h, out_w, kmax, lut, out, 1, stream);
+  ZH_CHECK_ARG(filter == ZH_FILTER_BILINEAR || filter == ZH_FILTER_BICUBIC, "zh_resize_normalize_u8: filter %d is neither ZH_FILTER_BILINEAR nor ZH_FILTER_BICUBIC", filter);
+  const int kmin = filter == ZH_FILTER_BILINEAR ? 3 : 5;
+  ZH_CHECK_ARG(kmax >= kmin && kmax <= ZH_RCN_KMAX, "zh_resize_normalize_u8: kmax %d outside [%d, %d] (taps per output pixel: resize such an image on the host)",
+               kmax, kmin, ZH_RCN_KMAX);
+  if (filter == ZH_FILTER_BILINEAR) rcn_launch<ZH_FILTER_BILINEAR>(packed, packed_bytes, desc, B, out_h, out_w, kmax, lut, out, 1, stream);
+  else rcn_launch<ZH_FILTER_BICUBIC>(packed, packed_bytes, desc, B, out_h, out_w, kmax, lut, out, 1, stream);
   ZH_CHECK_LAUNCH("zh_resize_normalize_u8");
   return ZH_OK;
 }

@@ -3,17 +3,14 @@
 #pragma once
 #include "common.h"
 
-#define RCN_KMAX 152    // include/zutis_hip.h ZH_RCN_KMAX: 96 * 152 * 4 + 768 bytes of LDS < 64 KiB
+// taps per output pixel are capped at ZH_RCN_KMAX: 96 * 152 * 4 + 768 bytes of LDS < 64 KiB; FILTER is ZH_FILTER_BILINEAR / ZH_FILTER_BICUBIC
 #define RCN_PRECISION_BITS 22
-
-#define RCN_BILINEAR 2  // include/zutis_hip.h ZH_FILTER_BILINEAR / ZH_FILTER_BICUBIC
-#define RCN_BICUBIC 3
 
 // Pillow's filter functions (Resample.c: bilinear_filter, bicubic_filter) and their supports
 template <int FILTER>
 __device__ __forceinline__ double rcn_filter(double x) {
   if (x < 0.0) x = -x;
-  if (FILTER == RCN_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
+  if (FILTER == ZH_FILTER_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
   const double a = -0.5;
   if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
   if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
@@ -24,7 +21,7 @@ template <int FILTER>
 __host__ __device__ __forceinline__ int rcn_ksize(int in_size, int out_size) {
   double fs = (double)in_size / (double)out_size;
   if (fs < 1.0) fs = 1.0;
-  return (int)ceil((FILTER == RCN_BILINEAR ? 1.0 : 2.0) * fs) * 2 + 1;
+  return (int)ceil((FILTER == ZH_FILTER_BILINEAR ? 1.0 : 2.0) * fs) * 2 + 1;
 }
 
 // precompute_coeffs + normalize_coeffs_8bpc for ONE output index xx: taps K[0 .. count) (stride `stride` ints), first source index xmin
@@ -32,7 +29,7 @@ template <int FILTER>
 __device__ void rcn_coeffs(int in_size, int out_size, int xx, int* K, int stride, int& xmin_out, int& count_out) {
   const double scale = (double)in_size / (double)out_size;
   const double fs = scale < 1.0 ? 1.0 : scale;
-  const double support = (FILTER == RCN_BILINEAR ? 1.0 : 2.0) * fs, ss = 1.0 / fs;
+  const double support = (FILTER == ZH_FILTER_BILINEAR ? 1.0 : 2.0) * fs, ss = 1.0 / fs;
   const double center = (xx + 0.5) * scale;
   int xmin = (int)(center - support + 0.5);
   if (xmin < 0) xmin = 0;

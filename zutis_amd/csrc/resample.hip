@@ -284,8 +284,6 @@ struct UaStore {                        // zh_upsample_argmax: the int64 label m
     if (valid) labels[pix] = label;
   }
 };
-#define ZH_GT_U8 0
-#define ZH_GT_RG16 1
 // zh_upsample_argmax_score: RunningScore._fast_hist (utils/running_score.py:11-16) on the label while it is in a register.
 // hist[n * gt + label] += 1 for gt < n.  Equal keys are merged inside the wave before memory is touched: the first pending lane's
 // key is broadcast, a ballot counts the lanes that hold it, that lane adds the count with ONE 64-bit atomic, and the loop goes on

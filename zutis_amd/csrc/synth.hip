@@ -73,7 +73,7 @@ __device__ __forceinline__ bool sy_desc_ok(const int* d, long packed_bytes, int 
   const int w = d[SD_W], h = d[SD_H], nw = d[SD_NW], nh = d[SD_NH];
   bool ok = w > 0 && h > 0 && nw > 0 && nh > 0 && d[SD_PAD_L] >= 0 && d[SD_PAD_T] >= 0 && d[SD_CROP_L] >= 0 && d[SD_CROP_T] >= 0;
   ok = ok && (long)(unsigned)d[SD_IMG] * 16 + 3l * w * h <= packed_bytes && (long)(unsigned)d[SD_MASK] * 16 + (long)w * h <= packed_bytes;
-  ok = ok && rcn_ksize<RCN_BILINEAR>(w, nw) <= kmax && rcn_ksize<RCN_BILINEAR>(h, nh) <= kmax;
+  ok = ok && rcn_ksize<ZH_FILTER_BILINEAR>(w, nw) <= kmax && rcn_ksize<ZH_FILTER_BILINEAR>(h, nh) <= kmax;
   return ok;
 }
 
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(SY_TX * SY_WAVES) void synth_fill_sums_kernel(const
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sx = tx * SY_TX + lane;
   int px[SY_RY][3];
-  rcn_tile_u8<RCN_BILINEAR>(packed + (size_t)(unsigned)d[SD_IMG] * 16, d[SD_W], d[SD_H], nw, nh, sx, ty * SY_TY, SY_TY, kmax, sy_lds, px);
+  rcn_tile_u8<ZH_FILTER_BILINEAR>(packed + (size_t)(unsigned)d[SD_IMG] * 16, d[SD_W], d[SD_H], nw, nh, sx, ty * SY_TY, SY_TY, kmax, sy_lds, px);
   u64_t s[3] = {0, 0, 0};
   if (sx < nw) {
 #pragma unroll
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(SY_TX * SY_WAVES) void synth_geometry_kernel(const 
   const int sx = ox < C ? d[SD_CROP_L] + x - d[SD_PAD_L] : -1;
   const int sy_base = d[SD_CROP_T] + ty * SY_TY - d[SD_PAD_T];
   int px[SY_RY][3];
-  rcn_tile_u8<RCN_BILINEAR>(packed + (size_t)(unsigned)d[SD_IMG] * 16, w, h, nw, nh, sx, sy_base, SY_TY, kmax, sy_lds, px);
+  rcn_tile_u8<ZH_FILTER_BILINEAR>(packed + (size_t)(unsigned)d[SD_IMG] * 16, w, h, nw, nh, sx, sy_base, SY_TY, kmax, sy_lds, px);
 
   // the fill: np.array(image).mean(axis=(0, 1)).astype(np.uint8).  NumPy sums the bytes in float64 (exact: the sum is an integer below
   // 2^53) and divides once, correctly rounded.  If count divides the sum the quotient is exact; otherwise the true quotient lies at least
@@ -425,7 +425,7 @@ extern "C" int zh_synth_geometry_u8(const unsigned char* packed, long packed_byt
   ZH_CHECK_ARG(N > 0 && N <= 65535 && C > 0 && C <= 16384 && packed_bytes > 0, "zh_synth_geometry_u8: bad sizes (N=%d C=%d packed_bytes=%ld)", N, C, packed_bytes);
   ZH_CHECK_ARG(ignore_index > 1 && ignore_index <= 255, "zh_synth_geometry_u8: ignore_index %d outside (1, 255] (the mask travels as a byte)", ignore_index);
   ZH_CHECK_ARG(((uintptr_t)packed & 15) == 0 && ((uintptr_t)work & 7) == 0 && ((uintptr_t)out_rgbm & 3) == 0, "zh_synth_geometry_u8: packed must be 16-byte, work 8-byte, out 4-byte aligned");
-  ZH_CHECK_ARG(kmax >= 3 && kmax <= RCN_KMAX, "zh_synth_geometry_u8: kmax %d outside [3, %d] (taps per output pixel: scale such an image on the host)", kmax, RCN_KMAX);
+  ZH_CHECK_ARG(kmax >= 3 && kmax <= ZH_RCN_KMAX, "zh_synth_geometry_u8: kmax %d outside [3, %d] (taps per output pixel: scale such an image on the host)", kmax, ZH_RCN_KMAX);
   ZH_CHECK_ARG(fill_w >= 0 && fill_h >= 0 && fill_w <= 65536 && fill_h <= 65536, "zh_synth_geometry_u8: bad fill extent %d x %d", fill_w, fill_h);
   if (fill_w > 0 && fill_h > 0) {
     const int tx = zh_cdiv(fill_w, SY_TX), ty = zh_cdiv(fill_h, SY_TY);

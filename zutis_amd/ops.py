@@ -13,7 +13,8 @@ import torch
 
 from . import _lib
 
-ACT_NONE, ACT_QUICKGELU, ACT_RELU, ACT_SIGMOID, ACT_GELU_ERF = 0, 1, 2, 3, 4
+_ZH = _lib.constants()     # the ZH_* constants of include/zutis_hip.h: the values the kernels were compiled with
+ACT_NONE, ACT_QUICKGELU, ACT_RELU, ACT_SIGMOID, ACT_GELU_ERF = (_ZH["ZH_ACT_" + a] for a in ("NONE", "QUICKGELU", "RELU", "SIGMOID", "GELU_ERF"))
 f16, f32 = torch.float16, torch.float32
 
 
@@ -184,7 +185,7 @@ def gemm_x3(A: Act, W: Act, out, bias=None, residual=None, res_rows: int = 0, ac
         assert bias.dtype == f32 and bias.numel() >= N
     args = (_p(a), lda, strideA, A.plane, _p(w), ldw, strideW, W.plane, _p(o), ldc, strideC, planeC, kind,
             float(A.out_scale * W.out_scale), _p(bias), _p(residual), ldr or 0, strideR, res_rows, *_pos(pos, N),
-            act, M, N, K, batch, int(bool(fixed_k_order)), _stream())
+            act, M, N, K, batch, _ZH["ZH_GEMM_FIXED_K_ORDER"] if fixed_k_order else 0, _stream())
     nbytes = _gemm_bytes(M, N, K, batch, strideA, strideW, 4, 4 if kind == 0 else (4 if kind == 2 else 2), residual is not None)
     if not W.plane:                                  # one-plane weight: 2 bytes per element instead of 4
         nbytes -= N * K * 2.0 * (batch if (strideW or batch == 1) else 1)
@@ -294,7 +295,7 @@ def group_mean_l2norm(x, out, groups, T, E):
     _call("zh_group_mean_l2norm", _p(x), _p(out), groups, T, E, _stream())
 
 
-STATUS_RANGE, STATUS_NONFINITE, STATUS_LABEL = 1, 2, 4     # bits of the status word (zutis_hip.h ZH_STATUS_*)
+STATUS_RANGE, STATUS_NONFINITE, STATUS_LABEL = _ZH["ZH_STATUS_RANGE"], _ZH["ZH_STATUS_NONFINITE"], _ZH["ZH_STATUS_LABEL"]     # bits of the status word
 UNIT_NORM_SCALE = 1024.0                     # f16_scale of the unit-norm producers (2^10): see zutis_hip.h
 
 
@@ -411,7 +412,7 @@ def upsample_argmax(logits_lo, labels, B, n, h, w, H, W):
     _call("zh_upsample_argmax", _p(logits_lo), _p(labels), B, n, h, w, H, W, lin_scale(h, H), lin_scale(w, W), _stream())
 
 
-GT_FORMATS = {"u8": 0, "rg16": 1}       # include/zutis_hip.h ZH_GT_*
+GT_FORMATS = {"u8": _ZH["ZH_GT_U8"], "rg16": _ZH["ZH_GT_RG16"]}
 
 
 def upsample_argmax_score(logits_lo, gt, hist, B, n, h, w, H, W, gt_format: str = "u8", labels=None):
@@ -587,7 +588,7 @@ def mask_rle_fused_kept(masks_u8, kept_index, kept_count, max_runs, out, cursor,
           _p(out), out.numel(), _p(cursor), _p(info), _stream())
 
 
-PAINT_MAX_Q = 1024      # zh_instance_paint: slots per image (its rank table lives in LDS)
+PAINT_MAX_Q = _ZH["ZH_PAINT_MAX_Q"]      # zh_instance_paint: slots per image (its rank table lives in LDS)
 
 
 def instance_paint_workspace_size(B, Q, H, W) -> int:
@@ -643,7 +644,7 @@ def instance_paint(index, score, count, H, W, *, masks=None, bits=None, colours=
 
 
 # ---------------------------------------------------------------------------------------- CLIP image pre-processing
-RCN_KMAX = 152     # include/zutis_hip.h ZH_RCN_KMAX
+RCN_KMAX = _ZH["ZH_RCN_KMAX"]
 
 
 def resize_crop_normalize(packed, desc, n_px: int, lut, out=None, kmax: Optional[int] = None):
@@ -665,7 +666,7 @@ def resize_crop_normalize(packed, desc, n_px: int, lut, out=None, kmax: Optional
     return out
 
 
-FILTERS = {"bilinear": 2, "bicubic": 3}      # include/zutis_hip.h ZH_FILTER_BILINEAR / ZH_FILTER_BICUBIC (= PIL.Image's values)
+FILTERS = {"bilinear": _ZH["ZH_FILTER_BILINEAR"], "bicubic": _ZH["ZH_FILTER_BICUBIC"]}      # (= PIL.Image's values)
 
 
 def resize_normalize(packed, desc, out_h: int, out_w: int, lut, filter: str = "bilinear", out=None, kmax: Optional[int] = None):
@@ -898,7 +899,7 @@ def mask_runs(masks_u8, sel, max_runs=8192):
     return pos, nr, ba
 
 
-POLYGON_LDS_CROSSINGS = 4096     # zh_polygon_lds_crossings(): crossings of one annotation's polygons the kernel sorts in LDS
+POLYGON_LDS_CROSSINGS = _ZH["ZH_POLYGON_LDS_CROSSINGS"]     # crossings of one annotation's polygons the kernel sorts in LDS
 
 
 def polygon_runs(xs, ys, step_pref, vert_off, poly_off, hw, out_off, flags, counts, n_runs):
@@ -931,8 +932,8 @@ def rle_prefix(counts, run_off, hw, run_end, run_fg, area, status):
         _call("zh_rle_prefix", _p(counts), _p(run_off), _p(hw), n, _p(run_end), _p(run_fg), _p(area), _p(status), _stream())
 
 
-OVERLAP_MODES = {"last": 0, "ignore": 1}      # ZH_OVERLAP_LAST / ZH_OVERLAP_IGNORE
-LABEL_TILE_W, LABEL_TILE_H = 32, 8            # ZH_LABEL_TILE_W / ZH_LABEL_TILE_H
+OVERLAP_MODES = {"last": _ZH["ZH_OVERLAP_LAST"], "ignore": _ZH["ZH_OVERLAP_IGNORE"]}
+LABEL_TILE_W, LABEL_TILE_H = _ZH["ZH_LABEL_TILE_W"], _ZH["ZH_LABEL_TILE_H"]
 
 
 def label_tiles(h: int, w: int) -> int:
@@ -969,7 +970,7 @@ def runs_label_maps(run_end, run_off, status, list_off, list_mask, list_label, h
     return out
 
 
-PNG_SEGMENT_BYTES = 16384                     # ZH_PNG_SEGMENT_BYTES
+PNG_SEGMENT_BYTES = _ZH["ZH_PNG_SEGMENT_BYTES"]
 
 
 def png_deflate(images, img_off, hw, c, out, out_off, lengths, max_segments, workspace=None):
@@ -1027,7 +1028,7 @@ def mask_match_grad(proposals, gt_u8, inst_off, pairs, stat_p, stat_pg, stat_g, 
     return out
 
 
-ASSIGN_MAX_DIM = 1024     # zh_linear_assignment_max_dim(): cap on max(instances of an image, queries), from the solver's LDS state
+ASSIGN_MAX_DIM = _ZH["ZH_ASSIGN_MAX_DIM"]     # cap on max(instances of an image, queries), from the solver's LDS state
 
 
 def assignment_pairs_capacity(B, L, Q, n_max, n_tot) -> int:

@@ -22,14 +22,15 @@ No torch at import.
 """
 from __future__ import annotations
 
-import re
 import struct
 import zlib
 from typing import Optional
 
 import numpy as np
 
-SEGMENT_BYTES = 16384        # ZH_PNG_SEGMENT_BYTES of include/zutis_hip.h (tests/test_png_device_cpu.py compares the two)
+from . import _lib
+
+SEGMENT_BYTES = _lib.constants()["ZH_PNG_SEGMENT_BYTES"]
 ENCODERS = ("host", "device")
 MODES = {"L": (1, 0), "P": (1, 3), "RGB": (3, 2)}       # mode -> (channels, PNG colour type)
 
@@ -186,11 +187,6 @@ def check_encoder(name: str, png_encoder) -> str:
     if png_encoder not in ENCODERS:
         raise ValueError(f"{name}: png_encoder {png_encoder!r} is not \"host\" or \"device\"")
     return png_encoder
-
-
-def header_segment_bytes(header_text: str) -> int:
-    """ZH_PNG_SEGMENT_BYTES as the header states it."""
-    return int(re.search(r"^#define\s+ZH_PNG_SEGMENT_BYTES\s+(\d+)", header_text, re.M).group(1))
 
 
 def write_stream(path: str, stream, H: int, W: int, mode: str, palette_bytes: Optional[bytes]):

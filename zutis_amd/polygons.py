@@ -22,10 +22,10 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import rle
+from . import _lib, rle
 
 SCALE = 5                     # rleFrPoly's upsampling
-LDS_CROSSINGS = 4096          # ZH_POLYGON_LDS_CROSSINGS: crossings of one annotation the kernel sorts in LDS
+LDS_CROSSINGS = _lib.constants()["ZH_POLYGON_LDS_CROSSINGS"]          # crossings of one annotation the kernel sorts in LDS
 MAX_COORD = 1 << 24           # scaled coordinates beyond this, and walks of more than MAX_STEPS points, take the host path
 MAX_STEPS = 1 << 22
 CHUNK_ANNOTATIONS = 16384     # annotations per launch of runs_device: at most 16384 * 4097 runs (256 MB) of output capacity
@@ -199,7 +199,6 @@ def runs_device(annotations: Sequence[Tuple], device=None, events=None):
     refuses, are filled from rle.from_polygons and counted: stats = {"annotations", "polygons", "host_fallback"}.  events (a list):
     gets (entry name, start, end) HIP events of each launch."""
     import torch
-    from . import _lib
     if device is None:
         if not torch.cuda.is_available():
             raise _lib.ZutisHipError("polygons.runs_device runs on the GPU (rle.from_polygons is the host form)")
@@ -261,7 +260,6 @@ def runs_resident(annotations: Sequence[Tuple], device=None, events=None):
     compacted to the runs actually written — annotation a's n_runs[a] counts follow those of a - 1, an annotation left to the host
     (n_runs -1, filled from rle.from_polygons in the dict) takes no place — so what stays resident is the runs, not out_off[-1] slots."""
     import torch
-    from . import _lib
     if device is None:
         if not torch.cuda.is_available():
             raise _lib.ZutisHipError("polygons.runs_resident runs on the GPU (rle.from_polygons is the host form)")

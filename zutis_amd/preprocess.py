@@ -38,8 +38,10 @@ import numpy as np
 import torch
 from PIL import Image
 
+from . import _lib
+
 PRECISION_BITS = 32 - 8 - 2     # Pillow's fixed-point coefficients: src/libImaging/Resample.c
-KMAX = 152                      # taps per output pixel the kernel serves (include/zutis_hip.h ZH_RCN_KMAX)
+KMAX = _lib.constants()["ZH_RCN_KMAX"]      # taps per output pixel the kernel serves
 MAX_THREADS = 16                # decoding and writing threads of one call, together
 ALIGN = 16                      # byte alignment of an image inside the packed buffer (descriptors hold offset / 16)
 DESC_INTS = 8                   # offset / 16, w, h, nw, nh, left, top, 0
