@@ -2,7 +2,9 @@
 run / RLE extraction of the kept masks and their picture, all on the device, and the host decode of the ONE buffer that comes back.
 Two device paths give the same results — fused (runs, boxes, areas and strings from ONE launch, zh_mask_rle_fused_kept: masks up to
 1024 columns whose bits + tables fit the LDS) and chain (run extraction, two launches, + string kernel) — and differ only in which
-kernels run (_launch_*) and in how a slot's string, box and area are read out of the buffer (read_*)."""
+kernels run (_launch_*) and in how a slot's string, box and area are read out of the buffer (read_*).  The kernels: csrc/instance.hip
+(statistics, masked mean, classification, IoU counts, NMS) and csrc/mask_rle.hip (run extraction, the string kernel, the fused kernel);
+the string format both paths and the host encoder (csrc/rle_host.hip) write is csrc/rle_codec.h's."""
 import collections
 import functools
 import math

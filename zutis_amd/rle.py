@@ -70,6 +70,15 @@ def encode_py(mask: np.ndarray) -> Dict:
     return {"size": [int(h), int(w)], "counts": _to_string(_counts(mask))}
 
 
+def _host_capacity(n_values: int, chars_per_value: int = 8) -> int:
+    """Bytes of the buffer handed to the host entry points (csrc/rle_host.hip) for a string of n_values run values.  The bound is
+    derived once, in csrc/rle_codec.h ("the character bound"): a value below 2^34 in magnitude takes at most 7 characters, so 8 per
+    value plus 16 holds every mask of fewer than 2^31 pixels; the entry points check the capacity for every value all the same and
+    return -1.  encode() asks for 4 per PIXEL instead: a value is at most the longer of runs k and k - 2 in magnitude, each run is
+    charged for at most two values, and a run of L >= 1 pixels needs no more than 2 L characters for a value up to L."""
+    return chars_per_value * n_values + 16
+
+
 def encode(mask: np.ndarray) -> Dict:
     """mask [H,W] {0,1}/bool -> {"size": [H, W], "counts": bytes} (pycocotools.mask.encode for one mask).
     Uses the C helper zh_rle_encode_host from libzutis_hip.so (host code, no GPU needed)."""
@@ -78,8 +87,7 @@ def encode(mask: np.ndarray) -> Dict:
     assert mask.ndim == 2
     h, w = mask.shape
     m = np.ascontiguousarray(mask, dtype=np.uint8)
-    cap = 8 * (m.size + 2) // 2 + 16
-    cap = min(cap, 6 * (h * w + 2))
+    cap = min(_host_capacity(m.size + 2, 4), 6 * (h * w + 2))
     buf = C.create_string_buffer(cap)
     n = _lib.load().zh_rle_encode_host(m.ctypes.data, h, w, C.addressof(buf), cap)
     if n < 0:
@@ -102,24 +110,15 @@ def decode(rle: Dict) -> np.ndarray:
 
 def decode_np(rle: Dict) -> np.ndarray:
     """decode() in NumPy, for the read-back check of the pseudo-label writers (pseudo_masks.save_rle_json), where the per-character Python
-    loop of decode() was the longest step of the tail: the characters of a value are its 5-bit groups (bit 0x20 = more follow, bit 0x10
-    of the last = sign), values from the fourth on are deltas against the value two places back, i.e. running sums over the odd and over
-    the even places.  decode() stays as the readable restatement it is checked against (tests/test_pseudo_files_cpu.py)."""
+    loop of decode() was the longest step of the tail.  The run lengths are counts_np's (the one NumPy string parser: a string that ends
+    inside a value, or holds a value of more than 12 characters, is its ValueError); only the repeat into pixels happens here.  decode()
+    stays as the readable restatement it is checked against (tests/test_pseudo_files_cpu.py)."""
     h, w = rle["size"]
     s = rle["counts"]
-    c = np.frombuffer(s.encode("ascii") if isinstance(s, str) else bytes(s), np.uint8).astype(np.int64) - 48
+    cnts = counts_np(s if isinstance(s, (bytes, bytearray, str)) else bytes(s))
     flat = np.zeros(h * w, np.uint8)
-    if c.size:
-        ends = np.flatnonzero((c & 0x20) == 0)
-        starts = np.concatenate(([0], ends[:-1] + 1))
-        nchar = ends - starts + 1
-        part = (c & 0x1F) << (5 * (np.arange(c.size) - np.repeat(starts, nchar)))
-        cnts = np.add.reduceat(part, starts)
-        cnts = np.where((c[ends] & 0x10) != 0, cnts | np.left_shift(np.int64(-1), 5 * nchar), cnts)
-        cnts[1::2] = np.cumsum(cnts[1::2])
-        cnts[2::2] = np.cumsum(cnts[2::2])
-        runs = np.repeat((np.arange(cnts.size) & 1).astype(np.uint8), cnts)[:h * w]
-        flat[:runs.size] = runs
+    runs = np.repeat((np.arange(cnts.size) & 1).astype(np.uint8), cnts)[:h * w]
+    flat[:runs.size] = runs
     return flat.reshape((h, w), order="F")
 
 
@@ -140,7 +139,7 @@ def rle_from_transitions(positions: np.ndarray, first_value: int, h: int, w: int
     if first_value:
         counts = np.concatenate(([0], counts))
     counts = np.ascontiguousarray(counts, dtype=np.int64)
-    cap = 8 * counts.size + 16
+    cap = _host_capacity(counts.size)
     buf = C.create_string_buffer(cap)
     n = _lib.load().zh_rle_counts_to_string_host(counts.ctypes.data, counts.size, C.addressof(buf), cap)
     assert n >= 0
@@ -159,7 +158,7 @@ def rles_from_transitions(positions: np.ndarray, nruns: np.ndarray, h: int, w: i
     n = nr.shape[0]
     keep = int(packed_max_runs) if packed_max_runs else pos.shape[1]
     nt = nr[:, 0].tolist()
-    cap = 8 * (sum(min(t, keep) for t in nt) + 3 * n) + 16
+    cap = _host_capacity(sum(min(t, keep) for t in nt) + 3 * n)
     buf = C.create_string_buffer(cap)
     off = np.empty(n + 1, dtype=np.int64)
     total = _lib.load(raw=True).zh_rle_from_transitions_host(pos.ctypes.data, keep, 1 if packed_max_runs else 0, nr.ctypes.data, n, h * w,
@@ -173,8 +172,10 @@ def rles_from_transitions(positions: np.ndarray, nruns: np.ndarray, h: int, w: i
 
 def counts_np(counts) -> np.ndarray:
     """The uncompressed run lengths (int64, the run of zeros first) behind any of the three forms a COCO RLE's "counts" takes: the
-    compressed string as bytes or as str (what json writes and reads back), or the list of an uncompressed RLE.  The string form is
-    decode_np's arithmetic without the pixels: COCO mask AP (zutis_amd/coco_eval.py) works on the runs themselves."""
+    compressed string as bytes or as str (what json writes and reads back), or the list of an uncompressed RLE.  The string parser, in
+    NumPy: the characters of a value are its 5-bit groups (bit 0x20 = more follow, bit 0x10 of the last = sign), values from the fourth on
+    are deltas against the value two places back, i.e. running sums over the odd and over the even places.  COCO mask AP
+    (zutis_amd/coco_eval.py) works on the runs themselves; decode_np repeats them into pixels."""
     if not isinstance(counts, (bytes, bytearray, str)):
         return np.asarray(counts, dtype=np.int64).reshape(-1)
     c = np.frombuffer(counts.encode("ascii") if isinstance(counts, str) else bytes(counts), np.uint8).astype(np.int64) - 48
