@@ -9,8 +9,9 @@ score noise; fp16 cases) or zero (x3 cases: see below).  All tensors are returne
 float64 softmax(Q K^T scale) V of tests/test_layout_guard_attention_gpu.py::attn_case is the reference of exactly these operands, and the
 helper only chooses inputs.
 
-Constants are read from zutis_amd/csrc/attention.hip by regex (kernel_constants()): the lazy-max threshold L = ZH_ATTN_LAZY_LOG2 and the
-key-tile heights (KT for the fp16 kernels, the X3 arm of KTT for the split-pair ones); the cases follow them if they change.
+Constants: the key-tile heights are the header's (ZH_ATTN_KEY_TILE_F16 / _X3 of include/zutis_hip.h, which static_asserts hold the kernels to);
+the lazy-max threshold L = ZH_ATTN_LAZY_LOG2 is private to zutis_amd/csrc/attention.hip and read from it by regex (kernel_constants()).  The
+cases follow them if they change.
 
 Split-pair (x3) cases keep |scaled score| <= 64 log2 units for every key that carries weight: the raw fp32 score is then below 512
 (c >= 0.147 at head_dim 96), its ulp 2^-15, i.e. at most 2^-16 * c * ln 2 = 1.9e-6 of relative error in a probability, and the float32
@@ -28,6 +29,8 @@ from dataclasses import dataclass, field
 
 import torch
 
+from zutis_amd import _lib
+
 f16, f32, f64 = torch.float16, torch.float32, torch.float64
 LOG2E = 1.4426950408889634
 FAMILIES = ("staircase", "row_schedule", "peak_tail", "one_hot", "uniform", "common_offset", "causal", "key_split")
@@ -38,13 +41,11 @@ _SRC = pathlib.Path(__file__).resolve().parents[1] / "zutis_amd" / "csrc" / "att
 
 
 def kernel_constants():
-    """(L, kt_fp16, kt_x3) from attention.hip."""
-    text = _SRC.read_text()
-    lazy = re.search(r"#define\s+ZH_ATTN_LAZY_LOG2\s+([0-9]+(?:\.[0-9]*)?)f?\b", text)
-    kt = re.search(r"#define\s+KT\s+(\d+)\b", text)
-    ktt = re.search(r"\bKTT\s*=\s*X3\s*\?\s*(\d+)\s*:\s*KT\b", text)
-    assert lazy and kt and ktt, "attention.hip no longer defines ZH_ATTN_LAZY_LOG2 / KT / KTT = X3 ? n : KT"
-    return float(lazy.group(1)), int(kt.group(1)), int(ktt.group(1))
+    """(L, kt_fp16, kt_x3): L from attention.hip, the tile heights from the header."""
+    lazy = re.search(r"#define\s+ZH_ATTN_LAZY_LOG2\s+([0-9]+(?:\.[0-9]*)?)f?\b", _SRC.read_text())
+    assert lazy, "attention.hip no longer defines ZH_ATTN_LAZY_LOG2"
+    zh = _lib.constants()
+    return float(lazy.group(1)), zh["ZH_ATTN_KEY_TILE_F16"], zh["ZH_ATTN_KEY_TILE_X3"]
 
 
 LAZY, KT_F16, KT_X3 = kernel_constants()

@@ -10,7 +10,7 @@ In the packed layout images follow each other without a gap (the engine's stride
 next image's finite data, so the read-overrun screen rests on the slice layout; the packed cases check values and the output guards.
 O always has ldo > D and a padded batch stride; split-pair O has a padded plane offset.
 
-Key-tile height kt (attention.hip: `#define KT 64`, `KTT = X3 ? 32 : KT`): 64 keys for the fp16 kernels, 32 for the split-pair ones; a
+Key-tile height kt (include/zutis_hip.h: ZH_ATTN_KEY_TILE_F16, ZH_ATTN_KEY_TILE_X3): 64 keys for the fp16 kernels, 32 for the split-pair ones; a
 workgroup covers 128 queries (4 waves of 32), so Tq = 1 .. 127 leaves waves that only help with the tile loads, and their O rows — past
 Tq — must stay untouched.  K / V rows past Tk are never part of the logical input: a key tile that reads them must not let them reach
 the result (P = 0 times NaN is NaN), which the finite check shows.

@@ -4,7 +4,6 @@ product's shapes are pinned.  The pinned numbers were computed with the inline e
 finding, not a number to adjust."""
 import ast
 import os
-import re
 
 import pytest
 
@@ -25,12 +24,21 @@ def test_module_imports_only_math_and_os():
 
 
 def test_constants_match_the_kernels():
-    from _attention_case import kernel_constants
-    _, kt_f16, kt_x3 = kernel_constants()
-    assert (SR.key_tile(False), SR.key_tile(True)) == (kt_f16, kt_x3)
-    src = open(os.path.join(ROOT, "zutis_amd", "csrc", "attention.hip")).read()
-    m = re.search(r"\bnqb\s*=\s*zh_cdiv\(Tq,\s*(\d+)\)", src)
-    assert m and int(m.group(1)) == SR.QUERY_BLOCK == 128
+    """shape_rules' literals == the header's constants (which static_asserts hold the kernels to) == what the library's launch plan reports."""
+    from zutis_amd import _lib, build
+    from tests._attention_plan_case import ask
+    zh = _lib.constants()
+    assert SR.QUERY_BLOCK == zh["ZH_ATTN_QUERY_BLOCK"] == 128
+    assert (SR.key_tile(False), SR.key_tile(True)) == (zh["ZH_ATTN_KEY_TILE_F16"], zh["ZH_ATTN_KEY_TILE_X3"])
+    build.build(verbose=False)
+    lib = _lib.load(raw=True)
+    for x3 in (False, True):
+        assert ask(lib, Tq=1, Tk=1, x3=x3).key_tile == SR.key_tile(x3)
+        # the query block as the plan shows it: one block up to QUERY_BLOCK queries, two from the next on
+        assert [ask(lib, Tq=SR.QUERY_BLOCK + d, Tk=1, x3=x3).nqb for d in (-1, 0, 1)] == [1, 1, 2]
+        # ... and the key tile: a split of 2 fits from key_tile + 1 keys on, in chunks of one tile
+        assert ask(lib, Tq=1, Tk=SR.key_tile(x3), x3=x3, ksplit=2) is None
+        assert ask(lib, Tq=1, Tk=SR.key_tile(x3) + 1, x3=x3, ksplit=2).kchunk == SR.key_tile(x3)
     assert SR.CUS == 256
     assert SR.key_tiles(5505, True) == 173 and SR.key_tiles(5505, False) == 87 and SR.key_tiles(64, False) == 1
 

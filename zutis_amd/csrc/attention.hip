@@ -15,7 +15,7 @@
 // [key][d] in LDS and is consumed column-wise through ds_read_b64_tr_b16.
 // LDS strides: K rows dh+8 halves (conflict-free ds_read_b128), V rows 96 halves (4 consecutive rows cover
 // disjoint 16-dword bank ranges for the transposed read).
-#include "common.h"
+#include "attention_dispatch.h"
 #include <type_traits>
 
 struct AttnArgs {
@@ -36,7 +36,7 @@ struct AttnArgs {
 typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef __attribute__((address_space(3))) fp16x4* lds_fp16x4_ptr;
 
-#define KT 64
+#define KT 64         // keys per tile of the fp16 kernels: the ABI's ZH_ATTN_KEY_TILE_F16 (asserted where KTT is formed)
 #define VS 96
 
 // VALU diet of the key-tile loop (round 3; every vector instruction costs the SIMD's issue port 4 cycles, v_exp_f32 8, an MFMA 8 of
@@ -77,6 +77,7 @@ __device__ __forceinline__ float zh_xor32_sum(float x) {
 template <int DH, int NWAVE, int X3, int PIPE>
 __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_f16_kernel(AttnArgs p) {
   static_assert(!PIPE || X3, "the pipelined loop exists for the split-pair kernels");
+  static_assert(32 * NWAVE == ZH_ATTN_QUERY_BLOCK, "a workgroup's queries (32 per wave) are the ABI's query block");
   constexpr int NT = 64 * NWAVE;
   constexpr int KS = DH + 8;          // K row stride (halves)
   constexpr int NKS = DH / 16;        // k-steps of QK^T
@@ -86,6 +87,7 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
   // accumulators the registers, so at 64 keys only one workgroup fits a CU (one wave per SIMD, nothing to overlap with);
   // 32-key tiles halve both and two or three workgroups fit
   constexpr int KTT = X3 ? 32 : KT;        // (fp16 dh = 96 with 32 keys: cross-attention 44 -> 63 us — 256 workgroups, occupancy is not its limit)
+  static_assert(KTT == attn_key_tile(X3), "the tile heights are the ABI's ZH_ATTN_KEY_TILE_F16 / ZH_ATTN_KEY_TILE_X3 (the launch plan chunks keys by them)");
   constexpr int NU = KTT / 32;        // 32-key slot tiles per key tile
   constexpr int NLD = (KTT * CPR + NT - 1) / NT;              // chunk passes per thread (the last may be partial: dh = 96 x 32 keys)
   constexpr bool LDFULL = (KTT * CPR) % NT == 0;
@@ -494,75 +496,42 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* part_o, 
   zh_store_h4(O + (long)img * sO + (long)q * ldo + col, planeO, acc * inv);
 }
 
+// The six instantiations, keyed as attn_plan (attention_dispatch.h) names them; workgroups of NW waves = ZH_ATTN_QUERY_BLOCK queries
+constexpr int NW = ZH_ATTN_QUERY_BLOCK / 32;
+struct AttnKernelRow { int head_dim, variant; void (*kernel)(AttnArgs); };
+static constexpr AttnKernelRow ATTN_KERNELS[] = {
+  {64, ATTN_X3_PIPE, attn_f16_kernel<64, NW, 1, 1>}, {64, ATTN_X3, attn_f16_kernel<64, NW, 1, 0>}, {64, ATTN_F16, attn_f16_kernel<64, NW, 0, 0>},
+  {96, ATTN_X3_PIPE, attn_f16_kernel<96, NW, 1, 1>}, {96, ATTN_X3, attn_f16_kernel<96, NW, 1, 0>}, {96, ATTN_F16, attn_f16_kernel<96, NW, 0, 0>},
+};
+static_assert(attn_table_complete(ATTN_KERNELS), "a (head_dim, variant) that attn_plan can return has no kernel");
+
 static int attention_launch(const void* Q, long ldq, long strideQ, const void* K, long ldk, long strideK,
                             const void* V, long ldv, long strideV, void* O, long ldo, long strideO,
                             int batch, int heads, int Tq, int Tk, int head_dim, float scale, int causal,
                             long planeQ, long planeK, long planeV, long planeO, hipStream_t stream, int ksplit = 1, void* workspace = nullptr,
                             size_t workspace_bytes = 0) {
-  ZH_CHECK_ARG(Q && K && V && O, "zh_attention_f16: null operand");
-  ZH_CHECK_ARG(batch > 0 && heads > 0 && Tq > 0 && Tk > 0, "zh_attention_f16: bad shape");
-  ZH_CHECK_ARG(head_dim == 64 || head_dim == 96, "zh_attention_f16: head_dim %d not in {64, 96}", head_dim);
-  ZH_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0 && strideQ % 8 == 0 && strideK % 8 == 0 &&
-                   strideV % 8 == 0 && strideO % 4 == 0 && planeQ % 8 == 0 && planeK % 8 == 0 && planeV % 8 == 0 && planeO % 4 == 0,
-               "zh_attention_f16: row/batch/plane strides must keep 16-byte (Q,K,V) / 8-byte (O) alignment");
-  ZH_CHECK_ARG(((uintptr_t)Q & 15) == 0 && ((uintptr_t)K & 15) == 0 && ((uintptr_t)V & 15) == 0 && ((uintptr_t)O & 7) == 0,
-               "zh_attention_f16: misaligned pointer");
-  ZH_CHECK_ARG(heads < 65536 && batch < 65536, "zh_attention_f16: heads/batch exceed grid limits");
-  // K / V rows are addressed as (per-image, per-head base) + 32-bit byte offset
-  ZH_CHECK_ARG((long)Tk * ldk * 2 < (1L << 32) && (long)Tk * ldv * 2 < (1L << 32), "zh_attention_f16: Tk * ldk (ldv) exceeds 2^31 elements");
-  ZH_CHECK_ARG((planeQ != 0) == (planeK != 0) && (planeQ != 0) == (planeV != 0),
-               "zh_attention_f16: the split-pair mode needs the lo planes of Q, K and V (all three or none)");
+  const AttnProblem q = attn_problem(Q, ldq, strideQ, K, ldk, strideK, V, ldv, strideV, O, ldo, strideO, batch, heads, Tq, Tk, head_dim, causal,
+                                     planeQ, planeK, planeV, planeO, ksplit, workspace, workspace_bytes);
+  AttnPlan plan;
+  const int rc = attn_plan(q, &plan);
+  if (rc != ZH_OK) return rc;
   AttnArgs p;
   p.Q = (const half_t*)Q; p.ldq = ldq; p.sQ = strideQ;
   p.K = (const half_t*)K; p.ldk = ldk; p.sK = strideK;
   p.V = (const half_t*)V; p.ldv = ldv; p.sV = strideV;
   p.O = (half_t*)O; p.ldo = ldo; p.sO = strideO;
-  p.Tq = Tq; p.Tk = Tk; p.H = heads;
+  p.Tq = Tq; p.Tk = Tk; p.H = heads; p.nqb = plan.nqb; p.groups = plan.groups;
   p.scale_log2 = scale * 1.4426950408889634f;
   p.causal = causal;
   p.planeQ = planeQ; p.planeK = planeK; p.planeV = planeV; p.planeO = planeO;
-  // 128-query (4-wave) blocks: each K/V tile is shared four ways.  A 64-query (2-wave) variant was measured slower on
-  // every shape of the model (encoder 301 vs 423 TF, cross-attention 230 vs 397 TF) and was dropped.
-  const bool x3 = planeQ != 0;
-  p.nqb = zh_cdiv(Tq, 128);
-  p.groups = heads * batch;
-  p.ksplit = 1; p.kchunk = 0; p.part_o = p.part_m = p.part_l = nullptr;
-  if (ksplit > 1) {
-    ZH_CHECK_ARG(!causal && ksplit <= 64, "zh_attention_f16_splitk: ksplit %d not in 1..64 (and not for the causal form)", ksplit);
-    const int ktt = x3 ? 32 : 64;
-    p.ksplit = ksplit;
-    p.kchunk = zh_cdiv(zh_cdiv(Tk, ktt), ksplit) * ktt;
-    ZH_CHECK_ARG((long)(ksplit - 1) * p.kchunk < Tk, "zh_attention_f16_splitk: ksplit %d leaves an empty key chunk for Tk = %d", ksplit, Tk);
-    const size_t no = (size_t)ksplit * batch * Tq * heads * head_dim, nm = (size_t)ksplit * batch * heads * Tq;
-    ZH_CHECK_ARG(workspace && workspace_bytes >= (no + 2 * nm) * 4 && ((uintptr_t)workspace & 15) == 0,
-                 "zh_attention_f16_splitk: workspace too small or misaligned (%zu < %zu)", workspace_bytes, (no + 2 * nm) * 4);
-    p.part_o = (float*)workspace; p.part_m = p.part_o + no; p.part_l = p.part_m + nm;
-  }
-  const long items = (long)p.groups * p.nqb * p.ksplit;
-  ZH_CHECK_ARG(items < (1L << 31) - 8, "zh_attention_f16: grid too large");
-  const long nblk = (long)zh_cdiv(items, 8) * 8;        // decoded XCD-aware in the kernel: XCD x takes items [x * nblk / 8, (x + 1) * nblk / 8)
-  ZH_CHECK_ARG(nblk < (1L << 31), "zh_attention_f16: grid too large");
-  dim3 grid((unsigned)nblk);
-  // Split-pair kernels: the software-pipelined loop (K.Q^T of tile t+1 issued in among the softmax of tile t; bit-identical
-  // results) needs 193 registers at dh = 64, two waves per SIMD instead of three.  Same box, us, plain -> pipelined: decoder
-  // cross-attention (dh = 96, two waves either way) 120.4 -> 103.7; SelfMask T = 5505 (264 workgroups) 240.1 -> 223.2; 518-px
-  // encoder (864) 102.3 -> 98.7; 336-px encoder (1536) 76.5 -> 77.4; ViT-L/14 (20480) 1249 -> 1306.  So dh = 96 always takes it,
-  // dh = 64 when the grid needs no more rounds of the chip at two workgroups per CU than at three.
-  const bool pipe = x3 && (head_dim == 96 || zh_cdiv(nblk, 512L) <= zh_cdiv(nblk, 768L));
-  if (head_dim == 64) {
-    if (x3 && pipe) hipLaunchKernelGGL((attn_f16_kernel<64, 4, 1, 1>), grid, dim3(256), 0, stream, p);
-    else if (x3) hipLaunchKernelGGL((attn_f16_kernel<64, 4, 1, 0>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((attn_f16_kernel<64, 4, 0, 0>), grid, dim3(256), 0, stream, p);
-  } else {
-    if (x3 && pipe) hipLaunchKernelGGL((attn_f16_kernel<96, 4, 1, 1>), grid, dim3(256), 0, stream, p);
-    else if (x3) hipLaunchKernelGGL((attn_f16_kernel<96, 4, 1, 0>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((attn_f16_kernel<96, 4, 0, 0>), grid, dim3(256), 0, stream, p);
-  }
+  p.ksplit = plan.ksplit; p.kchunk = plan.kchunk;
+  char* const ws = plan.ksplit > 1 ? (char*)workspace : nullptr;
+  p.part_o = (float*)(ws + plan.off_o); p.part_m = (float*)(ws + plan.off_m); p.part_l = (float*)(ws + plan.off_l);
+  hipLaunchKernelGGL(ATTN_KERNELS[attn_table_row(ATTN_KERNELS, head_dim, plan.variant)].kernel, dim3(plan.grid), dim3(64 * NW), 0, stream, p);
   ZH_CHECK_LAUNCH("zh_attention_f16");
-  if (p.ksplit > 1) {
-    const long n4 = (long)batch * Tq * heads * head_dim / 4;
-    hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)zh_cdiv(n4, 256)), dim3(256), 0, stream, p.part_o, p.part_m, p.part_l, p.O, ldo, strideO,
-                       planeO, p.ksplit, batch, heads, Tq, head_dim);
+  if (plan.ksplit > 1) {
+    hipLaunchKernelGGL(attn_combine_kernel, dim3(plan.combine_grid), dim3(256), 0, stream, p.part_o, p.part_m, p.part_l, p.O, ldo, strideO,
+                       planeO, plan.ksplit, batch, heads, Tq, head_dim);
     ZH_CHECK_LAUNCH("zh_attention_f16_splitk (combine)");
   }
   return ZH_OK;
@@ -572,7 +541,7 @@ static int attention_launch(const void* Q, long ldq, long strideQ, const void* K
 // decoder's cross-attention: 100 queries, 1764 keys -> 256 workgroups, ONE per CU, each streaming 1.35 MB of K / V with a single
 // tile of prefetch: bytes in flight bound the kernel at half the HBM rate).  Two workgroups per CU double the bytes in flight.
 extern "C" size_t zh_attention_splitk_workspace_size(int batch, int heads, int Tq, int head_dim, int ksplit) {
-  return ((size_t)ksplit * batch * Tq * heads * head_dim + 2 * (size_t)ksplit * batch * heads * Tq) * 4;
+  return attn_splitk_workspace(batch, heads, Tq, head_dim, ksplit);
 }
 extern "C" int zh_attention_f16_splitk(const void* Q, long ldq, long strideQ, const void* K, long ldk, long strideK,
                                        const void* V, long ldv, long strideV, void* O, long ldo, long strideO,

@@ -58,6 +58,24 @@ extern "C" int zh_dev_gemm_plan(int mode, int M, int N, int K, int batch, long l
   return ZH_OK;
 }
 
+// What the attention launcher decides for a call, asked without launching: the plan function attention_launch calls (attention.hip).
+#include "attention_dispatch.h"
+extern "C" int zh_dev_attention_plan(const void* Q, long ldq, long strideQ, const void* K, long ldk, long strideK,
+                                     const void* V, long ldv, long strideV, const void* O, long ldo, long strideO,
+                                     int batch, int heads, int Tq, int Tk, int head_dim, int causal,
+                                     long planeQ, long planeK, long planeV, long planeO, int ksplit, const void* workspace, size_t workspace_bytes,
+                                     int* plan) {
+  ZH_CHECK_ARG(plan, "zh_dev_attention_plan: null plan");
+  AttnPlan a;
+  const int rc = attn_plan(attn_problem(Q, ldq, strideQ, K, ldk, strideK, V, ldv, strideV, O, ldo, strideO, batch, heads, Tq, Tk, head_dim, causal,
+                                        planeQ, planeK, planeV, planeO, ksplit, workspace, workspace_bytes), &a);
+  if (rc != ZH_OK) return rc;
+  ZH_CHECK_ARG(a.workspace_bytes <= 0x7FFFFFFF, "zh_dev_attention_plan: a workspace of %zu bytes does not fit the int row", a.workspace_bytes);
+  plan[0] = a.variant; plan[1] = a.key_tile; plan[2] = a.nqb; plan[3] = (int)a.items; plan[4] = (int)a.grid; plan[5] = a.pipe;
+  plan[6] = a.ksplit; plan[7] = a.kchunk; plan[8] = (int)a.workspace_bytes; plan[9] = (int)a.combine_grid;
+  return ZH_OK;
+}
+
 // persistent big-tile GEMMs (gemm_kernel.h PERS): workgroups per launch = the CUs of the CURRENT device rounded down to a multiple
 // of 8 (a persistent workgroup takes a CU's whole LDS; the tile walk deals ids modulo 8 to the XCDs) — 256 on an MI355X in SPX mode,
 // fewer in a partitioned mode.  Resolved at the first launch (no HIP call at load time: build() loads the library without a GPU) and

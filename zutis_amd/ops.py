@@ -256,22 +256,20 @@ def attention(Q, K, V, O, *, batch, heads, Tq, Tk, head_dim, ldq, ldk, ldv, ldo,
     if causal:
         if Tq != Tk:
             raise _lib.ZutisHipError("causal attention needs Tq == Tk")
-        args = (_p(Q), ldq, strideQ, _p(K), ldk, strideK, _p(V), ldv, strideV, _p(O), ldo, strideO,
-                batch, heads, Tq, head_dim, float(scale), pq, pk, pv, po, _stream())
-        _launch(name, 2.0 * batch * heads * Tq * Tk * head_dim, "zh_attention_causal_f16", args)
-        return O
+        ksplit = 1                               # the causal kernel has no split form
     if ksplit > 1:
         need = attention_splitk_workspace_size(batch, heads, Tq, head_dim, ksplit)
         if workspace is None or _nbytes(workspace) < need:
             raise _lib.ZutisHipError(f"attention(ksplit={ksplit}): workspace of {need} bytes required")
-        args = (_p(Q), ldq, strideQ, _p(K), ldk, strideK, _p(V), ldv, strideV, _p(O), ldo, strideO,
-                batch, heads, Tq, Tk, head_dim, float(scale), pq, pk, pv, po, ksplit, _p(workspace),
-                _nbytes(workspace), _stream())
-        _launch(name, 4.0 * batch * heads * Tq * Tk * head_dim, "zh_attention_f16_splitk", args)
-        return O
-    args = (_p(Q), ldq, strideQ, _p(K), ldk, strideK, _p(V), ldv, strideV, _p(O), ldo, strideO,
-            batch, heads, Tq, Tk, head_dim, float(scale), pq, pk, pv, po, _stream())
-    _launch(name, 4.0 * batch * heads * Tq * Tk * head_dim, "zh_attention_f16", args)
+    head = (_p(Q), ldq, strideQ, _p(K), ldk, strideK, _p(V), ldv, strideV, _p(O), ldo, strideO, batch, heads, Tq)
+    tail = (head_dim, float(scale), pq, pk, pv, po)
+    if causal:
+        entry, args = "zh_attention_causal_f16", head + tail
+    elif ksplit > 1:
+        entry, args = "zh_attention_f16_splitk", head + (Tk,) + tail + (ksplit, _p(workspace), _nbytes(workspace))
+    else:
+        entry, args = "zh_attention_f16", head + (Tk,) + tail
+    _launch(name, (2.0 if causal else 4.0) * batch * heads * Tq * Tk * head_dim, entry, args + (_stream(),))
     return O
 
 

@@ -7,12 +7,12 @@ decisions on a CPU and tests/test_launch_trace_gpu.py pins what the engines laun
 import os
 
 CUS = 256               # compute units of the MI355X
-QUERY_BLOCK = 128       # queries per attention workgroup (attention.hip)
+QUERY_BLOCK = 128       # queries per attention workgroup (ZH_ATTN_QUERY_BLOCK of include/zutis_hip.h)
 FEW_ITEMS = 128         # (image, head, query block) workgroups up to which a self-attention splits its keys
 
 
 def key_tile(x3: bool) -> int:
-    """Keys per tile of the attention kernels: 32 for split pairs, 64 for fp16."""
+    """Keys per tile of the attention kernels: 32 for split pairs, 64 for fp16 (ZH_ATTN_KEY_TILE_X3 / _F16)."""
     return 32 if x3 else 64
 
 
@@ -28,6 +28,15 @@ def fit_key_split(S: int, ktiles: int) -> int:
     return max(1, S)
 
 
+def pipelined_loop(n: int, head_dim: int, x3: bool) -> bool:
+    """Whether `n` attention workgroups (items x key split) run the software-pipelined split-pair loop: the launcher's rule
+    (csrc/attention_dispatch.h attn_pipelined; tests/test_attention_plan_cpu.py holds this copy to it).  dh = 96 always, dh = 64 when
+    the grid needs no more rounds of the chip at two workgroups per CU than at three.  The launcher asks it of n rounded up to 8,
+    which gives the same rounds: 2 * CUS and 3 * CUS are multiples of 8.  It reads the grid, and so the BATCH; the results are
+    bit-identical either way."""
+    return x3 and (head_dim == 96 or -(-n // (2 * CUS)) <= -(-n // (3 * CUS)))
+
+
 def long_sequence_key_split(items: int, ktiles: int, head_dim: int, x3: bool, out_elems: int) -> int:
     """Key split (1 .. 8) of a LONG self-attention (SelfMask's DINO ViT-S/8 at 512x683: T = 5505, networks/selfmask/vision_transformer.py:110-133)
     from a round-quantisation model of zh_attention_f16's grid: `items` = (image, head, 128-query block) workgroups, each walking `ktiles`
@@ -38,9 +47,7 @@ def long_sequence_key_split(items: int, ktiles: int, head_dim: int, x3: bool, ou
     rounds x (chunk + fixed) + a last partial round at the (faster) per-tile time of its occupancy + the merge traffic.
     `items` counts every image, so the split DEPENDS ON THE BATCH: 5 / 4 / 2 / 1 for 1 / 2 / 4 / 8 images at T = 5505 (split pairs)."""
     def wpc_of(n):
-        if x3 and (head_dim == 96 or -(-n // (2 * CUS)) <= -(-n // (3 * CUS))):
-            return 2                                       # the launcher's rule for the software-pipelined loop (attention.hip)
-        return 3 if head_dim == 64 else 2
+        return 2 if pipelined_loop(n, head_dim, x3) or head_dim == 96 else 3
     tile_time = {1: 0.78, 2: 0.89, 3: 1.0}                 # per-tile time of a workgroup with 1 / 2 / 3 resident per CU (stamps, profiles/NOTES.md)
     tile_us = 1.85 if x3 else 0.95                         # one key tile of a workgroup at full occupancy
     best, best_cost = 1, None
