@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 241 /* 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 242 /* 242: the attention entries take head_dim 128 (a behaviour change: a stale build would refuse the ViT-L decoder); 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -124,7 +124,7 @@ int zh_gemm_f16x3(const void* A, long lda, long strideA, long planeA, const void
                   int act, int M, int N, int K, int batch, int flags, zh_stream_t stream);
 
 /* Flash attention: O = softmax(scale * Q K^T) V per (image, head); Q [Tq, heads*dh] rows with stride ldq, etc.
- * f16 in/out, fp32 softmax/accumulate; head_dim in {64, 96}.
+ * f16 in/out, fp32 softmax/accumulate; head_dim in {64, 96, 128} (128: the ViT-L towers' decoder, 8 heads over width 1024).
  * planeQ / planeK / planeV != 0 (all or none): Q, K, V are split pairs; scores are Kh.Qh + Kl.Qh + Kh.Ql and the
  * probabilities are split in registers, O += Vh.Ph + Vl.Ph + Vh.Pl (fp32-class).  planeO != 0: O is written as a split pair.
  * Replaces nn.MultiheadAttention core at clip_arch.py:314-316, transformer.py:272-286,
@@ -159,7 +159,7 @@ int zh_attention_causal_f16(const void* Q, long ldq, long strideQ, const void* K
  * three entries above ask.  The arguments are theirs without scale and stream: causal = 1 for zh_attention_causal_f16 (Tq = Tk = T),
  * ksplit <= 1 with workspace NULL / 0 for the unsplit entries.  Pointers are VALUES (null and alignment checks only): nothing is
  * dereferenced, it runs without a GPU.  Returns what the entry's argument checks return, zh_last_error() included.
- * plan (HOST int[10]) = {variant (0 fp16, 1 split pair, 2 split pair with the software-pipelined loop), key tile, query blocks per
+ * plan (HOST int[10]) = {variant (0 fp16, 1 split pair, 2 split pair with the software-pipelined loop: head_dim 64 / 96 only), key tile, query blocks per
  * (image, head), workgroups with work (batch * heads * query blocks * ksplit), grid (those rounded up to 8), pipelined loop (0 / 1),
  * ksplit as launched (1 = none), keys per chunk (0 = no split), workspace bytes needed (0 = no split), grid of the merge launch (0 = none)}. */
 int zh_dev_attention_plan(const void* Q, long ldq, long strideQ, const void* K, long ldk, long strideK,

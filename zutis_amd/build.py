@@ -24,7 +24,9 @@ MAX_SCRATCH = int(os.environ.get("ZH_BUILD_MAX_SCRATCH", "0"))    # bytes per la
 # remarks; a key that matches no kernel of its source is a build error (a renamed template would otherwise drop its guard)
 MIN_OCCUPANCY = {"attention.hip": {"attn_f16_kernelILi64ELi4ELi1ELi0EE": 3, "attn_f16_kernelILi64ELi4ELi0ELi0EE": 3,
                                    "attn_f16_kernelILi64ELi4ELi1ELi1EE": 2, "attn_f16_kernelILi96ELi4ELi1ELi0EE": 2,
-                                   "attn_f16_kernelILi96ELi4ELi0ELi0EE": 2, "attn_f16_kernelILi96ELi4ELi1ELi1EE": 2},
+                                   "attn_f16_kernelILi96ELi4ELi0ELi0EE": 2, "attn_f16_kernelILi96ELi4ELi1ELi1EE": 2,
+                                   # dh = 128 (ViT-L decoder): fp16 and the plain split-pair loop, two workgroups of 75 776 LDS bytes per CU
+                                   "attn_f16_kernelILi128ELi4ELi0ELi0EE": 2, "attn_f16_kernelILi128ELi4ELi1ELi0EE": 2},
                  # the byte epilogue (zh_upsample_argmax_bytes) must not cost the arg-max kernels the occupancy of their int64 form (UaStore)
                  "resample.hip": {"upsample_argmax_pk_kernelI7UaBytes": 3, "upsample_argmax_lds_kernelI7UaBytes": 6,
                                   "upsample_argmax_kernelI7UaBytes": 8}}

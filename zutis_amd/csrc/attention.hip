@@ -1,7 +1,8 @@
-// Flash attention forward, fp16 operands / fp32 softmax+accumulate, head_dim 64 or 96 (gfx950).
+// Flash attention forward, fp16 operands / fp32 softmax+accumulate, head_dim 64, 96 or 128 (gfx950).
 //
 // Replaces nn.MultiheadAttention's softmax(QK^T/sqrt(dh))V at networks/clip_arch.py:314-316 (12 heads,
-// dh=64, T=1+hw), networks/transformer.py:272-286 (decoder self/cross attention, 8 heads, dh=96) and
+// dh=64, T=1+hw), networks/transformer.py:272-286 (decoder self/cross attention, 8 heads: dh=96 over the ViT-B towers' width 768,
+// dh=128 over the ViT-L towers' 1024) and
 // networks/selfmask/vision_transformer.py:110-133 (dh=64, T up to ~6k; the reference materialises
 // [B,6,T,T]).  Nothing T x T ever reaches HBM here.
 //
@@ -13,8 +14,11 @@
 // key-index bits 2 and 3, which makes the S^T accumulator registers 8s..8s+7 exactly the natural-k fp16
 // B-operand of k-step s of the PV product (no lane movement, no LDS round trip for P).  V stays row-major
 // [key][d] in LDS and is consumed column-wise through ds_read_b64_tr_b16.
-// LDS strides: K rows dh+8 halves (conflict-free ds_read_b128), V rows 96 halves (4 consecutive rows cover
-// disjoint 16-dword bank ranges for the transposed read).
+// LDS strides: K rows dh+8 halves (conflict-free ds_read_b128), V rows 96 halves, 160 at dh = 128 (4 consecutive rows cover
+// disjoint 16-dword bank ranges for the transposed read: the stride in dwords is 16 or 48 mod 64 — 96 halves = 48, 160 halves =
+// 80 = 16; dh + 8 = 136 halves = 68 = 4 would put the four rows on overlapping banks.  Derived from the bank layout, not measured).
+// dh = 128 has the fp16 kernel and the plain split-pair loop, both at two workgroups per CU (75 776 bytes of LDS each); the pipelined
+// split-pair loop does not fit its registers there (attention_dispatch.h ATTN_PIPE_HEAD_DIMS) and is not instantiated.
 #include "attention_dispatch.h"
 #include <type_traits>
 
@@ -37,7 +41,6 @@ typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef __attribute__((address_space(3))) fp16x4* lds_fp16x4_ptr;
 
 #define KT 64         // keys per tile of the fp16 kernels: the ABI's ZH_ATTN_KEY_TILE_F16 (asserted where KTT is formed)
-#define VS 96
 
 // VALU diet of the key-tile loop (round 3; every vector instruction costs the SIMD's issue port 4 cycles, v_exp_f32 8, an MFMA 8 of
 // its 32 — MI355X_MICROARCH.md "vector-instruction ISSUE cost" — and the softmax of a split-pair tile was ~145 of them beside 24
@@ -79,7 +82,10 @@ __global__ __launch_bounds__(64 * NWAVE, X3 ? 2 : (DH == 64 ? 3 : 2)) void attn_
   static_assert(!PIPE || X3, "the pipelined loop exists for the split-pair kernels");
   static_assert(32 * NWAVE == ZH_ATTN_QUERY_BLOCK, "a workgroup's queries (32 per wave) are the ABI's query block");
   constexpr int NT = 64 * NWAVE;
+  static_assert(!PIPE || attn_has_pipelined(DH), "no pipelined loop at this head dim (it spills): attn_plan never asks for one");
   constexpr int KS = DH + 8;          // K row stride (halves)
+  constexpr int VS = DH == 128 ? 160 : 96;   // V row stride (halves): >= DH, and 16 or 48 dwords mod 64 (header comment)
+  static_assert(VS >= DH && (VS / 2) % 32 == 16, "V rows: four consecutive rows on disjoint 16-dword bank ranges");
   constexpr int NKS = DH / 16;        // k-steps of QK^T
   constexpr int NDT = DH / 32;        // 32-row d tiles of O^T
   constexpr int CPR = DH / 8;         // 16-byte chunks per K/V row
@@ -496,14 +502,16 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* part_o, 
   zh_store_h4(O + (long)img * sO + (long)q * ldo + col, planeO, acc * inv);
 }
 
-// The six instantiations, keyed as attn_plan (attention_dispatch.h) names them; workgroups of NW waves = ZH_ATTN_QUERY_BLOCK queries
+// The eight instantiations, keyed as attn_plan (attention_dispatch.h) names them; workgroups of NW waves = ZH_ATTN_QUERY_BLOCK queries
 constexpr int NW = ZH_ATTN_QUERY_BLOCK / 32;
 struct AttnKernelRow { int head_dim, variant; void (*kernel)(AttnArgs); };
 static constexpr AttnKernelRow ATTN_KERNELS[] = {
   {64, ATTN_X3_PIPE, attn_f16_kernel<64, NW, 1, 1>}, {64, ATTN_X3, attn_f16_kernel<64, NW, 1, 0>}, {64, ATTN_F16, attn_f16_kernel<64, NW, 0, 0>},
   {96, ATTN_X3_PIPE, attn_f16_kernel<96, NW, 1, 1>}, {96, ATTN_X3, attn_f16_kernel<96, NW, 1, 0>}, {96, ATTN_F16, attn_f16_kernel<96, NW, 0, 0>},
+  {128, ATTN_X3, attn_f16_kernel<128, NW, 1, 0>}, {128, ATTN_F16, attn_f16_kernel<128, NW, 0, 0>},
 };
 static_assert(attn_table_complete(ATTN_KERNELS), "a (head_dim, variant) that attn_plan can return has no kernel");
+static_assert(attn_table_no_unplanned_pipe(ATTN_KERNELS), "a pipelined kernel is listed for a head dim attn_plan never pipelines");
 
 static int attention_launch(const void* Q, long ldq, long strideQ, const void* K, long ldk, long strideK,
                             const void* V, long ldv, long strideV, void* O, long ldo, long strideO,

@@ -11,7 +11,19 @@
 constexpr int ATTN_CUS = 256;
 
 enum { ATTN_F16 = 0, ATTN_X3 = 1, ATTN_X3_PIPE = 2, ATTN_VARIANTS = 3 };     // kernel variant = the template pair (X3, PIPE): (0, 0), (1, 0), (1, 1)
-constexpr int ATTN_HEAD_DIMS[] = {64, 96};
+constexpr int ATTN_HEAD_DIMS[] = {64, 96, 128};
+// head dims whose split-pair kernel has a software-pipelined form.  Not 128: K(t+2) in flight beside the S accumulators of two tiles
+// and four O tiles is 256 VGPRs plus 120 bytes of scratch per lane, and a spill in this file is a build error.
+constexpr int ATTN_PIPE_HEAD_DIMS[] = {64, 96};
+
+constexpr bool attn_head_dim_ok(int head_dim) {
+  for (int dh : ATTN_HEAD_DIMS) if (dh == head_dim) return true;
+  return false;
+}
+constexpr bool attn_has_pipelined(int head_dim) {
+  for (int dh : ATTN_PIPE_HEAD_DIMS) if (dh == head_dim) return true;
+  return false;
+}
 
 // What the choice depends on.  Q / K / V / O / workspace are pointer VALUES (null and alignment checks only); ksplit <= 1: no key split.
 struct AttnProblem {
@@ -53,18 +65,27 @@ static inline size_t attn_splitk_workspace(int batch, int heads, int Tq, int hea
 // Split-pair kernels: the software-pipelined loop (K.Q^T of tile t+1 issued in among the softmax of tile t; bit-identical
 // results) needs 193 registers at dh = 64, two waves per SIMD instead of three.  Same box, us, plain -> pipelined: decoder
 // cross-attention (dh = 96, two waves either way) 120.4 -> 103.7; SelfMask T = 5505 (264 workgroups) 240.1 -> 223.2; 518-px
-// encoder (864) 102.3 -> 98.7; 336-px encoder (1536) 76.5 -> 77.4; ViT-L/14 (20480) 1249 -> 1306.  So dh = 96 always takes it,
-// dh = 64 when the grid needs no more rounds of the chip at two workgroups per CU than at three.
+// encoder (864) 102.3 -> 98.7; 336-px encoder (1536) 76.5 -> 77.4; ViT-L/14 (20480) 1249 -> 1306.  So, of the head dims that have the
+// pipelined kernel (ATTN_PIPE_HEAD_DIMS): dh = 96 always takes it (its plain loop has no occupancy to lose), dh = 64 when the grid
+// needs no more rounds of the chip at two workgroups per CU than at three.  dh = 128 has none and runs the plain loop.
 // `grid` is the launch grid, items rounded up to 8; shape_rules.pipelined_loop asks the same of the items themselves, and the two
 // agree because 2 * ATTN_CUS and 3 * ATTN_CUS are multiples of 8: ceil(n / m) = ceil(8 ceil(n / 8) / m) whenever 8 divides m.
+constexpr bool attn_pipelined_always(int head_dim) { return head_dim == 96; }
 static inline bool attn_pipelined(bool x3, int head_dim, long grid) {
-  return x3 && (head_dim == 96 || zh_cdiv(grid, 2L * ATTN_CUS) <= zh_cdiv(grid, 3L * ATTN_CUS));
+  return x3 && attn_has_pipelined(head_dim) &&
+         (attn_pipelined_always(head_dim) || zh_cdiv(grid, 2L * ATTN_CUS) <= zh_cdiv(grid, 3L * ATTN_CUS));
+}
+// Whether attn_plan can return `variant` for `head_dim` (over all grids): the pairs the launcher's table must hold.
+constexpr bool attn_plan_returns(int head_dim, int variant) {
+  return attn_head_dim_ok(head_dim) &&
+         (variant == ATTN_F16 || (variant == ATTN_X3 && !(attn_has_pipelined(head_dim) && attn_pipelined_always(head_dim))) ||
+          (variant == ATTN_X3_PIPE && attn_has_pipelined(head_dim)));
 }
 
 static inline int attn_plan(const AttnProblem& q, AttnPlan* plan) {
   ZH_CHECK_ARG(q.Q && q.K && q.V && q.O, "zh_attention_f16: null operand");
   ZH_CHECK_ARG(q.batch > 0 && q.heads > 0 && q.Tq > 0 && q.Tk > 0, "zh_attention_f16: bad shape");
-  ZH_CHECK_ARG(q.head_dim == 64 || q.head_dim == 96, "zh_attention_f16: head_dim %d not in {64, 96}", q.head_dim);
+  ZH_CHECK_ARG(attn_head_dim_ok(q.head_dim), "zh_attention_f16: head_dim %d not in {64, 96, 128}", q.head_dim);
   ZH_CHECK_ARG(q.ldq % 8 == 0 && q.ldk % 8 == 0 && q.ldv % 8 == 0 && q.ldo % 4 == 0 && q.strideQ % 8 == 0 && q.strideK % 8 == 0 &&
                    q.strideV % 8 == 0 && q.strideO % 4 == 0 && q.planeQ % 8 == 0 && q.planeK % 8 == 0 && q.planeV % 8 == 0 && q.planeO % 4 == 0,
                "zh_attention_f16: row/batch/plane strides must keep 16-byte (Q,K,V) / 8-byte (O) alignment");
@@ -114,10 +135,17 @@ constexpr int attn_table_row(const Row (&rows)[R], int head_dim, int variant) {
   for (size_t i = 0; i < R; ++i) if (rows[i].head_dim == head_dim && rows[i].variant == variant) return (int)i;
   return -1;
 }
-// every (head_dim, variant) attn_plan can return has a row (and so has (96, ATTN_X3), which attn_pipelined never leaves to the plan)
+// every (head_dim, variant) attn_plan can return has a row.  Only those are required: dh = 128 has no pipelined kernel to list, and the
+// (96, ATTN_X3) row the table keeps is the plain loop the pipelined one is measured against, which the plan never picks.
 template <class Row, size_t R>
 constexpr bool attn_table_complete(const Row (&rows)[R]) {
   for (int dh : ATTN_HEAD_DIMS)
-    for (int v = 0; v < ATTN_VARIANTS; ++v) if (attn_table_row(rows, dh, v) < 0) return false;
+    for (int v = 0; v < ATTN_VARIANTS; ++v) if (attn_plan_returns(dh, v) && attn_table_row(rows, dh, v) < 0) return false;
+  return true;
+}
+// and no row is one the plan could pick by mistake: a head dim without a pipelined kernel lists none
+template <class Row, size_t R>
+constexpr bool attn_table_no_unplanned_pipe(const Row (&rows)[R]) {
+  for (size_t i = 0; i < R; ++i) if (rows[i].variant == ATTN_X3_PIPE && !attn_has_pipelined(rows[i].head_dim)) return false;
   return true;
 }

@@ -82,6 +82,13 @@ TINY = ZutisConfig(width=192, layers=2, patch=16, grid=4, embed_dim=64, n_querie
 # config of the build_model / convert_weights fixture (tests/golden/a4_build_model.npz): dh = 64 in encoder and decoder
 A4_TINY = ZutisConfig(width=128, layers=2, patch=16, grid=4, embed_dim=64, n_queries=5, dec_layers=2, dec_heads=2)
 
+# The ViT-L/14 towers (clip_arch.py:590-627: width 1024, 24 layers, embed 768; pos-embed grid 16 at 224 px, 24 at 336 px): 16 encoder
+# heads at dh = 64, and the decoder's 8 heads at dh = 128.  The full depths serve tools/zutis_vitl_bench.py; the shallow geometry
+# (2 + 2 layers at the full width: 53 M parameters) is what tests/test_zutis_vitl_gpu.py draws.
+VIT_L14 = ZutisConfig(width=1024, layers=24, patch=14, grid=16, embed_dim=768)
+VIT_L14_336 = ZutisConfig(width=1024, layers=24, patch=14, grid=24, embed_dim=768)
+VIT_L14_SHALLOW = ZutisConfig(width=1024, layers=2, patch=14, grid=16, embed_dim=768, n_queries=100, dec_layers=2, dec_heads=8)
+
 
 def zutis_param_shapes(cfg: ZutisConfig) -> "OrderedDict[str, Tuple[Tuple[int, ...], float, float]]":
     """name -> (shape, std, mean) in reference state_dict order-insensitive form."""

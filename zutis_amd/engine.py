@@ -11,7 +11,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, compose, instances, ops
+from . import _lib, compose, instances, ops, shape_rules
 from ._lib import ZutisHipError
 from .engine_base import (ALL_SITES, DECODER_SITES, ENCODER_SITES, HEAD_SITES, PRECISIONS, P_shape0, _EngineBase, _rup, f16, f32,
                           resolve_precision)
@@ -34,8 +34,8 @@ class ZutisEngine(_EngineBase):
         self.Q = params["query_embed"].shape[0]
         self.E = params["encoder.proj"].shape[1]
         self.grid = int(math.isqrt(params["encoder.positional_embedding"].shape[0] - 1))
-        if self.dec_dh not in (64, 96):
-            raise ZutisHipError(f"decoder head_dim {self.dec_dh} unsupported by zh_attention_f16 (64 or 96)")
+        if self.dec_dh not in shape_rules.HEAD_DIMS:
+            raise ZutisHipError(f"decoder head_dim {self.dec_dh} unsupported by zh_attention_f16 ({', '.join(map(str, shape_rules.HEAD_DIMS))})")
         self._init_base(precision)
 
     # ------------------------------------------------------------------ packing

@@ -9,6 +9,11 @@ import os
 CUS = 256               # compute units of the MI355X
 QUERY_BLOCK = 128       # queries per attention workgroup (ZH_ATTN_QUERY_BLOCK of include/zutis_hip.h)
 FEW_ITEMS = 128         # (image, head, query block) workgroups up to which a self-attention splits its keys
+# Head dims zh_attention_f16 has kernels for (csrc/attention_dispatch.h ATTN_HEAD_DIMS): 64 the encoders, 96 / 128 the ZUTIS decoder's 8
+# heads over the ViT-B / ViT-L towers' width.  The engines' checks and error texts read this tuple; tests/test_attention_dh128_cpu.py
+# holds it to what the library's plan accepts.
+HEAD_DIMS = (64, 96, 128)
+PIPELINED_HEAD_DIMS = (64, 96)     # ... of which these have the software-pipelined split-pair loop (ATTN_PIPE_HEAD_DIMS)
 
 
 def key_tile(x3: bool) -> int:
@@ -31,23 +36,23 @@ def fit_key_split(S: int, ktiles: int) -> int:
 def pipelined_loop(n: int, head_dim: int, x3: bool) -> bool:
     """Whether `n` attention workgroups (items x key split) run the software-pipelined split-pair loop: the launcher's rule
     (csrc/attention_dispatch.h attn_pipelined; tests/test_attention_plan_cpu.py holds this copy to it).  dh = 96 always, dh = 64 when
-    the grid needs no more rounds of the chip at two workgroups per CU than at three.  The launcher asks it of n rounded up to 8,
+    the grid needs no more rounds of the chip at two workgroups per CU than at three, dh = 128 never (it has no pipelined kernel).  The launcher asks it of n rounded up to 8,
     which gives the same rounds: 2 * CUS and 3 * CUS are multiples of 8.  It reads the grid, and so the BATCH; the results are
     bit-identical either way."""
-    return x3 and (head_dim == 96 or -(-n // (2 * CUS)) <= -(-n // (3 * CUS)))
+    return x3 and head_dim in PIPELINED_HEAD_DIMS and (head_dim == 96 or -(-n // (2 * CUS)) <= -(-n // (3 * CUS)))
 
 
 def long_sequence_key_split(items: int, ktiles: int, head_dim: int, x3: bool, out_elems: int) -> int:
     """Key split (1 .. 8) of a LONG self-attention (SelfMask's DINO ViT-S/8 at 512x683: T = 5505, networks/selfmask/vision_transformer.py:110-133)
     from a round-quantisation model of zh_attention_f16's grid: `items` = (image, head, 128-query block) workgroups, each walking `ktiles`
-    key tiles.  A CU holds 3 such workgroups (2 for the pipelined split-pair loop and at dh = 96), so 4 images x 6 heads x 44 blocks = 1056
+    key tiles.  A CU holds 3 such workgroups (2 for the pipelined split-pair loop and at dh = 96 / 128), so 4 images x 6 heads x 44 blocks = 1056
     workgroups are 1.375 rounds of the chip's 768 slots — two rounds, the second a third full — and ONE image (264 workgroups) leaves
     every SIMD a single wave with nothing to overlap its softmax with.  Splitting the keys over S workgroups per item (partials merged by
     attn_combine_kernel) buys finer rounds for one pass over the fp32 partials.  Cost in key-tile times of a full CU:
     rounds x (chunk + fixed) + a last partial round at the (faster) per-tile time of its occupancy + the merge traffic.
     `items` counts every image, so the split DEPENDS ON THE BATCH: 5 / 4 / 2 / 1 for 1 / 2 / 4 / 8 images at T = 5505 (split pairs)."""
     def wpc_of(n):
-        return 2 if pipelined_loop(n, head_dim, x3) or head_dim == 96 else 3
+        return 2 if pipelined_loop(n, head_dim, x3) or head_dim in (96, 128) else 3
     tile_time = {1: 0.78, 2: 0.89, 3: 1.0}                 # per-tile time of a workgroup with 1 / 2 / 3 resident per CU (stamps, profiles/NOTES.md)
     tile_us = 1.85 if x3 else 0.95                         # one key tile of a workgroup at full occupancy
     best, best_cost = 1, None
