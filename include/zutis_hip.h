@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 242 /* 242: the attention entries take head_dim 128 (a behaviour change: a stale build would refuse the ViT-L decoder); 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 243 /* 243: zh_jpeg_decode / zh_jpeg_decode_host (the device JPEG decoder: baseline files reach the GPU as file bytes, ZH_JPEG_*); 242: the attention entries take head_dim 128 (a behaviour change: a stale build would refuse the ViT-L decoder); 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -650,6 +650,51 @@ int zh_png_deflate(const unsigned char* images, long image_bytes, const long lon
                    const long long* out_off, unsigned char* out, long out_bytes, int* lengths, void* workspace, size_t workspace_bytes,
                    zh_stream_t stream);
 
+/* ---- device JPEG decoder (zutis_amd/jpeg_device.py is the definition; csrc/jpeg.hip and csrc/jpeg_host.hip over csrc/jpeg_codec.h) ---- */
+/* B baseline JPEG files, given as their entropy-coded bytes and parsed headers (jpeg_device.parse / pack), decoded to interleaved RGB
+ * u8 [h, w, 3], byte for byte jpeg_device.decode_np = what Pillow (libjpeg-turbo) gives for Image.open(p).convert("RGB"): Huffman
+ * decoding, islow inverse DCT, fancy chroma upsampling of the cropped planes, 16-bit fixed-point YCbCr -> RGB.
+ * scan u8 [scan_bytes]: the entropy segments of all files (the bytes between the RSTn markers, stuffed bytes still in).
+ * segments int32 [n_segments, ZH_JPEG_SEGMENT_WORDS] = {image, first byte, end byte, first MCU}: one lane decodes one segment, so
+ *   the caller sorts them by length (longest first); a segment holds min(restart interval, MCUs - first MCU) MCUs, all of them
+ *   when the interval is 0.
+ * images int32 [B, ZH_JPEG_IMAGE_WORDS] = {w, h, components (1 | 3), luma sampling h, v ((1,1) | (2,1) | (2,2); chroma is (1,1)),
+ *   MCUs per row, MCU rows, table set, first 8 x 8 block in the workspace, output offset / 16, restart interval in MCUs, 0}.
+ * tables u8 [n_sets, ZH_JPEG_TABLE_SET_BYTES]: four canonical Huffman tables (luma DC, luma AC, chroma DC, chroma AC) of
+ *   ZH_JPEG_HUFF_TABLE_BYTES each — look u16 [256] = (length << 8 | value) of the code that is a prefix of 8 bits (0: longer), maxcode
+ *   int32 [18] by length (-1: none), valoff int32 [18], vals u8 [256] — then quant u16 [2, 64] (luma, chroma) in natural order;
+ *   n_sets <= ZH_JPEG_MAX_TABLE_SETS (they live in LDS), n_segments <= ZH_JPEG_MAX_SEGMENTS.
+ * out u8 [out_bytes]: image b's pixels at 16 * its offset word, the offsets ops.resize_crop_normalize / resize_normalize read.
+ * status int32 [B]: 0, or the OR of ZH_JPEG_STATUS_* — the image's pixels are then not to be used (the caller decodes it on the host).
+ * By construction, whatever the bytes say: every loop is bounded by the geometry (a block takes at most 64 symbols, a segment at most
+ * 64 x its blocks); no byte outside a segment's range is read (a read past the end yields zero bits and, once such bits are used,
+ * sets TRUNCATED) and no coefficient outside the image's block range is written; a descriptor that does not fit (sizes, offsets,
+ * table set, block range, output range) is not read through and nothing of its image is written.
+ * max_image_blocks / max_image_pixels: at least the blocks (MCUs x blocks per MCU) and the pixels of every image — the widths of the
+ * grids of launches B and C; an image beyond them gets DESCRIPTOR.  B <= 65535.
+ * n_blocks: 8 x 8 blocks of the whole batch (below 2^24); workspace >= zh_jpeg_decode_workspace_size bytes, 16-byte aligned: MCU counters int32 [B],
+ * coefficients int16 [n_blocks, 64] in natural order (zeroed here), samples u8 [n_blocks, 64].  Three launches (entropy: one lane per
+ * segment; dequantise + inverse DCT: one lane per block; upsample + colour: one lane per pixel) behind two fills.  B = 0 launches
+ * nothing. */
+#define ZH_JPEG_IMAGE_WORDS 12
+#define ZH_JPEG_SEGMENT_WORDS 4
+#define ZH_JPEG_HUFF_TABLE_BYTES 912
+#define ZH_JPEG_TABLE_SET_BYTES 3904
+#define ZH_JPEG_MAX_TABLE_SETS 16
+#define ZH_JPEG_MAX_SEGMENTS 1048576
+#define ZH_JPEG_STATUS_TRUNCATED 1   /* bits past the end of the segment were used */
+#define ZH_JPEG_STATUS_CODE 2        /* an undefined Huffman code */
+#define ZH_JPEG_STATUS_INDEX 4       /* a coefficient index past 63 */
+#define ZH_JPEG_STATUS_MARKER 8      /* a marker (FF not followed by 00) inside a segment */
+#define ZH_JPEG_STATUS_BITS 16       /* a DC extra-bit count above 11 or an AC count above 10 */
+#define ZH_JPEG_STATUS_SEGMENT 32    /* a segment row outside the scan bytes or the image's MCUs */
+#define ZH_JPEG_STATUS_DESCRIPTOR 64 /* an image row the launch cannot serve */
+#define ZH_JPEG_STATUS_INCOMPLETE 128 /* the segments that decoded do not cover the image's MCUs */
+size_t zh_jpeg_decode_workspace_size(int B, long n_blocks);
+int zh_jpeg_decode(const unsigned char* scan, long scan_bytes, const int* segments, int n_segments, const int* images, int B,
+                   const unsigned char* tables, int n_sets, long n_blocks, long max_image_blocks, long max_image_pixels,
+                   unsigned char* out, long out_bytes, int* status, void* workspace, size_t workspace_bytes, zh_stream_t stream);
+
 /* Native launch plans (zutis_amd/plan.py): replay n recorded calls of the entry points above (op id + 32 argument words
  * each; dispatcher generated from this header) in one C loop; zh_plan_run2 alternates two plans on two streams. */
 int zh_plan_run(const void* cmds, int n, zh_stream_t stream);
@@ -705,6 +750,11 @@ int zh_synth_compose(const unsigned char* rgbm, const unsigned char* rgbm_blurre
 /* HOST helper (no GPU): COCO RLE string of one u8 [H,W] mask = pycocotools.mask.encode(np.asfortranarray(m))["counts"]
  * (zutis.py:290,448; datasets/index_dataset.py:219).  Returns the length, -1 if cap is too small. */
 long zh_rle_encode_host(const unsigned char* mask, int H, int W, char* out, long cap);
+
+/* HOST twin of zh_jpeg_decode (no GPU, HOST pointers, its own scratch): the same codec (csrc/jpeg_codec.h) and the same pixel
+ * arithmetic on the CPU, for the CPU tests and the host sanitizer program (tools/host/jpeg_host_check.cpp).  Arguments as there. */
+int zh_jpeg_decode_host(const unsigned char* scan, long scan_bytes, const int* segments, int n_segments, const int* images, int B,
+                        const unsigned char* tables, int n_sets, long n_blocks, unsigned char* out, long out_bytes, int* status);
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,7 @@ MIN_OCCUPANCY = {"attention.hip": {"attn_f16_kernelILi64ELi4ELi1ELi0EE": 3, "att
                  # the byte epilogue (zh_upsample_argmax_bytes) must not cost the arg-max kernels the occupancy of their int64 form (UaStore)
                  "resample.hip": {"upsample_argmax_pk_kernelI7UaBytes": 3, "upsample_argmax_lds_kernelI7UaBytes": 6,
                                   "upsample_argmax_kernelI7UaBytes": 8}}
-SOURCES = ["capi.hip", "rle_host.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "mask_rle.hip", "instance_paint.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "assign.hip", "cocoeval.hip", "polygon.hip", "label_paint.hip", "png.hip", "synth.hip", "plan.hip"]
+SOURCES = ["capi.hip", "rle_host.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "mask_rle.hip", "instance_paint.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "assign.hip", "cocoeval.hip", "polygon.hip", "label_paint.hip", "png.hip", "jpeg_host.hip", "jpeg.hip", "synth.hip", "plan.hip"]
 
 
 def _hipcc() -> str:

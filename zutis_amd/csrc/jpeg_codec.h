@@ -1,0 +1,289 @@
+// The baseline JPEG decoder (zutis_amd/jpeg_device.py is the definition), written ONCE for the device kernels (jpeg.hip) and the host
+// entry (jpeg_host.hip, which tools/host/jpeg_host_check.cpp runs under the host sanitizers).  Inline functions only.
+//
+//   jpeg_image         an image row of the launch, checked: nothing of an image whose row fails is read or written
+//   jpeg_segment       a segment row, checked against the scan bytes and the image's MCUs
+//   jpeg_step          ONE Huffman symbol of one segment: the state is (MCU, block in MCU, coefficient index k); the table is chosen by
+//                      arithmetic on it (class = block past the luma blocks, AC = k != 0), so lanes at different positions of
+//                      different images run the same instructions.  Every symbol advances k or ends the block, a block takes at most
+//                      64 symbols, so jpeg_segment_steps() bounds the loop whatever the bytes say.
+//   JpegBits           a 64-bit bit buffer over [pos, end) of the scan bytes, refilled four bytes at a time where none of them is FF,
+//                      byte by byte (FF 00 -> FF) otherwise.  Nothing outside [pos, end) is read: past the end the buffer takes zero bits,
+//                      counted in `fake`, and TRUNCATED is set once such a bit is consumed (read-ahead alone sets nothing).
+//   jpeg_idct_block    dequantise + islow inverse DCT of one block (64-bit sums: damaged coefficients cannot overflow)
+//   jpeg_pixel         fancy upsampling of the cropped chroma planes at one pixel + YCbCr -> RGB
+#pragma once
+#include "../../include/zutis_hip.h"
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define JPEG_HD __host__ __device__ inline
+#else
+#define JPEG_HD inline
+#endif
+
+#define JPEG_HUFF_SET_BYTES (4 * ZH_JPEG_HUFF_TABLE_BYTES)      // the part of a table set the entropy stage reads (what lives in LDS)
+#define JPEG_T_MAXCODE 512                                     // byte offsets inside one Huffman table
+#define JPEG_T_VALOFF 584
+#define JPEG_T_VALS 656
+
+struct JpegImage {
+  int w, h, nc, hs, vs, mcux, mcuy, tset, ri, bpm, lum;
+  long block0, nblocks, out;
+  bool ok;
+};
+
+JPEG_HD JpegImage jpeg_image(const int* r, int n_sets, long n_blocks, long out_bytes) {
+  JpegImage im;
+  im.w = r[0]; im.h = r[1]; im.nc = r[2]; im.hs = r[3]; im.vs = r[4]; im.mcux = r[5]; im.mcuy = r[6]; im.tset = r[7];
+  im.block0 = r[8]; im.out = 16L * r[9]; im.ri = r[10];
+  im.bpm = 0; im.lum = 0; im.nblocks = 0;
+  im.ok = false;
+  if (im.w < 1 || im.h < 1 || im.w > 65535 || im.h > 65535) return im;
+  const bool grey = im.nc == 1 && im.hs == 1 && im.vs == 1;
+  const bool colour = im.nc == 3 && (im.hs == 1 || im.hs == 2) && (im.vs == 1 || im.vs == 2) && !(im.hs == 1 && im.vs == 2);
+  if (!grey && !colour) return im;
+  if (im.mcux != (im.w + 8 * im.hs - 1) / (8 * im.hs) || im.mcuy != (im.h + 8 * im.vs - 1) / (8 * im.vs)) return im;
+  if (im.tset < 0 || im.tset >= n_sets || im.ri < 0) return im;
+  im.lum = im.hs * im.vs;
+  im.bpm = im.lum + (im.nc == 3 ? 2 : 0);
+  im.nblocks = (long)im.mcux * im.mcuy * im.bpm;
+  if (im.block0 < 0 || im.block0 + im.nblocks > n_blocks) return im;
+  if (r[9] < 0 || im.out + 3L * im.w * im.h > out_bytes) return im;
+  im.ok = true;
+  return im;
+}
+
+struct JpegBits {
+  const unsigned char* p;
+  long pos, end;
+  unsigned long long buf;      // the next bits, from bit 63 down
+  int n, fake, status;         // bits in buf; how many of them (the lowest) stand for bytes past the end
+};
+
+// after it: at least 32 bits in the buffer (a symbol takes at most 16 code bits and 11 more)
+JPEG_HD void jpeg_refill(JpegBits& s) {
+  if (s.n > 32) return;
+  if (s.pos + 4 <= s.end) {
+    unsigned w;
+    __builtin_memcpy(&w, s.p + s.pos, 4);
+    const unsigned inv = ~w;
+    if (!((inv - 0x01010101u) & ~inv & 0x80808080u)) {          // no byte is FF: nothing to unstuff
+      s.buf |= (unsigned long long)__builtin_bswap32(w) << (32 - s.n);
+      s.n += 32;
+      s.pos += 4;
+      return;
+    }
+  }
+  for (int i = 0; i < 4; ++i) {
+    unsigned b = 0;
+    if (s.pos < s.end) {
+      b = s.p[s.pos++];
+      if (b == 0xFFu) {
+        if (s.pos < s.end && s.p[s.pos] == 0) ++s.pos;
+        else { s.status |= ZH_JPEG_STATUS_MARKER; s.pos = s.end; }
+      }
+    } else {
+      s.fake += 8;
+    }
+    s.buf |= (unsigned long long)b << (56 - s.n);
+    s.n += 8;
+  }
+}
+
+JPEG_HD void jpeg_consume(JpegBits& s, int c) {
+  s.buf = c ? s.buf << c : s.buf;
+  s.n -= c;
+  if (s.n < s.fake) s.status |= ZH_JPEG_STATUS_TRUNCATED;
+}
+
+struct JpegSegment {
+  JpegBits bits;
+  int pred0, pred1, pred2;     // DC predictors of Y, Cb, Cr: 0 at the start of every segment
+  int mcu, mcu_end, b, k;      // the state: MCU, block inside it, coefficient index (0: the DC symbol is next)
+};
+
+// The segment row `r` of image `im` over scan bytes [0, scan_bytes): false (and SEGMENT in *status) when it does not fit.
+JPEG_HD bool jpeg_segment(const int* r, const JpegImage& im, const unsigned char* scan, long scan_bytes, JpegSegment& s, int* status) {
+  const long lo = r[1], hi = r[2], first = r[3], total = (long)im.mcux * im.mcuy;
+  s.bits.p = scan; s.bits.pos = lo; s.bits.end = hi; s.bits.buf = 0; s.bits.n = 0; s.bits.fake = 0; s.bits.status = 0;
+  s.pred0 = s.pred1 = s.pred2 = 0;
+  s.mcu = s.mcu_end = (int)first; s.b = 0; s.k = 0;
+  if (lo < 0 || hi < lo || hi > scan_bytes || first < 0 || first >= total || (im.ri == 0 && first != 0)) {
+    *status = ZH_JPEG_STATUS_SEGMENT;
+    return false;
+  }
+  const long count = im.ri ? (im.ri < total - first ? im.ri : total - first) : total;
+  s.mcu_end = (int)(first + count);
+  *status = 0;
+  return true;
+}
+
+JPEG_HD long jpeg_segment_steps(const JpegSegment& s, const JpegImage& im) { return 64L * (s.mcu_end - s.mcu) * im.bpm; }
+JPEG_HD bool jpeg_segment_done(const JpegSegment& s) { return s.mcu >= s.mcu_end || s.bits.status != 0; }
+
+// natural-order index of zigzag position k: eight positions to a 64-bit literal, picked by selects (a table would live in memory)
+constexpr unsigned long long jpeg_zz8(unsigned long long a, unsigned long long b, unsigned long long c, unsigned long long d, unsigned long long e,
+                                      unsigned long long f, unsigned long long g, unsigned long long h) {
+  return a | b << 8 | c << 16 | d << 24 | e << 32 | f << 40 | g << 48 | h << 56;
+}
+JPEG_HD int jpeg_zigzag(int k) {
+  const int g = (k >> 3) & 7;
+  const unsigned long long w = g == 0   ? jpeg_zz8(0, 1, 8, 16, 9, 2, 3, 10)
+                               : g == 1 ? jpeg_zz8(17, 24, 32, 25, 18, 11, 4, 5)
+                               : g == 2 ? jpeg_zz8(12, 19, 26, 33, 40, 48, 41, 34)
+                               : g == 3 ? jpeg_zz8(27, 20, 13, 6, 7, 14, 21, 28)
+                               : g == 4 ? jpeg_zz8(35, 42, 49, 56, 57, 50, 43, 36)
+                               : g == 5 ? jpeg_zz8(29, 22, 15, 23, 30, 37, 44, 51)
+                               : g == 6 ? jpeg_zz8(58, 59, 52, 45, 38, 31, 39, 46)
+                                        : jpeg_zz8(53, 60, 61, 54, 47, 55, 62, 63);
+  return (int)((w >> (8 * (k & 7))) & 63);
+}
+
+// One symbol.  huff: the image's four Huffman tables; coef: the IMAGE's first block (int16 [nblocks, 64], zeroed): the block written is
+// mcu * bpm + b with mcu < mcu_end <= the image's MCUs, the index inside it jpeg_zigzag() of k <= 63.
+JPEG_HD void jpeg_step(JpegSegment& s, const JpegImage& im, const unsigned char* huff, short* coef) {
+  JpegBits& bt = s.bits;
+  jpeg_refill(bt);
+  const int comp = s.b < im.lum ? 0 : s.b - im.lum + 1, ac = s.k != 0;
+  const unsigned char* t = huff + (2 * (comp != 0) + ac) * ZH_JPEG_HUFF_TABLE_BYTES;
+  const unsigned peek = (unsigned)(bt.buf >> 48);
+  const unsigned e = ((const unsigned short*)t)[peek >> 8];
+  int len = (int)(e >> 8), val = (int)(e & 255u);
+  if (!e) {                                                       // a code of 9 .. 16 bits, or none
+    const int* maxcode = (const int*)(t + JPEG_T_MAXCODE);
+    const int* valoff = (const int*)(t + JPEG_T_VALOFF);
+    for (int l = 9; l <= 16; ++l) {
+      const int code = (int)(peek >> (16 - l));
+      if (len == 0 && code <= maxcode[l]) { len = l; val = t[JPEG_T_VALS + ((code + valoff[l]) & 255)]; }
+    }
+    if (len == 0) { bt.status |= ZH_JPEG_STATUS_CODE; return; }
+  }
+  jpeg_consume(bt, len);
+  const int r = ac ? val >> 4 : 0, sz = ac ? val & 15 : val;
+  if (sz > (ac ? 10 : 11)) { bt.status |= ZH_JPEG_STATUS_BITS; return; }
+  int v = sz ? (int)(bt.buf >> (64 - sz)) : 0;
+  jpeg_consume(bt, sz);
+  if (sz && v < (1 << (sz - 1))) v -= (1 << sz) - 1;
+  if (bt.status) return;
+  short* blk = coef + ((long)s.mcu * im.bpm + s.b) * 64;
+  if (!ac) {
+    int pred = comp == 0 ? s.pred0 : comp == 1 ? s.pred1 : s.pred2;
+    pred += v;
+    if (comp == 0) s.pred0 = pred; else if (comp == 1) s.pred1 = pred; else s.pred2 = pred;
+    blk[0] = (short)pred;
+    s.k = 1;
+  } else if (sz == 0) {
+    if (r == 15) {
+      s.k += 16;
+      if (s.k > 64) { bt.status |= ZH_JPEG_STATUS_INDEX; return; }
+    } else {
+      s.k = 64;                                                     // end of block
+    }
+  } else {
+    s.k += r;
+    if (s.k > 63) { bt.status |= ZH_JPEG_STATUS_INDEX; return; }
+    blk[jpeg_zigzag(s.k)] = (short)v;
+    ++s.k;
+  }
+  if (s.k >= 64) {
+    s.k = 0;
+    if (++s.b == im.bpm) { s.b = 0; ++s.mcu; }
+  }
+}
+
+// ---- pixels
+// one pass of the islow inverse DCT over eight values, descaled by `shift` bits with rounding (13-bit constants)
+JPEG_HD void jpeg_idct8(const long long* in, int stride, long long* out, int shift) {
+  const long long i0 = in[0], i1 = in[stride], i2 = in[2 * stride], i3 = in[3 * stride], i4 = in[4 * stride], i5 = in[5 * stride],
+                  i6 = in[6 * stride], i7 = in[7 * stride];
+  long long z1 = (i2 + i6) * 4433;
+  const long long t2 = z1 - i6 * 15137, t3 = z1 + i2 * 6270;
+  const long long t0 = (i0 + i4) * 8192, t1 = (i0 - i4) * 8192;
+  const long long t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  long long a0 = i7, a1 = i5, a2 = i3, a3 = i1;
+  z1 = a0 + a3;
+  long long z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3;
+  const long long z5 = (z3 + z4) * 9633;
+  a0 *= 2446; a1 *= 16819; a2 *= 25172; a3 *= 12299;
+  z1 *= -7373; z2 *= -20995;
+  z3 = z3 * -16069 + z5;
+  z4 = z4 * -3196 + z5;
+  a0 += z1 + z3; a1 += z2 + z4; a2 += z2 + z3; a3 += z1 + z4;
+  const long long half = 1LL << (shift - 1);
+  out[0] = (t10 + a3 + half) >> shift;
+  out[stride] = (t11 + a2 + half) >> shift;
+  out[2 * stride] = (t12 + a1 + half) >> shift;
+  out[3 * stride] = (t13 + a0 + half) >> shift;
+  out[4 * stride] = (t13 - a0 + half) >> shift;
+  out[5 * stride] = (t12 - a1 + half) >> shift;
+  out[6 * stride] = (t11 - a2 + half) >> shift;
+  out[7 * stride] = (t10 - a3 + half) >> shift;
+}
+
+// coef int16 [64] (natural order) x q u16 [64] -> 8 x 8 samples at dst (row stride `ld`): columns descaled by 11 bits, rows by 18, + 128
+JPEG_HD void jpeg_idct_block(const short* coef, const unsigned short* q, unsigned char* dst, long ld) {
+  long long x[64], w[64];
+#pragma unroll
+  for (int i = 0; i < 64; ++i) x[i] = (long long)coef[i] * (long long)q[i];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) jpeg_idct8(x + c, 8, w + c, 11);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) jpeg_idct8(w + 8 * r, 1, x + 8 * r, 18);
+#pragma unroll
+  for (int r = 0; r < 8; ++r)
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const long long v = x[8 * r + c] + 128;
+      dst[r * ld + c] = (unsigned char)(v < 0 ? 0 : v > 255 ? 255 : v);
+    }
+}
+
+// where block j of the image (scan order) lies in its planes: the planes follow each other at samples + 64 * block0 — Y
+// [mcuy vs 8, mcux hs 8], then Cb and Cr [mcuy 8, mcux 8]; q_class: 0 luma, 1 chroma
+JPEG_HD long jpeg_block_place(const JpegImage& im, long j, long* ld, int* q_class) {
+  const long mcu = j / im.bpm;
+  const int b = (int)(j - mcu * im.bpm);
+  const long my = mcu / im.mcux, mx = mcu - my * im.mcux;
+  const long yw = (long)im.mcux * im.hs * 8, ysize = yw * im.mcuy * im.vs * 8, cw = (long)im.mcux * 8, csize = cw * im.mcuy * 8;
+  if (b < im.lum) {
+    const int by = b / im.hs, bx = b - by * im.hs;
+    *ld = yw; *q_class = 0;
+    return ((my * im.vs + by) * 8) * yw + (mx * im.hs + bx) * 8;
+  }
+  *ld = cw; *q_class = 1;
+  return ysize + (b - im.lum) * csize + (my * 8) * cw + mx * 8;
+}
+
+// the chroma sample of pixel (x, y) from plane c [*, cld], cropped to cw x ch samples before it is upsampled
+JPEG_HD int jpeg_chroma(const unsigned char* c, long cld, int cw, int ch, int hs, int vs, int x, int y) {
+  if (hs == 1) return c[(long)y * cld + x];
+  const int i = x >> 1;
+  if (cw <= 2) return c[(long)(vs == 2 ? y >> 1 : y) * cld + i];          // a narrow component is replicated
+  const int il = i > 0 ? i - 1 : 0, ir = i < cw - 1 ? i + 1 : cw - 1, in = (x & 1) ? ir : il;
+  if (vs == 1) {
+    const unsigned char* row = c + (long)y * cld;
+    if (in == i) return row[i];                                          // the first and the last output
+    return (3 * row[i] + row[in] + ((x & 1) ? 2 : 1)) >> 2;
+  }
+  const int j = y >> 1, jn = (y & 1) ? (j < ch - 1 ? j + 1 : j) : (j > 0 ? j - 1 : j);
+  const unsigned char *row = c + (long)j * cld, *nb = c + (long)jn * cld;
+  const int cs = 3 * row[i] + nb[i], csn = 3 * row[in] + nb[in];
+  const int bias = (x & 1) ? 7 : 8;
+  if (in == i) return (4 * cs + bias) >> 4;
+  return (3 * cs + csn + bias) >> 4;
+}
+
+JPEG_HD unsigned char jpeg_clamp8(int v) { return (unsigned char)(v < 0 ? 0 : v > 255 ? 255 : v); }
+
+// pixel (x, y) of the image from its sample planes -> rgb[3]
+JPEG_HD void jpeg_pixel(const JpegImage& im, const unsigned char* planes, int x, int y, unsigned char* rgb) {
+  const long yw = (long)im.mcux * im.hs * 8, ysize = yw * im.mcuy * im.vs * 8, cld = (long)im.mcux * 8, csize = cld * im.mcuy * 8;
+  const int Y = planes[(long)y * yw + x];
+  if (im.nc == 1) { rgb[0] = rgb[1] = rgb[2] = (unsigned char)Y; return; }
+  const int cw = (im.w + im.hs - 1) / im.hs, ch = (im.h + im.vs - 1) / im.vs;
+  const int cb = jpeg_chroma(planes + ysize, cld, cw, ch, im.hs, im.vs, x, y) - 128;
+  const int cr = jpeg_chroma(planes + ysize + csize, cld, cw, ch, im.hs, im.vs, x, y) - 128;
+  rgb[0] = jpeg_clamp8(Y + ((91881 * cr + 32768) >> 16));               // F(1.402), F(x) = int(x 65536 + 0.5)
+  rgb[1] = jpeg_clamp8(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16)); // F(0.34414), F(0.71414)
+  rgb[2] = jpeg_clamp8(Y + ((116130 * cb + 32768) >> 16));              // F(1.772)
+}

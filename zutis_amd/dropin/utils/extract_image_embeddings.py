@@ -17,6 +17,9 @@ bytes cross to the device in one copy per batch (zutis_amd.preprocess.device_bat
 resizes, crops and normalises them — the
 very bytes of Pillow's resampler and the very fp32 values of `_preprocess`, which stays here as the host statement of the same
 transform (the tests' reference), so the embeddings are bit for bit those of the host path.
+`decoder="device"` (opt-in; "host" is the default): the threads only read the files and parse their headers, baseline JPEG files
+cross to the device as file bytes and zh_jpeg_decode (zutis_amd/jpeg_device.py: byte for byte Pillow's pixels) decodes them in front
+of the resize kernel; any other file, and any the device reports as damaged, is decoded by Pillow as before — the embeddings are the same.
 """
 import os
 import pickle as pkl
@@ -64,6 +67,7 @@ def extract_image_embeddings(
         *,
         state_dict: Optional[dict] = None,
         precision: str = "exact",
+        decoder: str = "host",
 ) -> Dict[str, torch.Tensor]:
     if "ViT" not in model_name:
         raise NotImplementedError(f"{model_name}: only the CLIP-ViT towers are on the MI355X hot path")
@@ -77,7 +81,7 @@ def extract_image_embeddings(
     n_px = patch * enc.grid
     out: Dict[str, torch.Tensor] = {}
     lut = torch.from_numpy(preprocess.normalise_table(_MEAN, _STD)).to(device)
-    loader = preprocess.BatchLoader(p_images, n_px, batch_size, n_workers, resize_crop_box)
+    loader = preprocess.BatchLoader(p_images, n_px, batch_size, n_workers, resize_crop_box, decoder=decoder)
 
     def transform(batch, staged):
         packed, desc = preprocess.split_staging(staged, len(batch.paths))

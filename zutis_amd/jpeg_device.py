@@ -1,0 +1,559 @@
+"""The image the device JPEG decoder makes, defined in NumPy: what zh_jpeg_decode (csrc/jpeg.hip over csrc/jpeg_codec.h) and
+zh_jpeg_decode_host produce byte for byte, and what `Image.open(p).convert("RGB")` gives for the files it serves (Pillow on
+libjpeg-turbo: integer arithmetic throughout, restated here from the public algorithms).
+
+  served          SOF0 (baseline sequential Huffman), 8-bit samples, 8-bit quantisation tables, ONE interleaved scan over all components
+                  with Ss, Se, Ah, Al = 0, 63, 0, 0; one component at sampling (1, 1), or three with luma (1, 1), (2, 1) or (2, 2), both
+                  chroma (1, 1) on the same tables, a JFIF APP0 or component ids 1, 2, 3, no Adobe APP14; no DNL; every table defined;
+                  the scan followed by EOI.  parse() returns None for everything else — progressive, arithmetic, 12-bit, CMYK / YCCK,
+                  RGB-coded, multi-scan, other samplings, files that are no JPEG, anything it is unsure of — and the host decodes those.
+  entropy         T.81 Huffman decoding, FF 00 unstuffed; the scan is cut at its RSTn markers into segments that decode independently
+                  (the DC predictors start at 0 in each); coefficients de-zigzagged to natural order.
+  inverse DCT     "islow": 13-bit constants, columns first descaled by 11 bits, rows by 18, + 128, clamped to 0 .. 255.
+  cropping        a component's plane is cut to ceil(W h / hmax) x ceil(H v / vmax) samples BEFORE it is upsampled.
+  upsampling      the "fancy" triangle filter, h2v1 and h2v2; a component whose cropped width is <= 2 is replicated instead.
+  colour          YCbCr -> RGB in 16-bit fixed point, F(x) = int(x * 65536 + 0.5); a grey file gives Y three times.
+
+pack() lays the descriptor arrays of one launch out (scan bytes, segment rows sorted by length, image rows, table sets deduplicated
+across the batch, output offsets); table_set_bytes() is the ONE form of the canonical Huffman tables that decode_np, the host entry and
+the kernel read.  No torch at import.
+"""
+from __future__ import annotations
+
+import dataclasses
+import functools
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import _lib
+
+_K = _lib.constants()
+IMAGE_WORDS, SEGMENT_WORDS = _K["ZH_JPEG_IMAGE_WORDS"], _K["ZH_JPEG_SEGMENT_WORDS"]
+TABLE_BYTES, TABLE_SET_BYTES = _K["ZH_JPEG_HUFF_TABLE_BYTES"], _K["ZH_JPEG_TABLE_SET_BYTES"]
+MAX_TABLE_SETS, MAX_SEGMENTS = _K["ZH_JPEG_MAX_TABLE_SETS"], _K["ZH_JPEG_MAX_SEGMENTS"]
+STATUS = {k[len("ZH_JPEG_STATUS_"):].lower(): v for k, v in _K.items() if k.startswith("ZH_JPEG_STATUS_")}
+DECODERS = ("host", "device")
+ALIGN = 16                                        # byte alignment of an image inside the output (descriptors hold offset / 16)
+_LOOK, _MAXCODE, _VALOFF, _VALS = 0, 512, 584, 656      # byte offsets inside one Huffman table: u16 [256], i32 [18], i32 [18], u8 [256]
+
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
+
+
+class DamagedScan(ValueError):
+    """decode_np met entropy-coded data no decoder can follow; .status holds the codec's status bit."""
+
+    def __init__(self, status: int, what: str):
+        super().__init__(what)
+        self.status = status
+
+
+@dataclasses.dataclass(frozen=True)
+class JpegPlan:
+    """What parse() read from one file.  segments int64 [n, 3]: (first byte, end byte, first MCU) of every entropy segment, offsets
+    into the file; quant int [2, 64] (luma, chroma) in natural order; huff: the four canonical tables (luma DC, luma AC, chroma DC,
+    chroma AC) as (counts [16], values); a grey file's chroma entries are empty."""
+    width: int
+    height: int
+    ncomp: int
+    hs: int
+    vs: int
+    quant: np.ndarray
+    huff: tuple
+    restart_interval: int
+    segments: np.ndarray
+
+    @property
+    def mcux(self):
+        return -(-self.width // (8 * self.hs))
+
+    @property
+    def mcuy(self):
+        return -(-self.height // (8 * self.vs))
+
+    @property
+    def n_mcus(self):
+        return self.mcux * self.mcuy
+
+    @property
+    def blocks_per_mcu(self):
+        return self.hs * self.vs + (2 if self.ncomp == 3 else 0)
+
+    @property
+    def n_blocks(self):
+        return self.n_mcus * self.blocks_per_mcu
+
+
+# ------------------------------------------------------------------------------------------------- tables
+def huffman_table_bytes(counts, values) -> Optional[np.ndarray]:
+    """u8 [TABLE_BYTES] of one canonical table (T.81 Annex C): look u16 [256] = (length << 8 | value) of the code that is a prefix of the
+    8 bits, 0 when it is longer; maxcode i32 [18] (index = length, -1: no code of that length); valoff i32 [18] = index of the length's
+    first value minus its first code; vals u8 [256].  None when the counts describe no prefix code.  No counts: all zero (no code).
+    Cached: files written without optimised tables all carry the same four; the array is shared and read-only."""
+    return _huffman_table(tuple(int(c) for c in counts), tuple(int(v) for v in values))
+
+
+@functools.lru_cache(maxsize=4096)
+def _huffman_table(counts: tuple, values: tuple) -> Optional[np.ndarray]:
+    out = np.zeros(TABLE_BYTES, np.uint8)
+    if len(counts) != 16 or sum(counts) != len(values) or len(values) > 256:
+        return None
+    look, maxcode, valoff = out[_LOOK:_MAXCODE].view("<u2"), out[_MAXCODE:_VALOFF].view("<i4"), out[_VALOFF:_VALS].view("<i4")
+    maxcode[:] = -1
+    code = k = 0
+    for length in range(1, 17):
+        n = counts[length - 1]
+        if code + n > (1 << length):
+            return None
+        valoff[length] = k - code
+        for j in range(n):
+            if length <= 8:
+                first = (code + j) << (8 - length)
+                look[first:first + (1 << (8 - length))] = (length << 8) | values[k + j]
+        k += n
+        code += n
+        if n:
+            maxcode[length] = code - 1
+        code <<= 1
+    out[_VALS:_VALS + len(values)] = values
+    out.setflags(write=False)
+    return out
+
+
+def table_set_bytes(plan: JpegPlan) -> bytes:
+    """The file's table set as the codec reads it: four Huffman tables (luma DC, luma AC, chroma DC, chroma AC), then the two
+    quantisation tables u16 [2, 64] in natural order."""
+    parts = [huffman_table_bytes(c, v) for c, v in plan.huff]
+    return b"".join(p.tobytes() for p in parts) + np.asarray(plan.quant, "<u2").tobytes()
+
+
+# ------------------------------------------------------------------------------------------------- the file's markers
+def _u16(d, at):
+    return (d[at] << 8) | d[at + 1]
+
+
+def parse(data) -> Optional[JpegPlan]:
+    """The plan of one file's bytes, or None when the device does not serve it (module docstring)."""
+    d = bytes(data)
+    n = len(d)
+    if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
+        return None
+    quant, huff = {}, {}
+    frame = None
+    jfif = False
+    ri = 0
+    at = 2
+    while True:
+        if at + 4 > n or d[at] != 0xFF:
+            return None
+        while at < n and d[at] == 0xFF:                       # fill bytes in front of a marker
+            at += 1
+        if at >= n:
+            return None
+        m = d[at]
+        at += 1
+        if m in (0x00, 0x01, 0xD8, 0xD9) or 0xD0 <= m <= 0xD7:
+            return None
+        if at + 2 > n:
+            return None
+        L = _u16(d, at)
+        if L < 2 or at + L > n:
+            return None
+        body = d[at + 2:at + L]
+        if m == 0xE0:
+            jfif = jfif or body[:5] == b"JFIF\x00"
+        elif m == 0xEE:
+            if body[:5] == b"Adobe":
+                return None
+        elif m == 0xDB:
+            p = 0
+            while p < len(body):
+                pq, tq = body[p] >> 4, body[p] & 15
+                if pq != 0 or tq > 3 or p + 65 > len(body):
+                    return None
+                q = np.zeros(64, np.int64)
+                q[ZIGZAG] = np.frombuffer(body[p + 1:p + 65], np.uint8)
+                quant[tq] = q
+                p += 65
+        elif m == 0xC4:
+            p = 0
+            while p < len(body):
+                if p + 17 > len(body):
+                    return None
+                tc, th = body[p] >> 4, body[p] & 15
+                counts = list(body[p + 1:p + 17])
+                nv = sum(counts)
+                if tc > 1 or th > 3 or nv > 256 or p + 17 + nv > len(body):
+                    return None
+                values = list(body[p + 17:p + 17 + nv])
+                if huffman_table_bytes(counts, values) is None or (tc == 0 and any(v > 11 for v in values)):
+                    return None
+                huff[(tc, th)] = (counts, values)
+                p += 17 + nv
+        elif m == 0xC0:
+            if frame is not None or len(body) < 6:
+                return None
+            nc = body[5]
+            if body[0] != 8 or len(body) != 6 + 3 * nc or nc not in (1, 3):
+                return None
+            frame = (_u16(body, 1), _u16(body, 3), [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(nc)])
+        elif 0xC1 <= m <= 0xCF or m in (0xDC, 0xDE, 0xDF):     # other frame types, arithmetic conditioning, DNL, hierarchical
+            return None
+        elif m == 0xDD:
+            if L != 4:
+                return None
+            ri = _u16(body, 0)
+        elif m == 0xDA:
+            break
+        at += L
+    # ---- the frame and the scan header
+    if frame is None:
+        return None
+    H, W, comps = frame
+    if H < 1 or W < 1:
+        return None
+    nc = len(comps)
+    if len(body) != 4 + 2 * nc or body[0] != nc or tuple(body[1 + 2 * nc:]) != (0, 63, 0):
+        return None
+    sel = []
+    for i, (cid, _, _, _) in enumerate(comps):
+        if body[1 + 2 * i] != cid:
+            return None
+        sel.append((body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15))
+    if nc == 1:
+        if (comps[0][1], comps[0][2]) != (1, 1):
+            return None
+    else:
+        if (comps[0][1], comps[0][2]) not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
+            return None
+        if not jfif and [c[0] for c in comps] != [1, 2, 3]:
+            return None
+        if comps[1][3] != comps[2][3] or sel[1] != sel[2]:      # both chroma on the same tables: a table set has two classes
+            return None
+    classes = [0] if nc == 1 else [0, 1]
+    for cls in classes:
+        tq, (td, ta) = comps[cls][3], sel[cls]
+        if tq not in quant or (0, td) not in huff or (1, ta) not in huff:
+            return None
+    q2 = np.zeros((2, 64), np.int64)
+    tables = []
+    for cls in (0, 1):
+        if cls in classes:
+            q2[cls] = quant[comps[cls][3]]
+            tables += [huff[(0, sel[cls][0])], huff[(1, sel[cls][1])]]
+        else:
+            tables += [([0] * 16, []), ([0] * 16, [])]
+    hs, vs = comps[0][1], comps[0][2]
+    n_mcus = -(-W // (8 * hs)) * -(-H // (8 * vs))
+    # ---- the entropy segments: a vectorised search for FF xx with xx neither 00 (a stuffed byte) nor FF (fill)
+    start = at + L
+    a = np.frombuffer(d, np.uint8, n - start, start)
+    ff = np.flatnonzero(a[:-1] == 0xFF) if a.size > 1 else np.zeros(0, np.int64)
+    marks = ff[(a[ff + 1] != 0) & (a[ff + 1] != 0xFF)]
+    codes = a[marks + 1]
+    rst = (codes >= 0xD0) & (codes <= 0xD7)
+    stop = np.flatnonzero(~rst)
+    if stop.size == 0 or codes[stop[0]] != 0xD9:              # the scan is followed by EOI (no second scan, no DNL, no cut file)
+        return None
+    k = int(stop[0])
+    if not np.array_equal(codes[:k], 0xD0 + (np.arange(k) & 7)) or (k and not ri):
+        return None
+    lo = np.concatenate(([0], marks[:k] + 2))
+    hi = marks[:k + 1].copy()
+    for i in range(k + 1):                                    # fill bytes in front of a marker are not data
+        while hi[i] > lo[i] and a[hi[i] - 1] == 0xFF:
+            hi[i] -= 1
+    segs = np.stack([lo + start, hi + start, np.arange(k + 1) * (ri if ri else 0)], axis=1).astype(np.int64)
+    return JpegPlan(W, H, nc, hs, vs, q2, tuple((tuple(c), tuple(v)) for c, v in tables), ri, segs)
+
+
+# ------------------------------------------------------------------------------------------------- entropy decoding
+class _Bits:
+    """The bits of one segment, FF 00 unstuffed; reading past the end or meeting a marker is DamagedScan."""
+
+    def __init__(self, seg: bytes):
+        a = np.frombuffer(seg, np.uint8)
+        ff = np.flatnonzero(a == 0xFF)
+        if ff.size and (ff[-1] == a.size - 1 or (a[ff + 1] != 0).any()):       # every FF of a segment is followed by its stuffed 00
+            raise DamagedScan(STATUS["marker"], "a marker inside an entropy segment")
+        seg = seg.replace(b"\xff\x00", b"\xff")
+        self.total = 8 * len(seg)
+        self.value = int.from_bytes(seg + b"\x00\x00\x00\x00", "big")
+        self.pos = 0
+
+    def peek16(self):
+        return (self.value >> (self.total + 32 - self.pos - 16)) & 0xFFFF
+
+    def take(self, nbits):
+        v = (self.value >> (self.total + 32 - self.pos - nbits)) & ((1 << nbits) - 1) if nbits else 0
+        self.pos += nbits
+        if self.pos > self.total:
+            raise DamagedScan(STATUS["truncated"], "the entropy segment ends inside a symbol")
+        return v
+
+
+def _symbol(bits: _Bits, table):
+    look, maxcode, valoff, vals = table
+    peek = bits.peek16()
+    e = look[peek >> 8]
+    if e:
+        bits.take(e >> 8)
+        return e & 255
+    for length in range(9, 17):
+        code = peek >> (16 - length)
+        if code <= maxcode[length]:
+            bits.take(length)
+            return vals[(code + valoff[length]) & 255]
+    raise DamagedScan(STATUS["code"], "an undefined Huffman code")
+
+
+def _extend(v, s):
+    return v - (1 << s) + 1 if s and v < (1 << (s - 1)) else v
+
+
+def _tables_of(set_bytes: bytes):
+    out = []
+    for t in range(4):
+        b = np.frombuffer(set_bytes, np.uint8, TABLE_BYTES, t * TABLE_BYTES)
+        out.append((b[_LOOK:_MAXCODE].view("<u2").tolist(), b[_MAXCODE:_VALOFF].view("<i4").tolist(), b[_VALOFF:_VALS].view("<i4").tolist(),
+                    b[_VALS:].tolist()))
+    return out
+
+
+def decode_coefficients(plan: JpegPlan, data) -> np.ndarray:
+    """int16 [n_blocks, 64]: the quantised coefficients of every block in natural order, blocks in scan order (MCU by MCU, inside an MCU
+    the luma blocks row by row, then Cb, Cr)."""
+    d = bytes(data)
+    tables = _tables_of(table_set_bytes(plan))
+    bpm, lum = plan.blocks_per_mcu, plan.hs * plan.vs
+    coef = np.zeros((plan.n_blocks, 64), np.int64)
+    zz = ZIGZAG.tolist()
+    done = 0
+    for lo, hi, first in plan.segments.tolist():
+        if first < 0 or first >= plan.n_mcus or (plan.restart_interval == 0 and first != 0):
+            raise DamagedScan(STATUS["segment"], "an entropy segment outside the image")
+        count = min(plan.restart_interval, plan.n_mcus - first) if plan.restart_interval else plan.n_mcus
+        bits = _Bits(d[lo:hi])
+        pred = [0, 0, 0]
+        for mcu in range(first, first + count):
+            for b in range(bpm):
+                comp = 0 if b < lum else b - lum + 1
+                cls = 1 if comp else 0
+                row = coef[mcu * bpm + b]
+                s = _symbol(bits, tables[2 * cls])
+                if s > 11:
+                    raise DamagedScan(STATUS["bits"], "a DC category above 11")
+                pred[comp] += _extend(bits.take(s), s)
+                row[0] = pred[comp]
+                k = 1
+                while k < 64:
+                    rs = _symbol(bits, tables[2 * cls + 1])
+                    r, s = rs >> 4, rs & 15
+                    if s == 0:
+                        if r != 15:
+                            break
+                        k += 16
+                        if k > 64:
+                            raise DamagedScan(STATUS["index"], "a zero run past coefficient 63")
+                        continue
+                    if s > 10:
+                        raise DamagedScan(STATUS["bits"], "an AC category above 10")
+                    k += r
+                    if k > 63:
+                        raise DamagedScan(STATUS["index"], "a coefficient index past 63")
+                    row[zz[k]] = _extend(bits.take(s), s)
+                    k += 1
+        done += count
+    if done != plan.n_mcus:
+        raise DamagedScan(STATUS["incomplete"], "the entropy segments do not cover the image's MCUs")
+    return coef.astype(np.int16)
+
+
+# ------------------------------------------------------------------------------------------------- pixels
+def _idct_pass(x, shift):
+    """One pass of the islow inverse DCT over axis -2 of int64 [..., 8, n] -> the same shape, descaled by `shift` bits with rounding."""
+    i0, i1, i2, i3, i4, i5, i6, i7 = (x[..., k, :] for k in range(8))
+    z1 = (i2 + i6) * 4433
+    t2 = z1 - i6 * 15137
+    t3 = z1 + i2 * 6270
+    t0 = (i0 + i4) << 13
+    t1 = (i0 - i4) << 13
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    a0, a1, a2, a3 = i7, i5, i3, i1
+    z1, z2, z3, z4 = a0 + a3, a1 + a2, a0 + a2, a1 + a3
+    z5 = (z3 + z4) * 9633
+    a0, a1, a2, a3 = a0 * 2446, a1 * 16819, a2 * 25172, a3 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    a0, a1, a2, a3 = a0 + z1 + z3, a1 + z2 + z4, a2 + z2 + z3, a3 + z1 + z4
+    out = np.stack([t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3], axis=-2)
+    return (out + (1 << (shift - 1))) >> shift
+
+
+def idct_blocks(coef: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """u8 [n, 8, 8] samples of int [n, 64] quantised coefficients under the quantisation table q [64] (both in natural order)."""
+    x = (coef.astype(np.int64) * q.astype(np.int64)).reshape(-1, 8, 8)
+    w = _idct_pass(x, 11)                                     # columns: index [n, v, x] -> [n, y, x]
+    r = _idct_pass(w.transpose(0, 2, 1), 18).transpose(0, 2, 1)      # rows
+    return np.clip(r + 128, 0, 255).astype(np.uint8)
+
+
+def _h2v1(s):
+    ch, cw = s.shape
+    s = s.astype(np.int64)
+    out = np.empty((ch, 2 * cw), np.int64)
+    left, right = np.concatenate((s[:, :1], s[:, :-1]), 1), np.concatenate((s[:, 1:], s[:, -1:]), 1)
+    out[:, 0::2] = (3 * s + left + 1) >> 2
+    out[:, 1::2] = (3 * s + right + 2) >> 2
+    out[:, 0], out[:, -1] = s[:, 0], s[:, -1]
+    return out
+
+
+def _h2v2(s):
+    ch, cw = s.shape
+    s = s.astype(np.int64)
+    above, below = np.concatenate((s[:1], s[:-1]), 0), np.concatenate((s[1:], s[-1:]), 0)
+    out = np.empty((2 * ch, 2 * cw), np.int64)
+    for v, nb in ((0, above), (1, below)):
+        cs = 3 * s + nb
+        left, right = np.concatenate((cs[:, :1], cs[:, :-1]), 1), np.concatenate((cs[:, 1:], cs[:, -1:]), 1)
+        even, odd = (3 * cs + left + 8) >> 4, (3 * cs + right + 7) >> 4
+        even[:, 0], odd[:, -1] = (4 * cs[:, 0] + 8) >> 4, (4 * cs[:, -1] + 7) >> 4
+        out[v::2, 0::2], out[v::2, 1::2] = even, odd
+    return out
+
+
+def _upsample(s, hs, vs, W, H):
+    """The cropped chroma plane s at the image's size."""
+    if (hs, vs) == (1, 1):
+        return s.astype(np.int64)
+    if s.shape[1] <= 2:
+        up = np.repeat(np.repeat(s, vs, 0), hs, 1).astype(np.int64)
+    else:
+        up = _h2v1(s) if vs == 1 else _h2v2(s)
+    return up[:H, :W]
+
+
+def _fix(x):
+    return int(x * 65536 + 0.5)
+
+
+def pixels_of(plan: JpegPlan, coef: np.ndarray) -> np.ndarray:
+    """u8 [H, W, 3] from the coefficients of decode_coefficients."""
+    W, H, hs, vs = plan.width, plan.height, plan.hs, plan.vs
+    bpm, lum = plan.blocks_per_mcu, hs * vs
+    per_mcu = coef.reshape(plan.mcuy, plan.mcux, bpm, 64)
+
+    def plane(first, h, v, q):
+        px = idct_blocks(per_mcu[:, :, first:first + h * v].reshape(-1, 64), q).reshape(plan.mcuy, plan.mcux, v, h, 8, 8)
+        return px.transpose(0, 2, 4, 1, 3, 5).reshape(plan.mcuy * v * 8, plan.mcux * h * 8)
+
+    y = plane(0, hs, vs, plan.quant[0])[:H, :W].astype(np.int64)
+    if plan.ncomp == 1:
+        return np.repeat(y[:, :, None], 3, 2).astype(np.uint8)
+    cw, ch = -(-W // hs), -(-H // vs)
+    cb = _upsample(plane(lum, 1, 1, plan.quant[1])[:ch, :cw], hs, vs, W, H) - 128
+    cr = _upsample(plane(lum + 1, 1, 1, plan.quant[1])[:ch, :cw], hs, vs, W, H) - 128
+    r = y + ((_fix(1.402) * cr + 32768) >> 16)
+    g = y + ((-_fix(0.34414) * cb + 32768 - _fix(0.71414) * cr) >> 16)
+    b = y + ((_fix(1.772) * cb + 32768) >> 16)
+    return np.clip(np.stack([r, g, b], 2), 0, 255).astype(np.uint8)
+
+
+def decode_np(data, plan: Optional[JpegPlan] = None) -> np.ndarray:
+    """u8 [H, W, 3]: the definition.  ValueError for a file parse() does not serve, DamagedScan for a scan no decoder can follow."""
+    plan = parse(data) if plan is None else plan
+    if plan is None:
+        raise ValueError("jpeg_device.decode_np: not a file the device decoder serves")
+    return pixels_of(plan, decode_coefficients(plan, data))
+
+
+# ------------------------------------------------------------------------------------------------- one launch
+@dataclasses.dataclass
+class Packed:
+    """The flat arrays of one launch (include/zutis_hip.h, zh_jpeg_decode): scan u8 [scan_bytes]; segments int32 [S, 4] = (image, first
+    byte, end byte, first MCU), longest first; images int32 [B, 12]; tables u8 [n_sets, TABLE_SET_BYTES]; out_off int64 [B] (bytes,
+    multiples of 16) and out_bytes; n_blocks: 8 x 8 blocks of the whole batch (the workspace's size)."""
+    scan: np.ndarray
+    segments: np.ndarray
+    images: np.ndarray
+    tables: np.ndarray
+    out_off: np.ndarray
+    out_bytes: int
+    n_blocks: int
+    shapes: List[tuple]
+    max_image_blocks: int = 1        # the largest image's blocks and pixels: the widths of the pixel stage's grids
+    max_image_pixels: int = 1
+    kept: Optional[List[int]] = None      # positions, in pack()'s argument lists, of the images these arrays describe (all, unless skip_overflow)
+
+
+def pack(plans: Sequence[JpegPlan], datas: Sequence, out_off: Optional[Sequence[int]] = None, out_bytes: Optional[int] = None,
+         skip_overflow: bool = False) -> Packed:
+    """The descriptor arrays of one launch over `plans` (of the files `datas`).  out_off: where each image's [H, W, 3] bytes go (default:
+    back to back, aligned to 16).  More than MAX_TABLE_SETS distinct table sets is a ValueError — or, with skip_overflow, the images
+    that would bring a set past the limit are left out (Packed.kept lists the others: the caller leaves the rest to the host); more
+    than MAX_SEGMENTS segments is a ValueError."""
+    sets, set_index, kept = {}, [], []
+    for i, p in enumerate(plans):
+        key = table_set_bytes(p)
+        if key not in sets and len(sets) == MAX_TABLE_SETS:
+            if not skip_overflow:
+                raise ValueError(f"jpeg_device.pack: more than {MAX_TABLE_SETS} distinct table sets in one launch")
+            continue
+        set_index.append(sets.setdefault(key, len(sets)))
+        kept.append(i)
+    if out_off is not None:
+        out_off = [out_off[i] for i in kept]
+    plans, datas = [plans[i] for i in kept], [datas[i] for i in kept]
+    B = len(plans)
+    if out_off is None:
+        sizes = [-(-3 * p.width * p.height // ALIGN) * ALIGN for p in plans]
+        out_off = np.concatenate(([0], np.cumsum(sizes)))[:-1] if B else np.zeros(0)
+        out_bytes = int(sum(sizes))
+    out_off = np.asarray(out_off, np.int64).reshape(B)
+    if (out_off % ALIGN).any():
+        raise ValueError("jpeg_device.pack: output offsets are multiples of 16")
+    images = np.zeros((B, IMAGE_WORDS), np.int32)
+    chunks, rows, at, blocks = [], [], 0, 0
+    for b, (p, d) in enumerate(zip(plans, datas)):
+        d = np.frombuffer(bytes(d) if not isinstance(d, np.ndarray) else d, np.uint8)
+        images[b] = (p.width, p.height, p.ncomp, p.hs, p.vs, p.mcux, p.mcuy, set_index[b], blocks, out_off[b] // ALIGN, p.restart_interval, 0)
+        blocks += p.n_blocks
+        for lo, hi, first in p.segments.tolist():
+            chunks.append(d[lo:hi])
+            rows.append((b, at, at + hi - lo, first))
+            at += hi - lo
+    if len(rows) > MAX_SEGMENTS or at >= 2 ** 31 or blocks >= 2 ** 24:
+        raise ValueError(f"jpeg_device.pack: {len(rows)} segments / {at} scan bytes / {blocks} blocks exceed one launch")
+    segments = np.asarray(rows, np.int32).reshape(-1, SEGMENT_WORDS)
+    order = np.argsort(-(segments[:, 2] - segments[:, 1]), kind="stable")       # a wave's lanes finish together
+    scan = np.concatenate(chunks) if chunks else np.zeros(0, np.uint8)
+    tables = np.frombuffer(b"".join(sets), np.uint8).reshape(len(sets), TABLE_SET_BYTES).copy() if sets else np.zeros((0, TABLE_SET_BYTES), np.uint8)
+    return Packed(np.ascontiguousarray(scan), np.ascontiguousarray(segments[order]), images, tables, out_off, int(out_bytes), blocks,
+                  [(p.height, p.width) for p in plans], max([p.n_blocks for p in plans], default=1), max([p.width * p.height for p in plans], default=1), kept)
+
+
+def unpack(packed: Packed, out: np.ndarray) -> List[np.ndarray]:
+    """The images u8 [H, W, 3] of a launch's flat output."""
+    return [out[o:o + 3 * h * w].reshape(h, w, 3) for o, (h, w) in zip(packed.out_off.tolist(), packed.shapes)]
+
+
+def decode_host(packed: Packed):
+    """zh_jpeg_decode_host over a launch's arrays: (images, status int32 [B]).  The CPU twin of zh_jpeg_decode: same codec, same
+    arithmetic, no GPU."""
+    import ctypes as C
+    lib = _lib.load(raw=True)
+    B = len(packed.shapes)
+    out = np.zeros(max(packed.out_bytes, 1), np.uint8)
+    status = np.zeros(max(B, 1), np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    rc = lib.zh_jpeg_decode_host(ptr(packed.scan), packed.scan.size, ptr(packed.segments), len(packed.segments), ptr(packed.images), B,
+                                 ptr(packed.tables), len(packed.tables), packed.n_blocks, ptr(out), packed.out_bytes, ptr(status))
+    _lib.check(rc, "zh_jpeg_decode_host")
+    return unpack(packed, out), status[:B]
+
+
+def check_decoder(name: str, decoder) -> str:
+    if decoder not in DECODERS:
+        raise ValueError(f"{name}: decoder {decoder!r} is not \"host\" or \"device\"")
+    return decoder

@@ -996,6 +996,25 @@ def png_deflate(images, img_off, hw, c, out, out_off, lengths, max_segments, wor
     return lengths
 
 
+def jpeg_decode(scan, segments, images, tables, n_blocks, max_image_blocks, max_image_pixels, out, status, workspace=None):
+    """B baseline JPEG files to interleaved RGB in one call (zh_jpeg_decode; jpeg_device.decode_np byte for byte).  The arrays of
+    jpeg_device.pack on the device: scan u8 [bytes], segments int32 [S, 4], images int32 [B, 12], tables u8 [n_sets, TABLE_SET_BYTES];
+    n_blocks / max_image_blocks / max_image_pixels: the batch's 8 x 8 blocks and its largest image's blocks and pixels (the caller holds
+    the plans on the host); out u8 [bytes]: image b's [h, w, 3] at 16 x its row's offset word; status int32 [B]: 0 or the OR of
+    jpeg_device.STATUS bits (the image is then left to the host).  Everything on the device; nothing is copied.  Returns status."""
+    _chk(scan, torch.uint8, "jpeg_decode scan"); _chk(out, torch.uint8, "jpeg_decode out"); _chk(tables, torch.uint8, "jpeg_decode tables")
+    _chk(segments, torch.int32, "jpeg_decode segments"); _chk(images, torch.int32, "jpeg_decode images"); _chk(status, torch.int32, "jpeg_decode status")
+    B = images.shape[0] if images.dim() == 2 else -1
+    if B < 0 or images.shape[1] != _ZH["ZH_JPEG_IMAGE_WORDS"] or segments.dim() != 2 or segments.shape[1] != _ZH["ZH_JPEG_SEGMENT_WORDS"] or \
+            tables.dim() != 2 or tables.shape[1] != _ZH["ZH_JPEG_TABLE_SET_BYTES"] or status.numel() != B:
+        raise _lib.ZutisHipError("jpeg_decode: segments [S, 4], images [B, 12], tables [n_sets, TABLE_SET_BYTES] and status [B] do not describe one batch")
+    if B:
+        ws, need = _workspace_or(workspace, "jpeg_decode", "zh_jpeg_decode_workspace_size", out.device, B, int(n_blocks))
+        _call("zh_jpeg_decode", _p(scan), scan.numel(), _p(segments), segments.shape[0], _p(images), B, _p(tables), tables.shape[0], int(n_blocks),
+              int(max_image_blocks), int(max_image_pixels), _p(out), out.numel(), _p(status), _p(ws), need, _stream())
+    return status
+
+
 # ---- training criterion (criterion.py::Criterion): zutis_amd/criterion.py
 
 def mask_match_cost(proposals, gt_u8, inst_off, n_max, H, W, costs, stat_p, stat_pg, stat_g, skip, status, weight_dice=1.0, weight_bce=1.0):

@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import picture_out, png_device, preprocess
+from . import jpeg_device, picture_out, png_device, preprocess
 from .evaluate import _require_dropin, collect_instance_predictions
 from .preprocess import MAX_THREADS
 LABEL_LIMIT = {"u8": 256, "rg16": 65536}
@@ -200,7 +200,7 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
                        label_id_to_category: Optional[Dict[int, str]] = None, nms_type: Optional[str] = "hard",
                        predictions_json: Optional[str] = None, instance_map: bool = False, instance_overlay: bool = False,
                        instance_colours="instance", instance_min_score: float = 0.0, instance_outline: bool = True,
-                       png_encoder: str = "host") -> dict:
+                       png_encoder: str = "host", decoder: str = "host") -> dict:
     """The segmenter over a list of image files: label PNGs (and overlays) on disk, and / or the instance predictions.
 
     network: the drop-in ZUTIS (zutis_amd/dropin/networks/zutis.py) on a GPU; its text embeddings are the n categories.
@@ -237,12 +237,17 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     file.  The files decode to the same pixels, mode and palette; label and id maps come out at 1.14 - 1.19 x Pillow's level-1 size,
     photographic overlays at 2.0 x (1.05 of their raw bytes against 0.52; profiles/NOTES.md), which is why "host" is the default.
     compress_level is unused with "device".  Any other value: ValueError before any work.
+    decoder "host": the decoding threads run Pillow.  "device": they read the files and parse the headers; baseline JPEG files cross to
+    the device as their file bytes and are decoded there (zh_jpeg_decode: zutis_amd/jpeg_device.py defines the pixels, byte for byte
+    Pillow's), everything else — and any file whose scan the device reports as damaged — is decoded by Pillow as ever, so the files
+    written do not depend on it.  Any other value: ValueError before any work.
     Returns {"label_paths": [...] | None, "overlay_paths": [...] | None, "instance_predictions": the dicts predict gave (with "bbox"),
     in input-path order, "n_images": int}.
     A missing or unreadable image (FileNotFoundError / OSError / ValueError) and a directory or file that cannot be written (OSError)
     are raised here; no decoding or writing thread outlives the call and the device stays usable."""
     p_images = [os.fspath(p) for p in p_images]
     on_device = png_device.check_encoder("predict_from_files", png_encoder) == "device"
+    jpeg_device.check_decoder("predict_from_files", decoder)
     _require_dropin(network, "predict_from_files")
     n = int(network.text_embeddings.shape[0])
     pal = _validate(n, len(p_images), semantic, instance, label_format, palette, overlay, alpha, image_ids, compress_level)
@@ -270,7 +275,7 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
         lut = torch.from_numpy(preprocess.normalise_table(mean, std)).to(dev)
         pal_dev = torch.from_numpy(pal).to(dev) if (overlay and pal is not None) else None
         colour_dev = torch.from_numpy(colour_table).to(dev) if colour_table is not None else None
-        loader = preprocess.PredictBatchLoader(p_images, max_size, batch_size, n_decode, window=window)
+        loader = preprocess.PredictBatchLoader(p_images, max_size, batch_size, n_decode, window=window, decoder=decoder)
         # name -> (paths, (c, mode, palette bytes)) of the kinds of picture the call writes, in layout order; the id map's once Q is known
         kinds = {name: kind for name, kind in (("labels", (label_paths, (ch, mode, pal_bytes))), ("overlay", (overlay_paths, (3, "RGB", None))),
                                                ("ids", (map_paths, None)), ("instance_overlay", (iovl_paths, (3, "RGB", None)))) if kind[0] is not None}

@@ -38,7 +38,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import _lib
+from . import _lib, jpeg_device
 
 PRECISION_BITS = 32 - 8 - 2     # Pillow's fixed-point coefficients: src/libImaging/Resample.c
 KMAX = _lib.constants()["ZH_RCN_KMAX"]      # taps per output pixel the kernel serves
@@ -146,8 +146,8 @@ def device_supported(w: int, h: int, n_px: int) -> bool:
     return nw > 0 and nh > 0 and _taps_ok(w, h, nw, nh)
 
 
-Batch = collections.namedtuple("Batch", "paths indices sizes_hw size_hw out_hw staging packed desc kmax n_host host_paths gt_paths gt packed_bytes",
-                               defaults=(None,) * 14)
+Batch = collections.namedtuple("Batch", "paths indices sizes_hw size_hw out_hw staging packed desc kmax n_host host_paths gt_paths gt packed_bytes "
+                               "jpeg n_host_decoded host_decoded_paths", defaults=(None,) * 17)
 Batch.__doc__ = """One decoded batch of any loader; a field that does not apply is None.  paths: its files; staging: u8 tensor [32 * B +
 packed_bytes (+ ground-truth bytes)] (pinned when the loader pins), descriptor rows first — one host-to-device copy moves all of it;
 packed / desc: its first two views (u8 [packed_bytes], int32 [B, 8]), offsets relative to `packed`; kmax: the batch's largest tap count;
@@ -155,7 +155,18 @@ n_host / host_paths: the images that were resized on the host (outside device_su
 ShapeBucketLoader adds indices: the files' positions in the loader's path list; sizes_hw: the files' own (H, W); out_hw: the (out_h,
 out_w) every image of the batch resizes to; size_hw: the (H, W) every file has, when the file size is part of the bucket key;
 gt_paths / gt: the ground-truth files and the host view u8 [B, H, W] ("u8") or [B, H, W, 3] ("rg16") of the staging buffer's tail.
+With decoder="device" the staging buffer holds file bytes, not pixels: descriptor rows, then jpeg.staged_bytes bytes — the arrays of one
+zh_jpeg_decode launch (jpeg_device.pack) and, behind them, the pixels of the images the host decoded (n_host_decoded /
+host_decoded_paths: files jpeg_device.parse does not serve, images resized on the host, table sets past a launch's limit) — then the
+ground truth; `packed` is None, packed_bytes and desc still describe the decoded images at the offsets they have on the device once
+device_batches has run the decoder (jpeg: a JpegStage).
 Valid until the loader is advanced."""
+
+JpegStage = collections.namedtuple("JpegStage", "staged_bytes images segments tables scan n_blocks max_image_blocks max_image_pixels kept host")
+JpegStage.__doc__ = """Where the file bytes of a decoder="device" batch lie in its staging buffer, offsets counted from the end of the
+descriptor rows: images / segments / tables / scan = (offset, bytes) of the arrays of jpeg_device.pack; n_blocks, max_image_blocks,
+max_image_pixels: its launch sizes; kept: the batch positions of the images the launch decodes, in the order of its rows; host:
+(batch position, offset of its pixels in the staged bytes, bytes, offset of its slot in the decoded images) of every host-decoded image."""
 
 
 class DoubleBuffer:
@@ -221,14 +232,16 @@ class BatchLoader:
     raised by the iteration step that needs the batch, at the latest.
     The caller must be done reading a batch (its host-to-device copy complete) before it advances the loader."""
 
-    def __init__(self, paths: Sequence[str], n_px: int, batch_size: int, n_workers: int, box: Callable, pin=None):
+    def __init__(self, paths: Sequence[str], n_px: int, batch_size: int, n_workers: int, box: Callable, pin=None, decoder: str = "host"):
         if batch_size < 1 or n_px < 1:
             raise ValueError("BatchLoader: batch_size and n_px must be positive")
+        self.decoder = jpeg_device.check_decoder(type(self).__name__, decoder)
         self.paths, self.n_px, self.batch_size, self.box = list(paths), int(n_px), int(batch_size), box
         self.n_threads = max(1, min(int(n_workers), MAX_THREADS))
         self.pin = torch.cuda.is_available() if pin is None else bool(pin)
         self.filter = "bicubic"
         self._staging = DoubleBuffer(self.pin)
+        self._files = {}                # decoder="device": slot -> what _read gave for the batch being laid out, when _start read it
 
     def __len__(self):
         return (len(self.paths) + self.batch_size - 1) // self.batch_size
@@ -246,6 +259,51 @@ class BatchLoader:
             (nw, nh), (left, top) = host_box
             im = im.resize((nw, nh), FILTERS[self.filter][2]).crop((left, top, left + out_wh[0], top + out_wh[1]))
         np.copyto(dst, np.asarray(im))
+
+    def _read(self, path: str):
+        """decoder="device": the file's bytes and its plan — (data, plan, (w, h)); (None, None, (w, h)) from the header as Pillow reads
+        it for a file the device decoder does not serve."""
+        data = np.fromfile(path, np.uint8)
+        plan = jpeg_device.parse(data)
+        if plan is None:
+            return None, None, self._size(path)
+        return data, plan, (plan.width, plan.height)
+
+    def _pack_files(self, pool: ThreadPoolExecutor, slot: int, chunk, sizes, host_boxes, shapes, rows, kmax, off, out_wh, extra: int):
+        """_pack for decoder="device": the staging buffer gets the descriptor rows, the arrays of one zh_jpeg_decode launch over the files
+        the device serves and, compacted behind them, room for the pixels of the others, which Pillow decodes in the pool as ever."""
+        B = len(chunk)
+        files = self._files.pop(slot, None) or list(pool.map(self._read, chunk))
+        for p, size, (_, _, wh) in zip(chunk, sizes, files):
+            if wh != tuple(size):
+                raise ValueError(f"{p}: size {wh} differs from its header's {tuple(size)}")
+        want = [i for i in range(B) if files[i][1] is not None and host_boxes[i] is None]
+        jp = jpeg_device.pack([files[i][1] for i in want], [files[i][0] for i in want], out_off=[shapes[i][0] for i in want], out_bytes=off,
+                              skip_overflow=True)
+        kept = [want[k] for k in jp.kept]
+        arrays = [np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in (jp.images, jp.segments, jp.tables, jp.scan)]
+        at, places = 0, []
+        for a in arrays:
+            places.append((at, a.size))
+            at += -(-a.size // ALIGN) * ALIGN
+        host = []
+        for i in sorted(set(range(B)) - set(kept)):
+            o, h, w = shapes[i]
+            host.append((i, at, 3 * w * h, o))
+            at += -(-3 * w * h // ALIGN) * ALIGN
+        head = B * DESC_INTS * 4
+        staging = self._staging.take(slot, head + at + extra)
+        desc = staging[:head].view(torch.int32).view(B, DESC_INTS)
+        desc.numpy()[...] = rows
+        pay = staging[head:head + at].numpy()
+        for (o, n), a in zip(places, arrays):
+            pay[o:o + n] = a
+        futures = [pool.submit(self._decode, chunk[i], pay[o:o + n].reshape(shapes[i][1], shapes[i][2], 3), sizes[i], host_boxes[i], out_wh)
+                   for i, o, n, _ in host]
+        stage = JpegStage(at, *places, jp.n_blocks, jp.max_image_blocks, jp.max_image_pixels, kept, host)
+        resized = [p for p, hb in zip(chunk, host_boxes) if hb is not None]
+        return Batch(paths=chunk, staging=staging, desc=desc, kmax=kmax, n_host=len(resized), host_paths=resized, packed_bytes=off, jpeg=stage,
+                     n_host_decoded=len(host), host_decoded_paths=[chunk[i] for i, _, _, _ in host]), futures
 
     def _pack(self, pool: ThreadPoolExecutor, slot: int, chunk, sizes, boxes, out_wh, extra: int = 0):
         """Lay `chunk` (files of `sizes` = (w, h), resized and cropped as `boxes` = ((nw, nh), (left, top)) say, to out_wh = (w, h) of the
@@ -266,6 +324,8 @@ class BatchLoader:
             rows[i] = (off // ALIGN, w, h, nw, nh, left, top, 0)
             shapes.append((off, h, w))
             off += -(-3 * w * h // ALIGN) * ALIGN
+        if self.decoder == "device":
+            return self._pack_files(pool, slot, chunk, sizes, host_boxes, shapes, rows, kmax, off, out_wh, extra)
         head = B * DESC_INTS * 4
         staging = self._staging.take(slot, head + off + extra)
         packed, desc = split_staging(staging[:head + off], B)
@@ -279,7 +339,11 @@ class BatchLoader:
     def _start(self, pool: ThreadPoolExecutor, slot: int, k: int):
         """Fix batch k's layout from the headers and start its decodes: (Batch, futures)."""
         chunk = self.paths[k * self.batch_size:(k + 1) * self.batch_size]
-        sizes = list(pool.map(self._size, chunk))
+        if self.decoder == "device":    # one read serves the header and the decoder
+            self._files[slot] = list(pool.map(self._read, chunk))
+            sizes = [wh for _, _, wh in self._files[slot]]
+        else:
+            sizes = list(pool.map(self._size, chunk))
         n = self.n_px
         return self._pack(pool, slot, chunk, sizes, [self.box(w, h, n) for w, h in sizes], (n, n))
 
@@ -352,12 +416,12 @@ class ShapeBucketLoader(BatchLoader):
     of another mode, or of another size than its image, raises ValueError naming the file."""
 
     def __init__(self, paths: Sequence[str], image_size, batch_size: int, n_workers: int, window: int = 512, filter: str = "bilinear", pin=None, *,
-                 size_rule: Callable = mask_dataset_size, by_file_size: bool = False, gt_paths=None, gt_format: str = "u8"):
+                 size_rule: Callable = mask_dataset_size, by_file_size: bool = False, gt_paths=None, gt_format: str = "u8", decoder: str = "host"):
         if image_size is not None and image_size < 1:
             raise ValueError("ShapeBucketLoader: image_size must be positive or None")
         if window < 1 or filter not in FILTERS:
             raise ValueError(f"ShapeBucketLoader: window must be positive and filter one of {sorted(FILTERS)}")
-        super().__init__(paths, 1, batch_size, n_workers, None, pin)
+        super().__init__(paths, 1, batch_size, n_workers, None, pin, decoder)
         self.image_size, self.window, self.filter = image_size, int(window), filter
         self.size_rule, self.by_file_size = size_rule, bool(by_file_size)
         self.gt_paths, self.gt_format = None if gt_paths is None else list(gt_paths), gt_format
@@ -408,7 +472,7 @@ class ShapeBucketLoader(BatchLoader):
         batch = batch._replace(indices=idx, sizes_hw=[(h_, w_) for w_, h_ in sizes], out_hw=(nh, nw), size_hw=(h, w) if self.by_file_size else None)
         if ch:
             gts = [self.gt_paths[i] for i in idx]
-            gt = batch.staging[B * DESC_INTS * 4 + batch.packed_bytes:].view((B, h, w) if ch == 1 else (B, h, w, ch))
+            gt = batch.staging[B * DESC_INTS * 4 + (batch.packed_bytes if batch.jpeg is None else batch.jpeg.staged_bytes):].view((B, h, w) if ch == 1 else (B, h, w, ch))
             gt_np = gt.numpy()
             futures += [pool.submit(self._decode_gt, p, gt_np[b]) for b, p in enumerate(gts)]
             batch = batch._replace(gt_paths=gts, gt=gt)
@@ -438,13 +502,13 @@ class EvalBatchLoader(ShapeBucketLoader):
     edge (longer_edge_size, imagenet_s.py:71-76), Pillow BILINEAR.  gt_format as ShapeBucketLoader's."""
 
     def __init__(self, paths: Sequence[str], gt_paths: Sequence[str], max_size, batch_size: int, n_workers: int, window: int = 512,
-                 gt_format: str = "u8", pin=None):
+                 gt_format: str = "u8", pin=None, decoder: str = "host"):
         if gt_format not in GT_MODES:
             raise ValueError(f"EvalBatchLoader: gt_format {gt_format!r} is not one of {sorted(GT_MODES)}")
         if len(paths) != len(gt_paths):
             raise ValueError("EvalBatchLoader: one ground-truth file per image")
         super().__init__(paths, max_size, batch_size, n_workers, window=window, filter="bilinear", pin=pin, size_rule=longer_edge_size,
-                         by_file_size=True, gt_paths=gt_paths, gt_format=gt_format)
+                         by_file_size=True, gt_paths=gt_paths, gt_format=gt_format, decoder=decoder)
 
 
 class PredictBatchLoader(ShapeBucketLoader):
@@ -452,9 +516,9 @@ class PredictBatchLoader(ShapeBucketLoader):
     shares the file size as well as the resized shape.  It groups by the very key evaluation groups by, eval_bucket_key(w, h, w, h,
     max_size): for one path list, batch_size and window its batches are EvalBatchLoader's.  max_size as there."""
 
-    def __init__(self, paths: Sequence[str], max_size, batch_size: int, n_workers: int, window: int = 512, pin=None):
+    def __init__(self, paths: Sequence[str], max_size, batch_size: int, n_workers: int, window: int = 512, pin=None, decoder: str = "host"):
         super().__init__(paths, max_size, batch_size, n_workers, window=window, filter="bilinear", pin=pin, size_rule=longer_edge_size,
-                         by_file_size=True)
+                         by_file_size=True, decoder=decoder)
 
 
 # ------------------------------------------------------------------------------------------------- the device side of a driver
@@ -470,6 +534,42 @@ def resize_normalize_of(lut: torch.Tensor):
     return transform
 
 
+def decode_staged(batch: Batch, staged: torch.Tensor, full: torch.Tensor) -> torch.Tensor:
+    """The device side of decoder="device": `staged` is the batch's staging buffer on the device (descriptor rows, file bytes, host-decoded
+    pixels, ground truth); `full` receives what a host-decoded staging buffer would hold there — the rows, every image's RGB bytes at its
+    row's offset, the ground truth — and is returned.  One zh_jpeg_decode launch sequence (ops.jpeg_decode) writes the served images
+    straight into their slots, the host-decoded ones are copied into theirs on the device.  The status array is read once, here: the
+    read waits for the batch's upload and its decode (the wait device_batches makes behind the driver's body then returns at once).  An
+    image with a non-zero status is decoded by Pillow on the calling thread and written over its slot before anything reads it; whatever
+    Pillow raises for it is raised here."""
+    from . import ops
+    B, j = len(batch.paths), batch.jpeg
+    head = B * DESC_INTS * 4
+    full[:head].copy_(staged[:head])
+    if staged.numel() > head + j.staged_bytes:
+        full[head + batch.packed_bytes:].copy_(staged[head + j.staged_bytes:])
+    pay, rgb = staged[head:head + j.staged_bytes], full[head:head + batch.packed_bytes]
+    status = None
+    if j.kept:
+        part = lambda place, dtype, cols: pay[place[0]:place[0] + place[1]].view(dtype).view(-1, cols)      # noqa: E731
+        status = torch.empty(len(j.kept), dtype=torch.int32, device=staged.device)
+        ops.jpeg_decode(pay[j.scan[0]:j.scan[0] + j.scan[1]], part(j.segments, torch.int32, jpeg_device.SEGMENT_WORDS),
+                        part(j.images, torch.int32, jpeg_device.IMAGE_WORDS), part(j.tables, torch.uint8, jpeg_device.TABLE_SET_BYTES),
+                        j.n_blocks, j.max_image_blocks, j.max_image_pixels, rgb, status)
+    for _, at, n, slot in j.host:
+        rgb[slot:slot + n].copy_(pay[at:at + n])
+    if status is not None:
+        rows = batch.desc.numpy()
+        for k in np.flatnonzero(status.cpu().numpy()).tolist():
+            i = j.kept[k]
+            a = np.array(Image.open(batch.paths[i]).convert("RGB"))
+            o, w, h = int(rows[i, 0]) * ALIGN, int(rows[i, 1]), int(rows[i, 2])
+            if a.shape != (h, w, 3):
+                raise ValueError(f"{batch.paths[i]}: decoded size {a.shape[1::-1]} differs from its header's {(w, h)}")
+            rgb[o:o + 3 * w * h].copy_(torch.from_numpy(np.ascontiguousarray(a)).reshape(-1))
+    return full
+
+
 @contextlib.contextmanager
 def device_batches(loader, dev, transform: Callable):
     """The device loop every driver shares, `dev` the current device inside: `with device_batches(...) as steps: for batch, views, x in
@@ -480,11 +580,14 @@ def device_batches(loader, dev, transform: Callable):
     go) and the loader's generator closed (a failure outside the loader: its threads end here)."""
     copied = torch.cuda.Event()
     batches = iter(loader)
+    decoded = DoubleBuffer(False, dev)          # decoder="device": the decoded batches, at the layout a host-decoded staging buffer has
 
     def steps():
-        for batch in batches:
+        for k, batch in enumerate(batches):
             staged = batch.staging.to(dev, non_blocking=True)
             copied.record()
+            if getattr(batch, "jpeg", None) is not None:          # (synth.TrainBatch has no such field: its loader decodes on the host)
+                staged = decode_staged(batch, staged, decoded.take(k & 1, staged.numel() - batch.jpeg.staged_bytes + batch.packed_bytes))
             yield (batch, *transform(batch, staged))
             copied.synchronize()
 

@@ -156,7 +156,7 @@ def _write_masks(event, host: np.ndarray, items):
 @torch.no_grad()
 def generate_pseudo_masks_from_files(engine: SelfMaskEngine, p_images: Sequence[str], out_paths: Sequence[str], *, image_size: Optional[int] = 512,
                                      mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), bilateral_solver: bool = True,
-                                     batch_size: int = 8, n_workers: int = 16, window: int = 512) -> List[str]:
+                                     batch_size: int = 8, n_workers: int = 16, window: int = 512, decoder: str = "host") -> List[str]:
     """IndexDataset.generate_pseudo_masks (datasets/index_dataset.py:177-226) from a list of image files to the RLE JSON files
     `out_paths`, MaskDataset's transform (:405-411) included, over the file pipeline of preprocess.py.  Threads decode into pinned
     staging one batch ahead (ShapeBucketLoader: batches of ONE resized shape out of a window of `window` paths, so SelfMask and the
@@ -175,7 +175,7 @@ def generate_pseudo_masks_from_files(engine: SelfMaskEngine, p_images: Sequence[
     dev = engine._device()
     n_decode, n_writers = preprocess.thread_split(n_workers, 0.25)
     lut = torch.from_numpy(preprocess.normalise_table(mean, std)).to(dev)
-    loader = preprocess.ShapeBucketLoader(p_images, image_size, batch_size, n_decode, window=window, filter="bilinear")
+    loader = preprocess.ShapeBucketLoader(p_images, image_size, batch_size, n_decode, window=window, filter="bilinear", decoder=decoder)
     with preprocess.WriterRing(loader.pin, n_writers, "zutis-rle", device=dev) as ring, \
             preprocess.device_batches(loader, dev, preprocess.resize_normalize_of(lut)) as steps:
         for k, (batch, _, x) in enumerate(steps):
