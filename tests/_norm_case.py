@@ -223,7 +223,7 @@ def _lane_sum(v, m):
 
 
 def ln_rows_f32(x, g, b, eps, h8=False, wrong=None):
-    """ln_normalize / ln_normalize_h8 + affine in float32: two-pass mean, centred biased variance, rsqrt(var + eps).  wrong in
+    """ln_normalize (either row layout) + affine in float32: two-pass mean, centred biased variance, rsqrt(var + eps).  wrong in
     {None, "one_pass", "mean_fp16", "drop_last_float4"}: E[x^2] - mean^2; the mean taken from the fp16-rounded row; the last float4 of the
     row left out of both sums.  Returns float32 [rows, D]."""
     x = np.ascontiguousarray(x.numpy() if isinstance(x, torch.Tensor) else x, np.float32)

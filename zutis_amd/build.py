@@ -18,7 +18,8 @@ EXTRA_FLAGS = {"bilateral.hip": ["-ffp-contract=off"], "preprocess.hip": ["-ffp-
                "synth.hip": ["-ffp-contract=off"],   # synth.hip: Pillow's blend and HSV arithmetic, one IEEE operation at a time
                "polygon.hip": ["-ffp-contract=off"]}  # polygon.hip: rleFrPoly's double arithmetic, bit-compared with the host's
 # the MFMA kernels live at the register budget of their occupancy: a spill is a 2-3x slowdown, so it is a build error
-NO_SCRATCH = {"gemm.hip", "gemm_x3.hip", "attention.hip", "preprocess.hip", "synth.hip", "resample.hip", "label_paint.hip", "png.hip"}
+# (norm.hip: the row kernels keep a whole row in registers between the two moments and are launched more often than anything but the GEMMs)
+NO_SCRATCH = {"gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "preprocess.hip", "synth.hip", "resample.hip", "label_paint.hip", "png.hip"}
 MAX_SCRATCH = int(os.environ.get("ZH_BUILD_MAX_SCRATCH", "0"))    # bytes per lane tolerated: the MFMA loops must not spill (developer builds may raise it)
 # waves per SIMD the design of a kernel relies on (source -> mangled-name substring -> minimum), checked against the compiler's
 # remarks; a key that matches no kernel of its source is a build error (a renamed template would otherwise drop its guard)
@@ -29,7 +30,13 @@ MIN_OCCUPANCY = {"attention.hip": {"attn_f16_kernelILi64ELi4ELi1ELi0EE": 3, "att
                                    "attn_f16_kernelILi128ELi4ELi0ELi0EE": 2, "attn_f16_kernelILi128ELi4ELi1ELi0EE": 2},
                  # the byte epilogue (zh_upsample_argmax_bytes) must not cost the arg-max kernels the occupancy of their int64 form (UaStore)
                  "resample.hip": {"upsample_argmax_pk_kernelI7UaBytes": 3, "upsample_argmax_lds_kernelI7UaBytes": 6,
-                                  "upsample_argmax_kernelI7UaBytes": 8}}
+                                  "upsample_argmax_kernelI7UaBytes": 8},
+                 # the HBM-bound row kernels hide their load latency by occupancy; the split-K forms hold NPARTS planes of the row at once
+                 # (one plane fits 8 waves only while its four loads are issued back to back: 59 VGPRs of the 64 that 8 waves allow)
+                 "norm.hip": {"layernorm_kernelI6RowF32E": 8, "layernorm_kernelI6RowF16E": 8,
+                              "sum_layernorm_kernelILi0EE": 8, "sum_layernorm_kernelILi1EE": 8, "sum_layernorm_kernelILi2EE": 6,
+                              "sum_layernorm_kernelILi4EE": 4, "assemble_ln_kernelIfE": 8, "assemble_ln_kernelIDF16_E": 8,
+                              "l2norm_rows_kernel": 8, "gln_partial_kernel": 8, "gln_apply_kernel": 8}}
 SOURCES = ["capi.hip", "rle_host.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "mask_rle.hip", "instance_paint.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "assign.hip", "cocoeval.hip", "polygon.hip", "label_paint.hip", "png.hip", "jpeg_host.hip", "jpeg.hip", "synth.hip", "plan.hip"]
 
 

@@ -297,13 +297,17 @@ STATUS_RANGE, STATUS_NONFINITE, STATUS_LABEL = _ZH["ZH_STATUS_RANGE"], _ZH["ZH_S
 UNIT_NORM_SCALE = 1024.0                     # f16_scale of the unit-norm producers (2^10): see zutis_hip.h
 
 
+def _group_map(rows, group_rows, group_stride):
+    """Defaults of a row-group mapping (zutis_hip.h): one group of all `rows`, groups packed back to back."""
+    group_rows = rows if group_rows is None else group_rows
+    return group_rows, group_rows if group_stride is None else group_stride
+
+
 def layernorm(x, gamma, beta, eps, rows, D, *, out_f32=None, out_f16=None, out_f16_plus=None, out_f32_plus=None,
               add=None, add_rows=0, in_group_rows=None, in_group_stride=None, in_offset=0,
               out_group_rows=None, out_group_stride=None, out_offset=0, status=None):
-    in_group_rows = rows if in_group_rows is None else in_group_rows
-    in_group_stride = in_group_rows if in_group_stride is None else in_group_stride
-    out_group_rows = rows if out_group_rows is None else out_group_rows
-    out_group_stride = out_group_rows if out_group_stride is None else out_group_stride
+    in_group_rows, in_group_stride = _group_map(rows, in_group_rows, in_group_stride)
+    out_group_rows, out_group_stride = _group_map(rows, out_group_rows, out_group_stride)
     (out_f16, p1), (out_f16_plus, p2) = _hp(out_f16), _hp(out_f16_plus)
     if out_f16 is not None and out_f16_plus is not None and p1 != p2:
         raise _lib.ZutisHipError("layernorm: both fp16 outputs must be split pairs of the same shape, or both plain")
@@ -322,10 +326,8 @@ def sum_layernorm(parts, n_parts, rows, D, *, part_stride=None, bias=None, resid
     """x = sum of the n_parts fp32 planes of `parts` + bias + residual -> out_sum; LN(x) -> out_f32 / out_f16 (row-mapped); LN(LN(x)) with
     gamma2 / beta2 -> out2_* (zh_sum_layernorm_f32).  n_parts = 1 with no bias / residual is a plain (or chained) LayerNorm."""
     part_stride = rows * D if part_stride is None else part_stride
-    ogr = rows if out_group_rows is None else out_group_rows
-    ogs = ogr if out_group_stride is None else out_group_stride
-    ogr2 = rows if out2_group_rows is None else out2_group_rows
-    ogs2 = ogr2 if out2_group_stride is None else out2_group_stride
+    ogr, ogs = _group_map(rows, out_group_rows, out_group_stride)
+    ogr2, ogs2 = _group_map(rows, out2_group_rows, out2_group_stride)
     (out_f16, lo1), (out2_f16, lo2) = _hp(out_f16), _hp(out2_f16)
     _call("zh_sum_layernorm_f32", _p(parts), n_parts, part_stride, _p(bias), _p(residual), _p(out_sum), _p(gamma), _p(beta), float(eps),
           _p(out_f32), _p(out_f16), lo1, ogr, ogs, out_offset, int(skip_first_in_group),
