@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 243 /* 243: zh_jpeg_decode / zh_jpeg_decode_host (the device JPEG decoder: baseline files reach the GPU as file bytes, ZH_JPEG_*); 242: the attention entries take head_dim 128 (a behaviour change: a stale build would refuse the ViT-L decoder); 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 244 /* 244: zh_jpeg_decode_split / zh_jpeg_decode_split_host (a scan without restart markers split among lanes, ZH_JPEG_CHUNK_*, ZH_JPEG_SPLIT_*, ZH_JPEG_STATUS_UNSYNCED); 243: zh_jpeg_decode / zh_jpeg_decode_host (the device JPEG decoder: baseline files reach the GPU as file bytes, ZH_JPEG_*); 242: the attention entries take head_dim 128 (a behaviour change: a stale build would refuse the ViT-L decoder); 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -695,6 +695,42 @@ int zh_jpeg_decode(const unsigned char* scan, long scan_bytes, const int* segmen
                    const unsigned char* tables, int n_sets, long n_blocks, long max_image_blocks, long max_image_pixels,
                    unsigned char* out, long out_bytes, int* status, void* workspace, size_t workspace_bytes, zh_stream_t stream);
 
+/* zh_jpeg_decode with the entropy stage of every segment split among lanes (self-synchronising Huffman decoding, made exact by a
+ * verifying pass): a file without restart markers is ONE segment, which zh_jpeg_decode gives to one lane.  Arguments and results as
+ * zh_jpeg_decode, and:
+ * chunks int32 [n_chunks, ZH_JPEG_CHUNK_WORDS] = {segment row, first byte, unstuffed bits of the segment in front of it, 1 for the
+ *   first chunk of its segment}: every segment [lo, hi) cut every chunk_bytes bytes (a cut that falls on the 00 of an FF 00 pair moves
+ *   behind it), the chunks of a segment in order and next to each other, the segments in the order of their rows; a segment without
+ *   bytes has one chunk (jpeg_device.chunk_rows).  chunk_bytes: a multiple of 16 in ZH_JPEG_CHUNK_BYTES_MIN .. 4096
+ *   (ZH_JPEG_CHUNK_BYTES is what the loaders stage); n_chunks <= ZH_JPEG_MAX_CHUNKS.
+ * Launches: `passes` (1 .. 64; ZH_JPEG_SPLIT_PASSES by default) of the lenient synchronising kernel — one workgroup per sequence of
+ *   ZH_JPEG_SPLIT_LANES chunk rows; lane i decodes the symbols that start in its chunk from the state (bit, block in MCU, coefficient
+ *   index) lane i - 1 hands it, until no state changes; a sequence's first lane takes the last state of the sequence before it from
+ *   the launch before; a decoder that cannot fail: an undefined code skips a bit, an index past 63 ends the block, a category is
+ *   clamped —, a segmented scan of the blocks every chunk completes (two launches), the strict pass (one lane per chunk, the rules of
+ *   zh_jpeg_decode, DC values as differences) and the DC sums per segment and component; then the pixel stage of zh_jpeg_decode.
+ * The strict pass compares the state it ends in with the state the next chunk started from and the blocks it completed with the
+ *   count the scan used: a difference sets ZH_JPEG_STATUS_UNSYNCED.  The first chunk of a segment starts from the true state, so an
+ *   image without that bit (and without an error bit) was decoded from true states throughout: its pixels are zh_jpeg_decode's.
+ *   passes >= the sequences of the longest segment always suffices.  A chunk row that does not fit — outside its segment, not behind
+ *   its predecessor, longer than chunk_bytes + 1, an unstuffed count that is not the count of its predecessor's bytes — gives its
+ *   image DESCRIPTOR; a row whose segment or image cannot be told is ignored (the image then stays INCOMPLETE).
+ * Every loop is bounded by the bits of a chunk or by ZH_JPEG_SPLIT_LANES; nothing outside out, status and the workspace is written.
+ * workspace >= zh_jpeg_decode_split_workspace_size bytes, 16-byte aligned: that of zh_jpeg_decode, then per chunk the state it
+ *   starts from and ends in, its block count and first block, per sequence two hand-over states, its open block sum and carry. */
+#define ZH_JPEG_CHUNK_WORDS 4
+#define ZH_JPEG_CHUNK_BYTES 128
+#define ZH_JPEG_CHUNK_BYTES_MIN 16
+#define ZH_JPEG_SPLIT_LANES 256
+#define ZH_JPEG_SPLIT_PASSES 2
+#define ZH_JPEG_MAX_CHUNKS 4194304
+#define ZH_JPEG_STATUS_UNSYNCED 256  /* split decoding: a chunk did not start from the state its predecessor ended in */
+size_t zh_jpeg_decode_split_workspace_size(int B, long n_blocks, long n_chunks);
+int zh_jpeg_decode_split(const unsigned char* scan, long scan_bytes, const int* segments, int n_segments, const int* chunks, long n_chunks,
+                         int chunk_bytes, int passes, const int* images, int B, const unsigned char* tables, int n_sets, long n_blocks,
+                         long max_image_blocks, long max_image_pixels, unsigned char* out, long out_bytes, int* status, void* workspace,
+                         size_t workspace_bytes, zh_stream_t stream);
+
 /* Native launch plans (zutis_amd/plan.py): replay n recorded calls of the entry points above (op id + 32 argument words
  * each; dispatcher generated from this header) in one C loop; zh_plan_run2 alternates two plans on two streams. */
 int zh_plan_run(const void* cmds, int n, zh_stream_t stream);
@@ -755,6 +791,10 @@ long zh_rle_encode_host(const unsigned char* mask, int H, int W, char* out, long
  * arithmetic on the CPU, for the CPU tests and the host sanitizer program (tools/host/jpeg_host_check.cpp).  Arguments as there. */
 int zh_jpeg_decode_host(const unsigned char* scan, long scan_bytes, const int* segments, int n_segments, const int* images, int B,
                         const unsigned char* tables, int n_sets, long n_blocks, unsigned char* out, long out_bytes, int* status);
+/* HOST twin of zh_jpeg_decode_split: the same passes over the same rows with the same functions of csrc/jpeg_codec.h, lanes as loops. */
+int zh_jpeg_decode_split_host(const unsigned char* scan, long scan_bytes, const int* segments, int n_segments, const int* chunks, long n_chunks,
+                              int chunk_bytes, int passes, const int* images, int B, const unsigned char* tables, int n_sets, long n_blocks,
+                              unsigned char* out, long out_bytes, int* status);
 
 #ifdef __cplusplus
 }

@@ -287,3 +287,183 @@ JPEG_HD void jpeg_pixel(const JpegImage& im, const unsigned char* planes, int x,
   rgb[1] = jpeg_clamp8(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16)); // F(0.34414), F(0.71414)
   rgb[2] = jpeg_clamp8(Y + ((116130 * cb + 32768) >> 16));              // F(1.772)
 }
+
+// ---- a segment split among lanes (zh_jpeg_decode_split: include/zutis_hip.h has the method)
+//   jpeg_chunk          a chunk row, checked against its segment, the row in front of it and the row behind it
+//   jpeg_chunk_pairs    the FF 00 pairs of a chunk's bytes: what the unstuffed count of the NEXT row is checked with
+//   jpeg_chunk_lenient  the symbols that start in a chunk, from any state, under rules that cannot fail: no status, nothing written
+//   jpeg_chunk_strict   the same symbols under jpeg_step's rules: coefficients (DC as differences), status bits, the hand-over check
+//   jpeg_dc_add         the wrapping DC sum
+// A position is an unstuffed bit offset inside the segment; every loop is bounded by the bits of a chunk.
+struct JpegLaunch {
+  const unsigned char* scan;
+  long scan_bytes;
+  const int* segments;
+  int n_segments;
+  const int* chunks;
+  long n_chunks;
+  int chunk_bytes;
+  const int* images;
+  int B, n_sets;
+  long n_blocks, out_bytes, max_image_blocks, max_image_pixels;
+};
+
+struct JpegState {
+  int pos, bk;                 // the bit the next symbol starts at; block inside the MCU << 8 | coefficient index
+};
+JPEG_HD bool jpeg_state_equal(const JpegState& a, const JpegState& b) { return a.pos == b.pos && a.bk == b.bk; }
+
+struct JpegChunk {
+  int seg;                     // its segment row
+  long start, end;             // its bytes [start, end) of the scan
+  int ubits, uend;             // the unstuffed bits of the segment in front of it and in front of the next chunk (last: an upper bound)
+  bool first, last;
+};
+
+#define JPEG_BLOCK_SUM_MAX (1 << 29)      // block counts are added saturating (a damaged scan may count anything): still associative
+JPEG_HD int jpeg_block_sum(int a, int b) { return a + b > JPEG_BLOCK_SUM_MAX ? JPEG_BLOCK_SUM_MAX : a + b; }
+
+JPEG_HD JpegImage jpeg_launch_image(const JpegLaunch& L, int b) {
+  JpegImage im = jpeg_image(L.images + (long)b * ZH_JPEG_IMAGE_WORDS, L.n_sets, L.n_blocks, L.out_bytes);
+  if (im.ok && (im.nblocks > L.max_image_blocks || (long)im.w * im.h > L.max_image_pixels)) im.ok = false;
+  return im;
+}
+
+// Chunk row i.  0: it fits (c, im, s, *b are its chunk, image, segment and image index); -1: its segment or image cannot be told or
+// fails its own check (whoever owns that row reports it); 1: the row does not fit — image *b gets DESCRIPTOR.
+JPEG_HD int jpeg_chunk(const JpegLaunch& L, long i, JpegChunk& c, JpegImage& im, JpegSegment& s, int* b) {
+  const int* r = L.chunks + i * ZH_JPEG_CHUNK_WORDS;
+  c.seg = r[0];
+  if (c.seg < 0 || c.seg >= L.n_segments) return -1;
+  const int* srow = L.segments + (long)c.seg * ZH_JPEG_SEGMENT_WORDS;
+  *b = srow[0];
+  if (*b < 0 || *b >= L.B) return -1;
+  im = jpeg_launch_image(L, *b);
+  if (!im.ok) return -1;
+  int st;
+  if (!jpeg_segment(srow, im, L.scan, L.scan_bytes, s, &st)) return -1;
+  const long lo = s.bits.pos, hi = s.bits.end;
+  c.start = r[1]; c.ubits = r[2];
+  c.end = hi; c.uend = 0; c.last = true;
+  c.first = r[3] == 1;
+  if ((r[3] != 0 && r[3] != 1) || hi - lo >= (1L << 28) || c.start < lo || c.start > hi) return 1;
+  if (c.first) {
+    if (c.start != lo || c.ubits != 0) return 1;
+  } else {
+    if (i == 0) return 1;
+    const int* p = r - ZH_JPEG_CHUNK_WORDS;
+    if (p[0] != c.seg || p[1] < lo || p[1] >= c.start || c.start - p[1] > L.chunk_bytes + 1) return 1;
+    if (c.ubits < 0 || c.ubits > 8 * (c.start - lo) || (c.ubits & 7)) return 1;
+  }
+  if (i + 1 < L.n_chunks) {
+    const int* q = r + ZH_JPEG_CHUNK_WORDS;
+    if (q[0] == c.seg && q[3] == 0) { c.last = false; c.end = q[1]; c.uend = q[2]; }
+  }
+  if (c.end < c.start || c.end > hi || c.end - c.start > L.chunk_bytes + 1) return 1;
+  if (c.last) c.uend = c.ubits + (int)(8 * (c.end - c.start));
+  else if (c.uend < c.ubits || c.uend - c.ubits > 8 * (c.end - c.start)) return 1;
+  return 0;
+}
+
+// FF 00 pairs whose FF lies in the chunk's bytes and whose 00 lies inside the segment
+JPEG_HD int jpeg_chunk_pairs(const unsigned char* scan, const JpegChunk& c, long hi) {
+  int n = 0;
+  for (long q = c.start; q < c.end; ++q) n += scan[q] == 0xFFu && q + 1 < hi && scan[q + 1] == 0;
+  return n;
+}
+
+// the bit buffer of the chunk's segment at unstuffed bit `pos` of it, c.ubits <= pos: read from the chunk's first byte
+JPEG_HD void jpeg_chunk_bits(JpegBits& bt, const unsigned char* scan, const JpegChunk& c, long hi, int pos) {
+  bt.p = scan; bt.pos = c.start; bt.end = hi; bt.buf = 0; bt.n = 0; bt.fake = 0; bt.status = 0;
+  for (int skip = pos - c.ubits; skip > 0;) {
+    jpeg_refill(bt);
+    const int t = skip < 32 ? skip : 32;
+    jpeg_consume(bt, t);
+    skip -= t;
+  }
+}
+
+// The symbols that start in [in.pos, c.uend) from state `in` -> the state behind them; *blocks: the blocks they complete.  A total
+// function: an undefined code skips one bit, a category above the table's limit is clamped, an index past 63 ends the block; a state
+// outside the chunk passes through.  It stops where the segment's bytes end.
+JPEG_HD JpegState jpeg_chunk_lenient(const unsigned char* scan, long hi, const JpegChunk& c, const JpegImage& im, const unsigned char* huff,
+                                     JpegState in, int* blocks) {
+  *blocks = 0;
+  int pos = in.pos, b = in.bk >> 8, k = in.bk & 255, n = 0;
+  if (pos < c.ubits || pos >= c.uend || b < 0 || b >= im.bpm || k > 63) return in;
+  JpegBits bt;
+  jpeg_chunk_bits(bt, scan, c, hi, pos);
+  const int limit = c.uend - c.ubits;                               // every iteration takes at least one bit
+  for (int it = 0; it < limit && pos < c.uend && !(bt.status & ZH_JPEG_STATUS_TRUNCATED); ++it) {
+    jpeg_refill(bt);
+    const int ac = k != 0;
+    const unsigned char* t = huff + (2 * (b >= im.lum) + ac) * ZH_JPEG_HUFF_TABLE_BYTES;
+    const unsigned peek = (unsigned)(bt.buf >> 48);
+    const unsigned e = ((const unsigned short*)t)[peek >> 8];
+    int len = (int)(e >> 8), val = (int)(e & 255u);
+    if (!e) {
+      const int* maxcode = (const int*)(t + JPEG_T_MAXCODE);
+      const int* valoff = (const int*)(t + JPEG_T_VALOFF);
+      for (int l = 9; l <= 16; ++l) {
+        const int code = (int)(peek >> (16 - l));
+        if (len == 0 && code <= maxcode[l]) { len = l; val = t[JPEG_T_VALS + ((code + valoff[l]) & 255)]; }
+      }
+      if (len == 0) { jpeg_consume(bt, 1); ++pos; continue; }
+    }
+    jpeg_consume(bt, len);
+    const int r = ac ? val >> 4 : 0, most = ac ? 10 : 11;
+    int sz = ac ? val & 15 : val;
+    sz = sz > most ? most : sz;
+    jpeg_consume(bt, sz);
+    pos += len + sz;
+    if (!ac) k = 1;
+    else if (sz == 0) k = r == 15 ? k + 16 : 64;
+    else k += r + 1;
+    if (k >= 64) {
+      k = 0;
+      if (++b == im.bpm) b = 0;
+      ++n;
+    }
+  }
+  *blocks = n;
+  JpegState out = {pos, b << 8 | k};
+  return out;
+}
+
+// The same symbols under jpeg_step's rules, from the state the synchronising passes left for the chunk.  first_block: the blocks of the
+// segment the chunks in front of it complete (the scan of the lenient counts); want_blocks: its own lenient count; next: the state the
+// next chunk starts from (null for the last chunk).  coef: the image's first block; DC values are written as DIFFERENCES (the
+// predictors are taken as 0 at every symbol).  Returns the status bits: jpeg_step's, or UNSYNCED when the chunk ends clean in another
+// state or with another count than the next chunk was given; *mcus: the segment's MCUs when this chunk completed its last block.
+// Behind the segment's last block nothing is decoded, as zh_jpeg_decode leaves what follows it unread.
+JPEG_HD int jpeg_chunk_strict(const unsigned char* scan, const JpegChunk& c, const JpegImage& im, const JpegSegment& s, const unsigned char* huff,
+                              short* coef, JpegState in, int first_block, int want_blocks, const JpegState* next, int* mcus) {
+  *mcus = 0;
+  const long seg_blocks = (long)(s.mcu_end - s.mcu) * im.bpm;
+  if (first_block >= seg_blocks) return 0;
+  int pos = in.pos, n = 0;
+  const int b = in.bk >> 8, k = in.bk & 255;
+  if (pos < c.ubits || b != first_block % im.bpm || k > 63) return ZH_JPEG_STATUS_UNSYNCED;
+  JpegSegment t = s;
+  t.mcu = s.mcu + first_block / im.bpm; t.b = b; t.k = k;
+  if (c.last || pos < c.uend) {
+    jpeg_chunk_bits(t.bits, scan, c, s.bits.end, pos);
+    const long limit = 8 * (c.end - c.start) + 2;                   // the chunk's bits, and the symbol that runs past the segment's end
+    for (long it = 0; it < limit && (c.last || pos < c.uend) && !jpeg_segment_done(t); ++it) {
+      t.pred0 = t.pred1 = t.pred2 = 0;
+      while (t.bits.n <= 32) jpeg_refill(t.bits);                   // jpeg_step's own refill then adds nothing: the bits it takes are n0 - n
+      const int n0 = t.bits.n, b0 = t.b, m0 = t.mcu;
+      jpeg_step(t, im, huff, coef);
+      pos += n0 - t.bits.n;
+      n += t.b != b0 || t.mcu != m0;
+    }
+  }
+  if (t.bits.status) return t.bits.status;
+  if (t.mcu >= t.mcu_end) { *mcus = s.mcu_end - s.mcu; return 0; }
+  if (!next) return 0;                                              // (a last chunk ends in one of the two ways above)
+  const JpegState out = {pos, t.b << 8 | t.k};
+  return jpeg_state_equal(out, *next) && n == want_blocks ? 0 : ZH_JPEG_STATUS_UNSYNCED;
+}
+
+// DC predictor + difference as the serial decoder's int sum wraps (32-bit two's complement)
+JPEG_HD unsigned jpeg_dc_add(unsigned pred, short diff) { return pred + (unsigned)(int)diff; }

@@ -2,10 +2,34 @@
 // zh_jpeg_decode's launches.  HOST pointers throughout; no kernel and no HIP call in this file — it is what the CPU tests compare with
 // jpeg_device.decode_np and what tools/host/jpeg_host_check.cpp runs under the host sanitizers (tools/README.md).  The scratch
 // (coefficients, sample planes, MCU counters) is allocated here at exactly the sizes the device workspace has.
+// zh_jpeg_decode_split_host: the passes of zh_jpeg_decode_split over the same rows with the same codec functions; a sequence's lanes run
+// one after the other, which reaches the state the kernel's rounds settle in (lane i's state is a function of lane i - 1's alone).
 #include <stdlib.h>
 #include <string.h>
 #include "common.h"
 #include "jpeg_codec.h"
+
+// the launches behind the entropy stage, shared by both entries: DESCRIPTOR / INCOMPLETE, then per image B and C
+static void jpeg_host_pixels(const int* images, int B, const unsigned char* tables, int n_sets, long n_blocks, const short* coef, unsigned char* samples,
+                             const int* counters, unsigned char* out, long out_bytes, int* status) {
+  for (int b = 0; b < B; ++b) {
+    const JpegImage im = jpeg_image(images + (long)b * ZH_JPEG_IMAGE_WORDS, n_sets, n_blocks, out_bytes);
+    if (!im.ok) { status[b] |= ZH_JPEG_STATUS_DESCRIPTOR; continue; }
+    if (counters[b] != im.mcux * im.mcuy) status[b] |= ZH_JPEG_STATUS_INCOMPLETE;
+    // B: dequantise + inverse DCT
+    const unsigned short* q = (const unsigned short*)(tables + (long)im.tset * ZH_JPEG_TABLE_SET_BYTES + JPEG_HUFF_SET_BYTES);
+    unsigned char* planes = samples + im.block0 * 64;
+    for (long j = 0; j < im.nblocks; ++j) {
+      long ld;
+      int cls;
+      const long at = jpeg_block_place(im, j, &ld, &cls);
+      jpeg_idct_block(coef + (im.block0 + j) * 64, q + 64 * cls, planes + at, ld);
+    }
+    // C: upsample + colour
+    for (int y = 0; y < im.h; ++y)
+      for (int x = 0; x < im.w; ++x) jpeg_pixel(im, planes, x, y, out + im.out + 3 * ((long)y * im.w + x));
+  }
+}
 
 extern "C" int zh_jpeg_decode_host(const unsigned char* scan, long scan_bytes, const int* segments, int n_segments, const int* images, int B,
                                    const unsigned char* tables, int n_sets, long n_blocks, unsigned char* out, long out_bytes, int* status) {
@@ -43,23 +67,103 @@ extern "C" int zh_jpeg_decode_host(const unsigned char* scan, long scan_bytes, c
     if (s.bits.status) status[b] |= s.bits.status;
     else if (s.mcu >= s.mcu_end) counters[b] += mcus;
   }
-  for (int b = 0; b < B; ++b) {
-    const JpegImage im = jpeg_image(images + (long)b * ZH_JPEG_IMAGE_WORDS, n_sets, n_blocks, out_bytes);
-    if (!im.ok) { status[b] |= ZH_JPEG_STATUS_DESCRIPTOR; continue; }
-    if (counters[b] != im.mcux * im.mcuy) status[b] |= ZH_JPEG_STATUS_INCOMPLETE;
-    // B: dequantise + inverse DCT
-    const unsigned short* q = (const unsigned short*)(tables + (long)im.tset * ZH_JPEG_TABLE_SET_BYTES + JPEG_HUFF_SET_BYTES);
-    unsigned char* planes = samples + im.block0 * 64;
-    for (long j = 0; j < im.nblocks; ++j) {
-      long ld;
-      int cls;
-      const long at = jpeg_block_place(im, j, &ld, &cls);
-      jpeg_idct_block(coef + (im.block0 + j) * 64, q + 64 * cls, planes + at, ld);
-    }
-    // C: upsample + colour
-    for (int y = 0; y < im.h; ++y)
-      for (int x = 0; x < im.w; ++x) jpeg_pixel(im, planes, x, y, out + im.out + 3 * ((long)y * im.w + x));
-  }
+  jpeg_host_pixels(images, B, tables, n_sets, n_blocks, coef, samples, counters, out, out_bytes, status);
   free(coef); free(samples); free(counters);
+  return ZH_OK;
+}
+
+extern "C" int zh_jpeg_decode_split_host(const unsigned char* scan, long scan_bytes, const int* segments, int n_segments, const int* chunks, long n_chunks,
+                                         int chunk_bytes, int passes, const int* images, int B, const unsigned char* tables, int n_sets, long n_blocks,
+                                         unsigned char* out, long out_bytes, int* status) {
+  ZH_CHECK_ARG(B >= 0 && B <= 65535, "zh_jpeg_decode_split_host: B = %d outside 0 .. 65535", B);
+  if (B == 0) return ZH_OK;
+  ZH_CHECK_ARG(scan_bytes >= 0 && scan_bytes <= 0x7fffffffL && out_bytes >= 0, "zh_jpeg_decode_split_host: scan_bytes / out_bytes outside 0 .. 2^31 - 1 / negative");
+  ZH_CHECK_ARG(n_segments >= 0 && n_segments <= ZH_JPEG_MAX_SEGMENTS, "zh_jpeg_decode_split_host: n_segments = %d outside 0 .. %d", n_segments, ZH_JPEG_MAX_SEGMENTS);
+  ZH_CHECK_ARG(n_chunks >= 0 && n_chunks <= ZH_JPEG_MAX_CHUNKS, "zh_jpeg_decode_split_host: n_chunks = %ld outside 0 .. %d", n_chunks, ZH_JPEG_MAX_CHUNKS);
+  ZH_CHECK_ARG(chunk_bytes >= ZH_JPEG_CHUNK_BYTES_MIN && chunk_bytes <= 4096 && chunk_bytes % 16 == 0 && passes >= 1 && passes <= 64,
+               "zh_jpeg_decode_split_host: chunk_bytes = %d (a multiple of 16 in %d .. 4096) / passes = %d (1 .. 64)", chunk_bytes, ZH_JPEG_CHUNK_BYTES_MIN, passes);
+  ZH_CHECK_ARG(n_sets >= 1 && n_sets <= ZH_JPEG_MAX_TABLE_SETS, "zh_jpeg_decode_split_host: n_sets = %d outside 1 .. %d", n_sets, ZH_JPEG_MAX_TABLE_SETS);
+  ZH_CHECK_ARG(n_blocks >= 1 && n_blocks < (1L << 24), "zh_jpeg_decode_split_host: n_blocks = %ld outside 1 .. 2^24 - 1", n_blocks);
+  ZH_CHECK_ARG(scan && segments && chunks && images && tables && out && status, "zh_jpeg_decode_split_host: null pointer");
+  ZH_CHECK_ARG(((uintptr_t)tables & 3) == 0, "zh_jpeg_decode_split_host: tables must be 4-byte aligned");
+  const long n_seq = (n_chunks + ZH_JPEG_SPLIT_LANES - 1) / ZH_JPEG_SPLIT_LANES, nc = n_chunks > 0 ? n_chunks : 1, ns = n_seq > 0 ? n_seq : 1;
+  short* coef = (short*)calloc((size_t)n_blocks * 64, sizeof(short));
+  unsigned char* samples = (unsigned char*)malloc((size_t)n_blocks * 64);
+  int* counters = (int*)calloc((size_t)B, sizeof(int));
+  JpegState* st_in = (JpegState*)calloc((size_t)nc, sizeof(JpegState));
+  JpegState* st_out = (JpegState*)calloc((size_t)nc, sizeof(JpegState));
+  JpegState* hand = (JpegState*)calloc((size_t)ns * 2, sizeof(JpegState));
+  int* cnt = (int*)calloc((size_t)nc, sizeof(int));
+  int* first = (int*)calloc((size_t)nc, sizeof(int));
+  if (!coef || !samples || !counters || !st_in || !st_out || !hand || !cnt || !first) {
+    free(coef); free(samples); free(counters); free(st_in); free(st_out); free(hand); free(cnt); free(first);
+    zh_set_error("zh_jpeg_decode_split_host: out of memory for %ld blocks and %ld chunks", n_blocks, n_chunks);
+    return ZH_ERR_WORKSPACE;
+  }
+  memset(status, 0, (size_t)B * sizeof(int));
+  const JpegLaunch L = {scan, scan_bytes, segments, n_segments, chunks, n_chunks, chunk_bytes, images, B, n_sets, n_blocks, out_bytes, n_blocks, 64 * n_blocks};
+  // the synchronising passes
+  for (int pass = 0; pass < passes; ++pass)
+    for (long w = 0; w < n_seq; ++w) {
+      JpegState last = {0, 0};
+      for (long i = w * ZH_JPEG_SPLIT_LANES; i < n_chunks && i < (w + 1) * ZH_JPEG_SPLIT_LANES; ++i) {
+        JpegChunk c; JpegImage im; JpegSegment s;
+        int b;
+        const bool ok = jpeg_chunk(L, i, c, im, s, &b) == 0, lane0 = i == w * ZH_JPEG_SPLIT_LANES;
+        JpegState in = {ok ? c.ubits : 0, 0}, o = in;
+        int n = 0;
+        if (ok) {
+          if (!c.first && !lane0) in = last;
+          else if (pass > 0) {
+            in = st_in[i];
+            if (!c.first && w > 0) in = hand[((pass - 1) & 1) * n_seq + w - 1];
+          }
+          o = jpeg_chunk_lenient(scan, s.bits.end, c, im, tables + (long)im.tset * ZH_JPEG_TABLE_SET_BYTES, in, &n);
+        }
+        st_in[i] = in; st_out[i] = o; cnt[i] = n;
+        last = o;
+      }
+      hand[(pass & 1) * n_seq + w] = last;
+    }
+  // the scan of the block counts: every chunk's first block inside its segment
+  for (long i = 0, run = 0; i < n_chunks; ++i) {
+    if (chunks[i * ZH_JPEG_CHUNK_WORDS + 3] == 1) run = 0;
+    first[i] = (int)run;
+    run = jpeg_block_sum((int)run, cnt[i]);
+  }
+  // the strict pass
+  for (long i = 0; i < n_chunks; ++i) {
+    JpegChunk c; JpegImage im; JpegSegment s;
+    int b;
+    const int rc = jpeg_chunk(L, i, c, im, s, &b);
+    if (rc < 0) continue;
+    if (rc > 0 || (!c.last && c.ubits + 8 * (int)(c.end - c.start - jpeg_chunk_pairs(scan, c, s.bits.end)) != c.uend)) { status[b] |= ZH_JPEG_STATUS_DESCRIPTOR; continue; }
+    const JpegState pinned = {0, 0};
+    int mcus;
+    status[b] |= jpeg_chunk_strict(scan, c, im, s, tables + (long)im.tset * ZH_JPEG_TABLE_SET_BYTES, coef + im.block0 * 64, c.first ? pinned : st_in[i], first[i],
+                                   cnt[i], c.last ? nullptr : &st_in[i + 1], &mcus);
+    counters[b] += mcus;
+  }
+  // the DC sums of every segment
+  for (long sg = 0; sg < n_segments; ++sg) {
+    const int* row = segments + sg * ZH_JPEG_SEGMENT_WORDS;
+    const int b = row[0];
+    if (b < 0 || b >= B) continue;
+    const JpegImage im = jpeg_launch_image(L, b);
+    if (!im.ok) continue;
+    JpegSegment s;
+    int st;
+    if (!jpeg_segment(row, im, scan, scan_bytes, s, &st)) { status[b] |= st; continue; }
+    unsigned pred[3] = {0, 0, 0};
+    for (long m = s.mcu; m < s.mcu_end; ++m)
+      for (int j = 0; j < im.bpm; ++j) {
+        short* blk = coef + (im.block0 + m * im.bpm + j) * 64;
+        const int comp = j < im.lum ? 0 : j - im.lum + 1;
+        pred[comp] = jpeg_dc_add(pred[comp], blk[0]);
+        blk[0] = (short)pred[comp];
+      }
+  }
+  jpeg_host_pixels(images, B, tables, n_sets, n_blocks, coef, samples, counters, out, out_bytes, status);
+  free(coef); free(samples); free(counters); free(st_in); free(st_out); free(hand); free(cnt); free(first);
   return ZH_OK;
 }

@@ -20,6 +20,8 @@ transform (the tests' reference), so the embeddings are bit for bit those of the
 `decoder="device"` (opt-in; "host" is the default): the threads only read the files and parse their headers, baseline JPEG files
 cross to the device as file bytes and zh_jpeg_decode (zutis_amd/jpeg_device.py: byte for byte Pillow's pixels) decodes them in front
 of the resize kernel; any other file, and any the device reports as damaged, is decoded by Pillow as before — the embeddings are the same.
+`decoder="device-split"`: the same route with every file's scan split among lanes (zh_jpeg_decode_split: a file without restart markers
+is one entropy segment, which "device" leaves to one lane); the same pixels, the same embeddings.
 """
 import os
 import pickle as pkl

@@ -16,7 +16,9 @@ libjpeg-turbo: integer arithmetic throughout, restated here from the public algo
 
 pack() lays the descriptor arrays of one launch out (scan bytes, segment rows sorted by length, image rows, table sets deduplicated
 across the batch, output offsets); table_set_bytes() is the ONE form of the canonical Huffman tables that decode_np, the host entry and
-the kernel read.  No torch at import.
+the kernel read.  chunk_rows() cuts the segments of a launch into the chunk rows of zh_jpeg_decode_split (decoder "device-split": a
+scan without restart markers split among lanes; include/zutis_hip.h has the method), chunk_rows_np() is their definition byte by byte.
+No torch at import.
 """
 from __future__ import annotations
 
@@ -33,7 +35,10 @@ IMAGE_WORDS, SEGMENT_WORDS = _K["ZH_JPEG_IMAGE_WORDS"], _K["ZH_JPEG_SEGMENT_WORD
 TABLE_BYTES, TABLE_SET_BYTES = _K["ZH_JPEG_HUFF_TABLE_BYTES"], _K["ZH_JPEG_TABLE_SET_BYTES"]
 MAX_TABLE_SETS, MAX_SEGMENTS = _K["ZH_JPEG_MAX_TABLE_SETS"], _K["ZH_JPEG_MAX_SEGMENTS"]
 STATUS = {k[len("ZH_JPEG_STATUS_"):].lower(): v for k, v in _K.items() if k.startswith("ZH_JPEG_STATUS_")}
-DECODERS = ("host", "device")
+CHUNK_WORDS, CHUNK_BYTES, CHUNK_BYTES_MIN = _K["ZH_JPEG_CHUNK_WORDS"], _K["ZH_JPEG_CHUNK_BYTES"], _K["ZH_JPEG_CHUNK_BYTES_MIN"]
+SPLIT_LANES, SPLIT_PASSES, MAX_CHUNKS = _K["ZH_JPEG_SPLIT_LANES"], _K["ZH_JPEG_SPLIT_PASSES"], _K["ZH_JPEG_MAX_CHUNKS"]
+MAX_SEGMENT_BYTES = 2 ** 28                       # split decoding counts a segment's unstuffed BITS in int32
+DECODERS = ("host", "device", "device-split")
 ALIGN = 16                                        # byte alignment of an image inside the output (descriptors hold offset / 16)
 _LOOK, _MAXCODE, _VALOFF, _VALS = 0, 512, 584, 656      # byte offsets inside one Huffman table: u16 [256], i32 [18], i32 [18], u8 [256]
 
@@ -485,16 +490,23 @@ class Packed:
     max_image_blocks: int = 1        # the largest image's blocks and pixels: the widths of the pixel stage's grids
     max_image_pixels: int = 1
     kept: Optional[List[int]] = None      # positions, in pack()'s argument lists, of the images these arrays describe (all, unless skip_overflow)
+    chunks: Optional[np.ndarray] = None   # pack(chunk_bytes=...): int32 [C, 4], the chunk rows of zh_jpeg_decode_split (chunk_rows)
+    chunk_bytes: Optional[int] = None
 
 
 def pack(plans: Sequence[JpegPlan], datas: Sequence, out_off: Optional[Sequence[int]] = None, out_bytes: Optional[int] = None,
-         skip_overflow: bool = False) -> Packed:
+         skip_overflow: bool = False, chunk_bytes: Optional[int] = None) -> Packed:
     """The descriptor arrays of one launch over `plans` (of the files `datas`).  out_off: where each image's [H, W, 3] bytes go (default:
     back to back, aligned to 16).  More than MAX_TABLE_SETS distinct table sets is a ValueError — or, with skip_overflow, the images
     that would bring a set past the limit are left out (Packed.kept lists the others: the caller leaves the rest to the host); more
-    than MAX_SEGMENTS segments is a ValueError."""
+    than MAX_SEGMENTS segments is a ValueError.  chunk_bytes: also the chunk rows of zh_jpeg_decode_split (Packed.chunks); an image
+    with a segment of MAX_SEGMENT_BYTES or more is then treated as one that brings a table set too many."""
     sets, set_index, kept = {}, [], []
     for i, p in enumerate(plans):
+        if chunk_bytes is not None and len(p.segments) and int((p.segments[:, 1] - p.segments[:, 0]).max()) >= MAX_SEGMENT_BYTES:
+            if not skip_overflow:
+                raise ValueError(f"jpeg_device.pack: an entropy segment of {MAX_SEGMENT_BYTES} bytes or more cannot be split into chunks")
+            continue
         key = table_set_bytes(p)
         if key not in sets and len(sets) == MAX_TABLE_SETS:
             if not skip_overflow:
@@ -529,8 +541,64 @@ def pack(plans: Sequence[JpegPlan], datas: Sequence, out_off: Optional[Sequence[
     order = np.argsort(-(segments[:, 2] - segments[:, 1]), kind="stable")       # a wave's lanes finish together
     scan = np.concatenate(chunks) if chunks else np.zeros(0, np.uint8)
     tables = np.frombuffer(b"".join(sets), np.uint8).reshape(len(sets), TABLE_SET_BYTES).copy() if sets else np.zeros((0, TABLE_SET_BYTES), np.uint8)
-    return Packed(np.ascontiguousarray(scan), np.ascontiguousarray(segments[order]), images, tables, out_off, int(out_bytes), blocks,
-                  [(p.height, p.width) for p in plans], max([p.n_blocks for p in plans], default=1), max([p.width * p.height for p in plans], default=1), kept)
+    packed = Packed(np.ascontiguousarray(scan), np.ascontiguousarray(segments[order]), images, tables, out_off, int(out_bytes), blocks,
+                    [(p.height, p.width) for p in plans], max([p.n_blocks for p in plans], default=1), max([p.width * p.height for p in plans], default=1), kept)
+    if chunk_bytes is not None:
+        packed.chunks, packed.chunk_bytes = chunk_rows(packed, chunk_bytes), int(chunk_bytes)
+    return packed
+
+
+def _check_chunk_bytes(chunk_bytes) -> int:
+    cb = int(chunk_bytes)
+    if cb != chunk_bytes or cb < CHUNK_BYTES_MIN or cb > 4096 or cb % 16:
+        raise ValueError(f"jpeg_device: chunk_bytes {chunk_bytes!r} is not a multiple of 16 in {CHUNK_BYTES_MIN} .. 4096")
+    return cb
+
+
+def chunk_rows(packed: Packed, chunk_bytes: int = CHUNK_BYTES) -> np.ndarray:
+    """int32 [C, CHUNK_WORDS] = (segment row, first byte, unstuffed bits of the segment in front of it, 1 for a segment's first chunk):
+    every segment [lo, hi) of packed.segments cut every chunk_bytes bytes, segment after segment in the order of the rows; a cut that
+    falls on the 00 of an FF 00 pair moves behind it; a segment without bytes has one chunk.  The stuffed bytes are those of an FF 00
+    pair that lies inside one segment.  Vectorised: one search of the stuffed bytes against the cuts."""
+    cb = _check_chunk_bytes(chunk_bytes)
+    seg = packed.segments.astype(np.int64).reshape(-1, SEGMENT_WORDS)
+    lo, hi = seg[:, 1], seg[:, 2]
+    n = np.maximum(1, -(-(hi - lo) // cb))
+    total = int(n.sum())
+    if total > MAX_CHUNKS:
+        raise ValueError(f"jpeg_device.chunk_rows: {total} chunks exceed one launch ({MAX_CHUNKS})")
+    row = np.repeat(np.arange(len(seg)), n)
+    j = np.arange(total) - np.repeat(np.cumsum(n) - n, n)
+    start = lo[row] + cb * j
+    scan = packed.scan
+    ff = np.flatnonzero(scan[:-1] == 0xFF) if scan.size > 1 else np.zeros(0, np.int64)
+    zeros = ff[scan[ff + 1] == 0] + 1
+    stuffed = np.zeros(scan.size + 1, bool)
+    stuffed[zeros] = True
+    stuffed[lo] = False                                     # an FF that ends a segment in front of a 00 that begins the next is no pair
+    zeros = zeros[stuffed[zeros]]
+    start = start + stuffed[start]
+    ubits = 8 * ((start - lo[row]) - (np.searchsorted(zeros, start) - np.searchsorted(zeros, lo[row])))
+    return np.ascontiguousarray(np.stack([row, start, ubits, j == 0], axis=1).astype(np.int32))
+
+
+def chunk_rows_np(packed: Packed, chunk_bytes: int = CHUNK_BYTES) -> np.ndarray:
+    """chunk_rows, defined byte by byte (plain loops; the tests compare the two)."""
+    cb = _check_chunk_bytes(chunk_bytes)
+    scan, rows = packed.scan.tolist(), []
+    for r, (_, lo, hi, _) in enumerate(packed.segments.tolist()):
+        stuffed = [q > lo and scan[q] == 0 and scan[q - 1] == 0xFF for q in range(lo, hi)]
+        for j in range(max(1, -(-(hi - lo) // cb))):
+            start = lo + cb * j
+            if start < hi and stuffed[start - lo]:
+                start += 1
+            rows.append((r, start, 8 * (start - lo - sum(stuffed[:start - lo])), int(j == 0)))
+    return np.asarray(rows, np.int32).reshape(-1, CHUNK_WORDS)
+
+
+def sequences(packed: Packed) -> int:
+    """The sequences (workgroups of SPLIT_LANES chunk rows) of a launch: as many passes always reach every true state."""
+    return max(1, -(-len(packed.chunks) // SPLIT_LANES))
 
 
 def unpack(packed: Packed, out: np.ndarray) -> List[np.ndarray]:
@@ -553,7 +621,28 @@ def decode_host(packed: Packed):
     return unpack(packed, out), status[:B]
 
 
+def decode_split_host(packed: Packed, chunk_bytes: Optional[int] = None, passes: int = SPLIT_PASSES):
+    """zh_jpeg_decode_split_host over a launch's arrays: (images, status int32 [B]).  The CPU twin of zh_jpeg_decode_split.  The chunk
+    rows are packed.chunks (pack(chunk_bytes=...)) when chunk_bytes is None or theirs, chunk_rows(packed, chunk_bytes) otherwise."""
+    import ctypes as C
+    lib = _lib.load(raw=True)
+    if packed.chunks is not None and chunk_bytes in (None, packed.chunk_bytes):
+        chunks, cb = packed.chunks, packed.chunk_bytes
+    else:
+        cb = CHUNK_BYTES if chunk_bytes is None else chunk_bytes
+        chunks = chunk_rows(packed, cb)
+    B = len(packed.shapes)
+    out = np.zeros(max(packed.out_bytes, 1), np.uint8)
+    status = np.zeros(max(B, 1), np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    rc = lib.zh_jpeg_decode_split_host(ptr(packed.scan), packed.scan.size, ptr(packed.segments), len(packed.segments), ptr(chunks), len(chunks), int(cb),
+                                       int(passes), ptr(packed.images), B, ptr(packed.tables), len(packed.tables), packed.n_blocks, ptr(out),
+                                       packed.out_bytes, ptr(status))
+    _lib.check(rc, "zh_jpeg_decode_split_host")
+    return unpack(packed, out), status[:B]
+
+
 def check_decoder(name: str, decoder) -> str:
     if decoder not in DECODERS:
-        raise ValueError(f"{name}: decoder {decoder!r} is not \"host\" or \"device\"")
+        raise ValueError(f"{name}: decoder {decoder!r} is not \"host\", \"device\" or \"device-split\"")
     return decoder

@@ -1017,6 +1017,30 @@ def jpeg_decode(scan, segments, images, tables, n_blocks, max_image_blocks, max_
     return status
 
 
+def jpeg_decode_split(scan, segments, chunks, images, tables, n_blocks, max_image_blocks, max_image_pixels, out, status, chunk_bytes=None, passes=None,
+                      workspace=None):
+    """jpeg_decode with every segment's entropy stage split among lanes (zh_jpeg_decode_split): chunks int32 [C, 4] are the rows of
+    jpeg_device.chunk_rows at chunk_bytes (default: jpeg_device.CHUNK_BYTES), passes the synchronising launches (default:
+    jpeg_device.SPLIT_PASSES).  An image whose chunks did not all start from verified states has the `unsynced` bit in its status and is
+    left to the host like any other non-zero status; every other image's pixels are jpeg_decode's.  Returns status."""
+    _chk(scan, torch.uint8, "jpeg_decode_split scan"); _chk(out, torch.uint8, "jpeg_decode_split out"); _chk(tables, torch.uint8, "jpeg_decode_split tables")
+    _chk(segments, torch.int32, "jpeg_decode_split segments"); _chk(images, torch.int32, "jpeg_decode_split images")
+    _chk(status, torch.int32, "jpeg_decode_split status"); _chk(chunks, torch.int32, "jpeg_decode_split chunks")
+    B = images.shape[0] if images.dim() == 2 else -1
+    if B < 0 or images.shape[1] != _ZH["ZH_JPEG_IMAGE_WORDS"] or segments.dim() != 2 or segments.shape[1] != _ZH["ZH_JPEG_SEGMENT_WORDS"] or \
+            chunks.dim() != 2 or chunks.shape[1] != _ZH["ZH_JPEG_CHUNK_WORDS"] or tables.dim() != 2 or tables.shape[1] != _ZH["ZH_JPEG_TABLE_SET_BYTES"] or \
+            status.numel() != B:
+        raise _lib.ZutisHipError("jpeg_decode_split: segments [S, 4], chunks [C, 4], images [B, 12], tables [n_sets, TABLE_SET_BYTES] and status [B] do not "
+                                 "describe one batch")
+    chunk_bytes = _ZH["ZH_JPEG_CHUNK_BYTES"] if chunk_bytes is None else int(chunk_bytes)
+    passes = _ZH["ZH_JPEG_SPLIT_PASSES"] if passes is None else int(passes)
+    if B:
+        ws, need = _workspace_or(workspace, "jpeg_decode_split", "zh_jpeg_decode_split_workspace_size", out.device, B, int(n_blocks), chunks.shape[0])
+        _call("zh_jpeg_decode_split", _p(scan), scan.numel(), _p(segments), segments.shape[0], _p(chunks), chunks.shape[0], chunk_bytes, passes, _p(images), B,
+              _p(tables), tables.shape[0], int(n_blocks), int(max_image_blocks), int(max_image_pixels), _p(out), out.numel(), _p(status), _p(ws), need, _stream())
+    return status
+
+
 # ---- training criterion (criterion.py::Criterion): zutis_amd/criterion.py
 
 def mask_match_cost(proposals, gt_u8, inst_off, n_max, H, W, costs, stat_p, stat_pg, stat_g, skip, status, weight_dice=1.0, weight_bce=1.0):

@@ -240,7 +240,8 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     decoder "host": the decoding threads run Pillow.  "device": they read the files and parse the headers; baseline JPEG files cross to
     the device as their file bytes and are decoded there (zh_jpeg_decode: zutis_amd/jpeg_device.py defines the pixels, byte for byte
     Pillow's), everything else — and any file whose scan the device reports as damaged — is decoded by Pillow as ever, so the files
-    written do not depend on it.  Any other value: ValueError before any work.
+    written do not depend on it.  "device-split": as "device", with every file's scan split among lanes (zh_jpeg_decode_split), which is
+    what a file without restart markers needs to be decoded in parallel.  Any other value: ValueError before any work.
     Returns {"label_paths": [...] | None, "overlay_paths": [...] | None, "instance_predictions": the dicts predict gave (with "bbox"),
     in input-path order, "n_images": int}.
     A missing or unreadable image (FileNotFoundError / OSError / ValueError) and a directory or file that cannot be written (OSError)

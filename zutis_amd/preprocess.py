@@ -162,11 +162,14 @@ ground truth; `packed` is None, packed_bytes and desc still describe the decoded
 device_batches has run the decoder (jpeg: a JpegStage).
 Valid until the loader is advanced."""
 
-JpegStage = collections.namedtuple("JpegStage", "staged_bytes images segments tables scan n_blocks max_image_blocks max_image_pixels kept host")
+JpegStage = collections.namedtuple("JpegStage", "staged_bytes images segments tables scan n_blocks max_image_blocks max_image_pixels kept host chunks",
+                                   defaults=(None,))
 JpegStage.__doc__ = """Where the file bytes of a decoder="device" batch lie in its staging buffer, offsets counted from the end of the
 descriptor rows: images / segments / tables / scan = (offset, bytes) of the arrays of jpeg_device.pack; n_blocks, max_image_blocks,
 max_image_pixels: its launch sizes; kept: the batch positions of the images the launch decodes, in the order of its rows; host:
-(batch position, offset of its pixels in the staged bytes, bytes, offset of its slot in the decoded images) of every host-decoded image."""
+(batch position, offset of its pixels in the staged bytes, bytes, offset of its slot in the decoded images) of every host-decoded image;
+chunks: (offset, bytes) of the chunk rows of jpeg_device.chunk_rows at jpeg_device.CHUNK_BYTES, staged behind the scan bytes when the
+loader's decoder is "device-split" (None otherwise): decode_staged then calls ops.jpeg_decode_split."""
 
 
 class DoubleBuffer:
@@ -279,9 +282,9 @@ class BatchLoader:
                 raise ValueError(f"{p}: size {wh} differs from its header's {tuple(size)}")
         want = [i for i in range(B) if files[i][1] is not None and host_boxes[i] is None]
         jp = jpeg_device.pack([files[i][1] for i in want], [files[i][0] for i in want], out_off=[shapes[i][0] for i in want], out_bytes=off,
-                              skip_overflow=True)
+                              skip_overflow=True, chunk_bytes=jpeg_device.CHUNK_BYTES if self.decoder == "device-split" else None)
         kept = [want[k] for k in jp.kept]
-        arrays = [np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in (jp.images, jp.segments, jp.tables, jp.scan)]
+        arrays = [np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in (jp.images, jp.segments, jp.tables, jp.scan) + (() if jp.chunks is None else (jp.chunks,))]
         at, places = 0, []
         for a in arrays:
             places.append((at, a.size))
@@ -300,7 +303,7 @@ class BatchLoader:
             pay[o:o + n] = a
         futures = [pool.submit(self._decode, chunk[i], pay[o:o + n].reshape(shapes[i][1], shapes[i][2], 3), sizes[i], host_boxes[i], out_wh)
                    for i, o, n, _ in host]
-        stage = JpegStage(at, *places, jp.n_blocks, jp.max_image_blocks, jp.max_image_pixels, kept, host)
+        stage = JpegStage(at, *places[:4], jp.n_blocks, jp.max_image_blocks, jp.max_image_pixels, kept, host, places[4] if len(places) > 4 else None)
         resized = [p for p, hb in zip(chunk, host_boxes) if hb is not None]
         return Batch(paths=chunk, staging=staging, desc=desc, kmax=kmax, n_host=len(resized), host_paths=resized, packed_bytes=off, jpeg=stage,
                      n_host_decoded=len(host), host_decoded_paths=[chunk[i] for i, _, _, _ in host]), futures
@@ -324,7 +327,7 @@ class BatchLoader:
             rows[i] = (off // ALIGN, w, h, nw, nh, left, top, 0)
             shapes.append((off, h, w))
             off += -(-3 * w * h // ALIGN) * ALIGN
-        if self.decoder == "device":
+        if self.decoder != "host":
             return self._pack_files(pool, slot, chunk, sizes, host_boxes, shapes, rows, kmax, off, out_wh, extra)
         head = B * DESC_INTS * 4
         staging = self._staging.take(slot, head + off + extra)
@@ -339,7 +342,7 @@ class BatchLoader:
     def _start(self, pool: ThreadPoolExecutor, slot: int, k: int):
         """Fix batch k's layout from the headers and start its decodes: (Batch, futures)."""
         chunk = self.paths[k * self.batch_size:(k + 1) * self.batch_size]
-        if self.decoder == "device":    # one read serves the header and the decoder
+        if self.decoder != "host":      # one read serves the header and the decoder
             self._files[slot] = list(pool.map(self._read, chunk))
             sizes = [wh for _, _, wh in self._files[slot]]
         else:
@@ -537,7 +540,8 @@ def resize_normalize_of(lut: torch.Tensor):
 def decode_staged(batch: Batch, staged: torch.Tensor, full: torch.Tensor) -> torch.Tensor:
     """The device side of decoder="device": `staged` is the batch's staging buffer on the device (descriptor rows, file bytes, host-decoded
     pixels, ground truth); `full` receives what a host-decoded staging buffer would hold there — the rows, every image's RGB bytes at its
-    row's offset, the ground truth — and is returned.  One zh_jpeg_decode launch sequence (ops.jpeg_decode) writes the served images
+    row's offset, the ground truth — and is returned.  One zh_jpeg_decode launch sequence (ops.jpeg_decode; ops.jpeg_decode_split when the
+    loader staged chunk rows: decoder="device-split") writes the served images
     straight into their slots, the host-decoded ones are copied into theirs on the device.  The status array is read once, here: the
     read waits for the batch's upload and its decode (the wait device_batches makes behind the driver's body then returns at once).  An
     image with a non-zero status is decoded by Pillow on the calling thread and written over its slot before anything reads it; whatever
@@ -553,9 +557,13 @@ def decode_staged(batch: Batch, staged: torch.Tensor, full: torch.Tensor) -> tor
     if j.kept:
         part = lambda place, dtype, cols: pay[place[0]:place[0] + place[1]].view(dtype).view(-1, cols)      # noqa: E731
         status = torch.empty(len(j.kept), dtype=torch.int32, device=staged.device)
-        ops.jpeg_decode(pay[j.scan[0]:j.scan[0] + j.scan[1]], part(j.segments, torch.int32, jpeg_device.SEGMENT_WORDS),
-                        part(j.images, torch.int32, jpeg_device.IMAGE_WORDS), part(j.tables, torch.uint8, jpeg_device.TABLE_SET_BYTES),
-                        j.n_blocks, j.max_image_blocks, j.max_image_pixels, rgb, status)
+        arrays = (pay[j.scan[0]:j.scan[0] + j.scan[1]], part(j.segments, torch.int32, jpeg_device.SEGMENT_WORDS),
+                  part(j.images, torch.int32, jpeg_device.IMAGE_WORDS), part(j.tables, torch.uint8, jpeg_device.TABLE_SET_BYTES))
+        if j.chunks is None:
+            ops.jpeg_decode(*arrays, j.n_blocks, j.max_image_blocks, j.max_image_pixels, rgb, status)
+        else:
+            ops.jpeg_decode_split(*arrays[:2], part(j.chunks, torch.int32, jpeg_device.CHUNK_WORDS), *arrays[2:], j.n_blocks, j.max_image_blocks,
+                                  j.max_image_pixels, rgb, status)
     for _, at, n, slot in j.host:
         rgb[slot:slot + n].copy_(pay[at:at + n])
     if status is not None:
