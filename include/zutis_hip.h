@@ -44,7 +44,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 244 /* 244: zh_jpeg_decode_split / zh_jpeg_decode_split_host (a scan without restart markers split among lanes, ZH_JPEG_CHUNK_*, ZH_JPEG_SPLIT_*, ZH_JPEG_STATUS_UNSYNCED); 243: zh_jpeg_decode / zh_jpeg_decode_host (the device JPEG decoder: baseline files reach the GPU as file bytes, ZH_JPEG_*); 242: the attention entries take head_dim 128 (a behaviour change: a stale build would refuse the ViT-L decoder); 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 245 /* 245: zh_jpeg_encode / zh_jpeg_encode_host (the device JPEG encoder: overlays leave the GPU as the scan of a baseline JPEG, ZH_JPEG_ENC_*); 244: zh_jpeg_decode_split / zh_jpeg_decode_split_host (a scan without restart markers split among lanes, ZH_JPEG_CHUNK_*, ZH_JPEG_SPLIT_*, ZH_JPEG_STATUS_UNSYNCED); 243: zh_jpeg_decode / zh_jpeg_decode_host (the device JPEG decoder: baseline files reach the GPU as file bytes, ZH_JPEG_*); 242: the attention entries take head_dim 128 (a behaviour change: a stale build would refuse the ViT-L decoder); 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -730,6 +730,38 @@ int zh_jpeg_decode_split(const unsigned char* scan, long scan_bytes, const int* 
                          int chunk_bytes, int passes, const int* images, int B, const unsigned char* tables, int n_sets, long n_blocks,
                          long max_image_blocks, long max_image_pixels, unsigned char* out, long out_bytes, int* status, void* workspace,
                          size_t workspace_bytes, zh_stream_t stream);
+
+/* ---- device JPEG encoder (zutis_amd/jpeg_device.py encode_np / scan_np is the definition; csrc/jpeg_enc.hip and csrc/jpeg_host.hip over
+ * csrc/jpeg_codec.h) ---- */
+/* The entropy-coded scan of the baseline JPEG of B u8 RGB images, byte for byte jpeg_device.scan_np = what Pillow (libjpeg-turbo) writes
+ * between the SOS header and EOI for save(f, "JPEG", quality, subsampling, restart_marker_blocks=ZH_JPEG_ENC_INTERVAL_MCUS): 16-bit
+ * fixed-point RGB -> YCbCr, edge replication to the MCU grid, h2v2 chroma downsampling (subsampling 2) or none (0), the islow forward DCT,
+ * quantisation by the two tables given, libjpeg's dummy-block rule, the Annex K Huffman tables, a restart marker every
+ * ZH_JPEG_ENC_INTERVAL_MCUS MCUs.  What is left for the host is the header in front (jpeg_device.header_bytes) and FF D9 behind.
+ * images u8 [image_bytes]: image b is [h, w, 3] row-major at img_off[b] (int64 [B]), (h, w) = hw[2 b], hw[2 b + 1] (int32 [B, 2]).
+ * subsampling: 0 (4:4:4) or 2 (4:2:0) for the whole call; quant u16 [2, 64]: the luma and chroma tables in natural order, 1 .. 255.
+ * out u8 [out_bytes]: image b's scan starts at out_off[b] (int64 [B]), RSTn markers included; at most slot_bytes of it are written,
+ * the slots [out_off[b], out_off[b] + slot_bytes) being the caller's layout (jpeg_device.scan_slot); bytes past the length inside the
+ * slot are not written.  lengths[b] (int32 [B]) is the TRUE length of the scan also when it exceeds slot_bytes: the caller sees the
+ * overflow there and encodes that image another way.  max_mcus: at least the MCUs of every image (the grids' width).  An image that
+ * does not fit — h or w outside 1 .. 65535, bytes outside images, more MCUs than max_mcus, a slot outside out — is not read and not
+ * written: lengths[b] = -1.
+ * Three launches (coefficients: one lane per 8 x 8 block; entropy: one workgroup per restart interval; gather: the intervals into the
+ * slot with the markers between); workspace >= zh_jpeg_encode_workspace_size bytes, 16-byte aligned: per image the zig-zag int16
+ * coefficients of max_mcus MCUs, a worst-case slot (ZH_JPEG_ENC_BLOCK_BYTES per block, doubled by stuffing) and a length word per
+ * interval.  Every loop is bounded by the geometry and these constants; nothing outside out, lengths and the workspace is written.
+ * B <= 65535; B = 0 launches nothing.  The bytes are the same every time. */
+#define ZH_JPEG_ENC_INTERVAL_MCUS 16
+#define ZH_JPEG_ENC_BLOCK_BYTES 208 /* a block's bits at the most: 11 + 11 of DC, 63 x (16 + 10) of AC = 1660 */
+#define ZH_JPEG_ENC_SLOT_EXTRA 1024 /* jpeg_device.scan_slot(h, w) = 3 h w + this */
+size_t zh_jpeg_encode_workspace_size(int B, long max_mcus, int subsampling);
+int zh_jpeg_encode(const unsigned char* images, long image_bytes, const long long* img_off, const int* hw, int B, int subsampling,
+                   long max_mcus, const unsigned short* quant, const long long* out_off, unsigned char* out, long out_bytes,
+                   long slot_bytes, int* lengths, void* workspace, size_t workspace_bytes, zh_stream_t stream);
+/* HOST twin of zh_jpeg_encode: HOST pointers, the same codec functions in three loops, scratch allocated inside at the workspace's sizes. */
+int zh_jpeg_encode_host(const unsigned char* images, long image_bytes, const long long* img_off, const int* hw, int B, int subsampling,
+                        long max_mcus, const unsigned short* quant, const long long* out_off, unsigned char* out, long out_bytes,
+                        long slot_bytes, int* lengths);
 
 /* Native launch plans (zutis_amd/plan.py): replay n recorded calls of the entry points above (op id + 32 argument words
  * each; dispatcher generated from this header) in one C loop; zh_plan_run2 alternates two plans on two streams. */

@@ -19,7 +19,7 @@ EXTRA_FLAGS = {"bilateral.hip": ["-ffp-contract=off"], "preprocess.hip": ["-ffp-
                "polygon.hip": ["-ffp-contract=off"]}  # polygon.hip: rleFrPoly's double arithmetic, bit-compared with the host's
 # the MFMA kernels live at the register budget of their occupancy: a spill is a 2-3x slowdown, so it is a build error
 # (norm.hip: the row kernels keep a whole row in registers between the two moments and are launched more often than anything but the GEMMs)
-NO_SCRATCH = {"gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "preprocess.hip", "synth.hip", "resample.hip", "label_paint.hip", "png.hip"}
+NO_SCRATCH = {"gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "preprocess.hip", "synth.hip", "resample.hip", "label_paint.hip", "png.hip", "jpeg_enc.hip"}
 MAX_SCRATCH = int(os.environ.get("ZH_BUILD_MAX_SCRATCH", "0"))    # bytes per lane tolerated: the MFMA loops must not spill (developer builds may raise it)
 # waves per SIMD the design of a kernel relies on (source -> mangled-name substring -> minimum), checked against the compiler's
 # remarks; a key that matches no kernel of its source is a build error (a renamed template would otherwise drop its guard)
@@ -37,7 +37,7 @@ MIN_OCCUPANCY = {"attention.hip": {"attn_f16_kernelILi64ELi4ELi1ELi0EE": 3, "att
                               "sum_layernorm_kernelILi0EE": 8, "sum_layernorm_kernelILi1EE": 8, "sum_layernorm_kernelILi2EE": 6,
                               "sum_layernorm_kernelILi4EE": 4, "assemble_ln_kernelIfE": 8, "assemble_ln_kernelIDF16_E": 8,
                               "l2norm_rows_kernel": 8, "gln_partial_kernel": 8, "gln_apply_kernel": 8}}
-SOURCES = ["capi.hip", "rle_host.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "mask_rle.hip", "instance_paint.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "assign.hip", "cocoeval.hip", "polygon.hip", "label_paint.hip", "png.hip", "jpeg_host.hip", "jpeg.hip", "synth.hip", "plan.hip"]
+SOURCES = ["capi.hip", "rle_host.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "mask_rle.hip", "instance_paint.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "assign.hip", "cocoeval.hip", "polygon.hip", "label_paint.hip", "png.hip", "jpeg_host.hip", "jpeg.hip", "jpeg_enc.hip", "synth.hip", "plan.hip"]
 
 
 def _hipcc() -> str:

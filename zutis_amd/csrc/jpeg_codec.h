@@ -1,5 +1,6 @@
 // The baseline JPEG decoder (zutis_amd/jpeg_device.py is the definition), written ONCE for the device kernels (jpeg.hip) and the host
-// entry (jpeg_host.hip, which tools/host/jpeg_host_check.cpp runs under the host sanitizers).  Inline functions only.
+// entry (jpeg_host.hip, which tools/host/jpeg_host_check.cpp runs under the host sanitizers).  Inline functions only.  The encoder's
+// functions (jpeg_enc.hip, zh_jpeg_encode_host) follow the decoder's, with a list of their own.
 //
 //   jpeg_image         an image row of the launch, checked: nothing of an image whose row fails is read or written
 //   jpeg_segment       a segment row, checked against the scan bytes and the image's MCUs
@@ -467,3 +468,212 @@ JPEG_HD int jpeg_chunk_strict(const unsigned char* scan, const JpegChunk& c, con
 
 // DC predictor + difference as the serial decoder's int sum wraps (32-bit two's complement)
 JPEG_HD unsigned jpeg_dc_add(unsigned pred, short diff) { return pred + (unsigned)(int)diff; }
+
+// ---- the baseline encoder (zh_jpeg_encode / zh_jpeg_encode_host: jpeg_device.scan_np is the definition; include/zutis_hip.h has the rules)
+//   jpeg_enc_image      an image of the launch, checked: nothing of an image that fails is read or written
+//   jpeg_enc_sample     one sample of a component on its edge-replicated MCU grid: colour conversion, h2v2 downsampling
+//   jpeg_enc_block      one block of the scan: samples, islow forward DCT, quantisation, the dummy-block rule -> 64 zig-zag coefficients
+//   jpeg_enc_tables     the Annex K Huffman codes by symbol
+//   jpeg_enc_token      the bits ONE zig-zag position of a block puts into the scan, from the block's mask of nonzero AC positions alone
+//   jpeg_enc_put        those bits into a word buffer, most significant first
+#define JPEG_ENC_TABLE_WORDS 256                               // code << 8 | length by symbol; four tables: luma DC, luma AC, chroma DC, chroma AC
+#define JPEG_ENC_BLOCK_BITS 1660                               // 11 + 11 of DC, 63 x (16 + 10) of AC: ZH_JPEG_ENC_BLOCK_BYTES rounded down
+
+struct JpegEncImage {
+  int h, w, hs, mcux, mcuy, lum, bpm, nint;                    // nint: restart intervals
+  long mcus, off, out;
+  bool ok;
+};
+
+JPEG_HD long jpeg_enc_intervals(long mcus) { return (mcus + ZH_JPEG_ENC_INTERVAL_MCUS - 1) / ZH_JPEG_ENC_INTERVAL_MCUS; }
+
+JPEG_HD JpegEncImage jpeg_enc_image(const long long* img_off, const int* hw, const long long* out_off, int b, int sub, long image_bytes, long out_bytes,
+                                    long slot_bytes, long max_mcus) {
+  JpegEncImage im;
+  im.h = hw[2 * b]; im.w = hw[2 * b + 1];
+  im.hs = sub == 2 ? 2 : 1; im.lum = im.hs * im.hs; im.bpm = im.lum + 2;
+  im.off = (long)img_off[b]; im.out = (long)out_off[b];
+  im.mcux = im.mcuy = im.nint = 0; im.mcus = 0;
+  im.ok = false;
+  if (im.h < 1 || im.w < 1 || im.h > 65535 || im.w > 65535) return im;
+  im.mcux = (im.w + 8 * im.hs - 1) / (8 * im.hs); im.mcuy = (im.h + 8 * im.hs - 1) / (8 * im.hs);
+  im.mcus = (long)im.mcux * im.mcuy;
+  im.nint = (int)jpeg_enc_intervals(im.mcus);
+  if (im.mcus > max_mcus || im.mcus * im.bpm * 2 * ZH_JPEG_ENC_BLOCK_BYTES + 2L * im.nint > 0x7fffffffL) return im;      // the length is an int32
+  if (im.off < 0 || im.off + 3L * im.h * im.w > image_bytes) return im;
+  if (im.out < 0 || slot_bytes < 0 || im.out + slot_bytes > out_bytes) return im;
+  im.ok = true;
+  return im;
+}
+
+// component comp (0 Y, 1 Cb, 2 Cr) of the pixel at px
+JPEG_HD int jpeg_enc_ycc(const unsigned char* px, int comp) {
+  const int r = px[0], g = px[1], b = px[2];
+  if (comp == 0) return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;                         // F(.299), F(.587), F(.114)
+  if (comp == 1) return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;         // F(.16874), F(.33126), F(.5)
+  return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;                          // F(.5), F(.41869), F(.08131)
+}
+
+// sample (x, y) of component comp on its padded grid; img: the image's first byte.  Luma and 4:4:4 chroma: the edge pixel repeats.  4:2:0
+// chroma: the full-resolution plane repeats its last row and column, and the last DOWNSAMPLED row (ceil(h / 2) - 1) repeats below it.
+JPEG_HD int jpeg_enc_sample(const JpegEncImage& im, const unsigned char* img, int comp, int x, int y) {
+  if (comp == 0 || im.hs == 1) {
+    const int xx = x < im.w ? x : im.w - 1, yy = y < im.h ? y : im.h - 1;
+    return jpeg_enc_ycc(img + 3 * ((long)yy * im.w + xx), comp);
+  }
+  const int rows = (im.h + 1) >> 1, cy = y < rows ? y : rows - 1;
+  const int y0 = 2 * cy < im.h ? 2 * cy : im.h - 1, y1 = 2 * cy + 1 < im.h ? 2 * cy + 1 : im.h - 1;
+  const int x0 = 2 * x < im.w ? 2 * x : im.w - 1, x1 = 2 * x + 1 < im.w ? 2 * x + 1 : im.w - 1;
+  const int s = jpeg_enc_ycc(img + 3 * ((long)y0 * im.w + x0), comp) + jpeg_enc_ycc(img + 3 * ((long)y0 * im.w + x1), comp) +
+                jpeg_enc_ycc(img + 3 * ((long)y1 * im.w + x0), comp) + jpeg_enc_ycc(img + 3 * ((long)y1 * im.w + x1), comp);
+  return (s + ((x & 1) ? 2 : 1)) >> 2;
+}
+
+// one pass of the islow forward DCT over eight values in place: the first (rows) scales up by 2 bits, the second (columns) back down
+JPEG_HD void jpeg_fdct8(int* d, int stride, bool first) {
+  const int t0 = d[0] + d[7 * stride], t7 = d[0] - d[7 * stride], t1 = d[stride] + d[6 * stride], t6 = d[stride] - d[6 * stride];
+  const int t2 = d[2 * stride] + d[5 * stride], t5 = d[2 * stride] - d[5 * stride], t3 = d[3 * stride] + d[4 * stride], t4 = d[3 * stride] - d[4 * stride];
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  const int sh = first ? 11 : 15, half = 1 << (sh - 1);
+  d[0] = first ? (t10 + t11) * 4 : (t10 + t11 + 2) >> 2;
+  d[4 * stride] = first ? (t10 - t11) * 4 : (t10 - t11 + 2) >> 2;
+  int z1 = (t12 + t13) * 4433;
+  d[2 * stride] = (z1 + t13 * 6270 + half) >> sh;
+  d[6 * stride] = (z1 - t12 * 15137 + half) >> sh;
+  z1 = t4 + t7;
+  int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+  const int z5 = (z3 + z4) * 9633;
+  const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+  z1 *= -7373; z2 *= -20995;
+  z3 = z3 * -16069 + z5;
+  z4 = z4 * -3196 + z5;
+  d[7 * stride] = (a4 + z1 + z3 + half) >> sh;
+  d[5 * stride] = (a5 + z2 + z4 + half) >> sh;
+  d[3 * stride] = (a6 + z2 + z3 + half) >> sh;
+  d[stride] = (a7 + z1 + z4 + half) >> sh;
+}
+
+// Block j of MCU `mcu` -> zz[64], zig-zag order.  quant u16 [2, 64] natural order.  A luma block outside the component's real blocks is a
+// dummy: AC 0, DC that of the real block libjpeg's chain of copies ends at — (by, 0) in a real block row, else block (0, 1) when that
+// column is real, else block (0, 0).
+JPEG_HD void jpeg_enc_block(const JpegEncImage& im, const unsigned char* img, const unsigned short* quant, long mcu, int j, short* zz) {
+  const int my = (int)(mcu / im.mcux), mx = (int)(mcu - (long)my * im.mcux);
+  const int comp = j < im.lum ? 0 : j - im.lum + 1;
+  int bx = mx, by = my;
+  bool dummy = false;
+  if (comp == 0) {
+    const int rows = (im.h + 7) >> 3, cols = (im.w + 7) >> 3;
+    by = my * im.hs + j / im.hs; bx = mx * im.hs + j % im.hs;
+    if (by >= rows) { dummy = true; by = my * im.hs; bx = mx * im.hs + 1 < cols ? mx * im.hs + 1 : mx * im.hs; }
+    else if (bx >= cols) { dummy = true; bx = mx * im.hs; }
+  }
+  int d[64];
+#pragma unroll
+  for (int r = 0; r < 8; ++r)
+#pragma unroll
+    for (int c = 0; c < 8; ++c) d[8 * r + c] = jpeg_enc_sample(im, img, comp, 8 * bx + c, 8 * by + r) - 128;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) jpeg_fdct8(d + 8 * r, 1, true);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) jpeg_fdct8(d + c, 8, false);
+  const unsigned short* q = quant + (comp ? 64 : 0);
+#pragma unroll
+  for (int k = 0; k < 64; ++k) {
+    const int n = jpeg_zigzag(k), q8 = 8 * (int)q[n], v = d[n], a = ((v < 0 ? -v : v) + (q8 >> 1)) / q8;
+    zz[k] = (short)(dummy && k ? 0 : v < 0 ? -a : a);
+  }
+}
+
+// Annex K.3 as (codes per length 1 .. 16, values); table t: 0 luma DC, 1 luma AC, 2 chroma DC, 3 chroma AC -> out[symbol] = code << 8 | length
+JPEG_HD void jpeg_enc_tables(int t, unsigned* out) {
+  const unsigned char counts[4][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125},
+                                       {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
+  const unsigned char ac[2][162] = {
+      {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+       0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+       0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+       0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+       0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+       0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+       0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+       0xfa},
+      {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+       0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+       0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+       0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+       0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+       0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+       0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+       0xfa}};
+  for (int i = 0; i < JPEG_ENC_TABLE_WORDS; ++i) out[i] = 0u;
+  unsigned code = 0;
+  int k = 0;
+  for (int len = 1; len <= 16; ++len) {
+    for (int i = 0; i < counts[t][len - 1]; ++i, ++k, ++code) out[(t & 1) ? ac[t >> 1][k] : k] = code << 8 | (unsigned)len;     // a DC table's values are 0 .. 11 in order
+    code <<= 1;
+  }
+}
+
+JPEG_HD int jpeg_enc_size(int v) {
+  const unsigned a = (unsigned)(v < 0 ? -v : v);
+  return a ? 32 - __builtin_clz(a) : 0;
+}
+
+// the block, inside its restart interval, whose DC predicts block i's (blocks in scan order, bpm a MCU, the first `lum` luma): -1 at the first
+JPEG_HD int jpeg_enc_dc_from(int i, int bpm, int lum) {
+  const int j = i % bpm;
+  if (j < lum) return j ? i - 1 : i >= bpm ? i - bpm + lum - 1 : -1;
+  return i >= bpm ? i - bpm : -1;
+}
+
+// The bits zig-zag position k of a block adds to the scan -> *val (the first bit highest), their count returned (at most 3 x 11 + 16 + 10 =
+// 59).  tables: the four of jpeg_enc_tables; k = 0: v is the DC DIFFERENCE; k >= 1: v is the coefficient and nz the mask of the block's
+// nonzero AC positions (bit k for position k), from which the run in front of it follows; position 63 carries the EOB when it is zero.
+JPEG_HD int jpeg_enc_token(const unsigned* tables, bool chroma, int k, int v, unsigned long long nz, unsigned long long* val) {
+  const unsigned* dc = tables + (chroma ? 2 : 0) * JPEG_ENC_TABLE_WORDS;
+  const unsigned* ac = dc + JPEG_ENC_TABLE_WORDS;
+  *val = 0;
+  int s = jpeg_enc_size(v);
+  const int most = k ? 10 : 11;
+  s = s > most ? most : s;                                     // (a coefficient of this encoder never exceeds it)
+  const unsigned long long extra = (unsigned long long)(unsigned)(v < 0 ? v + (1 << s) - 1 : v) & ((1ull << s) - 1ull);
+  if (k == 0) {
+    const unsigned e = dc[s];
+    *val = (unsigned long long)(e >> 8) << s | extra;
+    return (int)(e & 255u) + s;
+  }
+  if (v == 0) {
+    if (k != 63) return 0;
+    *val = ac[0] >> 8;
+    return (int)(ac[0] & 255u);
+  }
+  const unsigned long long below = nz & ((1ull << k) - 1ull);
+  const int run = k - 1 - (below ? 63 - __builtin_clzll(below) : 0);
+  const unsigned e = ac[((run & 15) << 4) | s], z = ac[0xF0];
+  unsigned long long out = 0;
+  int n = 0;
+  for (int i = 0; i < 3; ++i)
+    if (i < (run >> 4)) { out = out << (z & 255u) | (z >> 8); n += (int)(z & 255u); }
+  *val = out << ((e & 255u) + s) | (unsigned long long)(e >> 8) << s | extra;
+  return n + (int)(e & 255u) + s;
+}
+
+// OR the n <= 64 bits of val (the first highest) into words from bit `at`: bit 31 of words[0] is bit 0 of the stream.  The device
+// kernels' words live in LDS and lanes share them, hence the atomic there.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define JPEG_ENC_OR(p, v) atomicOr((p), (v))
+#else
+#define JPEG_ENC_OR(p, v) (*(p) |= (v))
+#endif
+JPEG_HD void jpeg_enc_put(unsigned* words, unsigned at, unsigned long long val, int n) {
+  if (n <= 0) return;
+  const unsigned long long top = val << (64 - n);
+  const int s = (int)(at & 31u);
+  unsigned* w = words + (at >> 5);
+  const unsigned long long head = top >> s;
+  const unsigned a = (unsigned)(head >> 32), b = (unsigned)head, c = s ? (unsigned)((top << (64 - s)) >> 32) : 0u;
+  if (a) JPEG_ENC_OR(w, a);
+  if (b) JPEG_ENC_OR(w + 1, b);
+  if (c) JPEG_ENC_OR(w + 2, c);
+}
+JPEG_HD unsigned jpeg_enc_byte(const unsigned* words, int i) { return (words[i >> 2] >> (24 - 8 * (i & 3))) & 255u; }

@@ -167,3 +167,75 @@ extern "C" int zh_jpeg_decode_split_host(const unsigned char* scan, long scan_by
   free(coef); free(samples); free(counters); free(st_in); free(st_out); free(hand); free(cnt); free(first);
   return ZH_OK;
 }
+
+// Host twin of the device JPEG encoder (jpeg_enc.hip): the functions of jpeg_codec.h in the order of zh_jpeg_encode's three launches, a
+// lane's work as a loop iteration; the scratch has the workspace's sizes.  tools/host/jpeg_enc_host_check.cpp runs it under the sanitizers.
+extern "C" int zh_jpeg_encode_host(const unsigned char* images, long image_bytes, const long long* img_off, const int* hw, int B, int subsampling,
+                                   long max_mcus, const unsigned short* quant, const long long* out_off, unsigned char* out, long out_bytes,
+                                   long slot_bytes, int* lengths) {
+  ZH_CHECK_ARG(B >= 0 && B <= 65535, "zh_jpeg_encode_host: B = %d outside 0 .. 65535", B);
+  ZH_CHECK_ARG(subsampling == 0 || subsampling == 2, "zh_jpeg_encode_host: subsampling = %d is not 0 (4:4:4) or 2 (4:2:0)", subsampling);
+  ZH_CHECK_ARG(image_bytes >= 0 && out_bytes >= 0 && slot_bytes >= 0 && max_mcus >= 0, "zh_jpeg_encode_host: negative count");
+  if (B == 0) return ZH_OK;
+  ZH_CHECK_ARG(max_mcus >= 1 && max_mcus <= (1L << 26), "zh_jpeg_encode_host: max_mcus = %ld outside 1 .. 2^26", max_mcus);
+  ZH_CHECK_ARG(images && img_off && hw && quant && out_off && out && lengths, "zh_jpeg_encode_host: null pointer");
+  for (int i = 0; i < 128; ++i) ZH_CHECK_ARG(quant[i] >= 1 && quant[i] <= 255, "zh_jpeg_encode_host: quant[%d] = %d outside 1 .. 255", i, (int)quant[i]);
+  const int bpm = subsampling == 2 ? 6 : 3, iv_blocks = ZH_JPEG_ENC_INTERVAL_MCUS * bpm, iv_bytes = iv_blocks * ZH_JPEG_ENC_BLOCK_BYTES;
+  short* coef = (short*)malloc((size_t)max_mcus * bpm * 64 * sizeof(short));
+  unsigned* words = (unsigned*)malloc((size_t)iv_bytes);
+  unsigned char* slot = (unsigned char*)malloc((size_t)iv_bytes * 2);
+  if (!coef || !words || !slot) {
+    free(coef); free(words); free(slot);
+    zh_set_error("zh_jpeg_encode_host: out of memory for %ld MCUs", max_mcus);
+    return ZH_ERR_WORKSPACE;
+  }
+  unsigned tables[4 * JPEG_ENC_TABLE_WORDS];
+  for (int t = 0; t < 4; ++t) jpeg_enc_tables(t, tables + t * JPEG_ENC_TABLE_WORDS);
+  for (int b = 0; b < B; ++b) {
+    const JpegEncImage im = jpeg_enc_image(img_off, hw, out_off, b, subsampling, image_bytes, out_bytes, slot_bytes, max_mcus);
+    if (!im.ok) { lengths[b] = -1; continue; }
+    // A: coefficients
+    for (long i = 0; i < im.mcus * im.bpm; ++i) jpeg_enc_block(im, images + im.off, quant, i / im.bpm, (int)(i % im.bpm), coef + i * 64);
+    // B + C: every interval's bits, padded and stuffed, then into the slot behind the intervals in front of it
+    long at = 0;
+    unsigned char* dst = out + im.out;
+    for (int iv = 0; iv < im.nint; ++iv) {
+      const long mcu0 = (long)iv * ZH_JPEG_ENC_INTERVAL_MCUS, left = im.mcus - mcu0;
+      const int nb = (int)(left < ZH_JPEG_ENC_INTERVAL_MCUS ? left : ZH_JPEG_ENC_INTERVAL_MCUS) * im.bpm;
+      const short* c = coef + mcu0 * im.bpm * 64;
+      memset(words, 0, (size_t)iv_bytes);
+      unsigned bit = 0;
+      for (int i = 0; i < nb; ++i) {
+        const short* blk = c + i * 64;
+        const int from = jpeg_enc_dc_from(i, im.bpm, im.lum);
+        unsigned long long nz = 0;
+        for (int k = 1; k < 64; ++k) nz |= (unsigned long long)(blk[k] != 0) << k;
+        for (int k = 0; k < 64; ++k) {
+          unsigned long long val;
+          const int n = jpeg_enc_token(tables, i % im.bpm >= im.lum, k, k ? blk[k] : blk[0] - (from < 0 ? 0 : c[from * 64]), nz, &val);
+          jpeg_enc_put(words, bit, val, n);
+          bit += (unsigned)n;
+        }
+      }
+      if (bit & 7u) { const int pad = 8 - (int)(bit & 7u); jpeg_enc_put(words, bit, (1ull << pad) - 1ull, pad); }
+      const int nbytes = (int)((bit + 7u) >> 3);
+      int len = 0;
+      for (int i = 0; i < nbytes; ++i) {
+        const unsigned v = jpeg_enc_byte(words, i);
+        slot[len++] = (unsigned char)v;
+        if (v == 0xFFu) slot[len++] = 0;
+      }
+      for (int i = 0; i < len; ++i)
+        if (at + i < slot_bytes) dst[at + i] = slot[i];
+      at += len;
+      if (iv + 1 < im.nint) {
+        if (at < slot_bytes) dst[at] = 0xFF;
+        if (at + 1 < slot_bytes) dst[at + 1] = (unsigned char)(0xD0 + (iv & 7));
+        at += 2;
+      }
+    }
+    lengths[b] = (int)at;
+  }
+  free(coef); free(words); free(slot);
+  return ZH_OK;
+}

@@ -18,7 +18,8 @@ pack() lays the descriptor arrays of one launch out (scan bytes, segment rows so
 across the batch, output offsets); table_set_bytes() is the ONE form of the canonical Huffman tables that decode_np, the host entry and
 the kernel read.  chunk_rows() cuts the segments of a launch into the chunk rows of zh_jpeg_decode_split (decoder "device-split": a
 scan without restart markers split among lanes; include/zutis_hip.h has the method), chunk_rows_np() is their definition byte by byte.
-No torch at import.
+The second half of the module defines the ENCODER the same way: encode_np(), the baseline JPEG file zh_jpeg_encode's scans are framed
+into, byte for byte Pillow's (its rules stand in front of it).  No torch at import.
 """
 from __future__ import annotations
 
@@ -646,3 +647,374 @@ def check_decoder(name: str, decoder) -> str:
     if decoder not in DECODERS:
         raise ValueError(f"{name}: decoder {decoder!r} is not \"host\", \"device\" or \"device-split\"")
     return decoder
+
+
+# ---- the encoder: the baseline JPEG zh_jpeg_encode (csrc/jpeg_enc.hip over csrc/jpeg_codec.h) and zh_jpeg_encode_host write, defined in
+# NumPy.  encode_np(a, q, s, r) is byte for byte what Pillow (libjpeg-turbo) writes for Image.fromarray(a).save(f, "JPEG", quality=q,
+# subsampling=0 | 2, restart_marker_blocks=r); restated from the public algorithms like the decoder above.
+#   quantisation    the Annex K tables scaled by libjpeg's rule (quant_tables)
+#   colour          RGB -> YCbCr in 16-bit fixed point, F(x) = int(x * 65536 + 0.5); the chroma rounding constant is 32767, not 32768
+#   edges           luma (and 4:4:4 chroma) edge-replicated to the MCU grid; 4:2:0 chroma: the full-resolution plane replicated to even
+#                   rows and 16-multiple columns, downsampled, and the last DOWNSAMPLED row replicated down to the 8-multiple
+#   h2v2            (a + b + c + d + bias) >> 2, bias 1 on even output columns and 2 on odd ones
+#   forward DCT     samples - 128, "islow": 13-bit constants, rows first (scaled up by 2 bits), then columns: 8 x the coefficient
+#   quantise        sign(c) * ((|c| + (8 q >> 1)) // (8 q))
+#   dummy blocks    a luma block of an MCU outside the component's ceil(H / 8) x ceil(W / 8) real blocks is not transformed: AC = 0, DC =
+#                   that of the block before it in its block row of the MCU (right edge) or of the last block of the MCU's previous block
+#                   row (a dummy row)
+#   entropy         DC category + extra bits (prediction 0 at every restart), AC run / size with ZRL only in front of a nonzero
+#                   coefficient, EOB unless coefficient 63 is nonzero; codes from the most significant bit; the last byte of an interval
+#                   padded with 1-bits; FF stuffed as FF 00; RSTn (n mod 8) behind every interval but the last
+#   header          SOI, APP0 (JFIF 1.01, units 0, density 1 x 1), DQT x 2, SOF0, DHT x 4, DRI (always), SOS
+ENC_INTERVAL_MCUS, ENC_BLOCK_BYTES, ENC_SLOT_EXTRA = _K["ZH_JPEG_ENC_INTERVAL_MCUS"], _K["ZH_JPEG_ENC_BLOCK_BYTES"], _K["ZH_JPEG_ENC_SLOT_EXTRA"]
+ENCODERS = ("host", "device")
+SUBSAMPLINGS = {"4:4:4": 0, "4:2:0": 2}                # name -> Pillow's (and zh_jpeg_encode's) code
+OVERLAY_FORMATS = ("png", "jpeg")
+
+_ANNEX_K_QUANT = np.array([
+    [16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99],
+    [17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66] + [99] * 38])
+# Annex K.3: (codes of each length 1 .. 16, values) of luma DC, luma AC, chroma DC, chroma AC
+ANNEX_K_HUFF = (
+    ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), bytes(range(12))),
+    ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125), bytes.fromhex(
+        "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a434445464748494a"
+        "535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7"
+        "c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")),
+    ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), bytes(range(12))),
+    ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119), bytes.fromhex(
+        "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a43444546474849"
+        "4a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5"
+        "c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")),
+)
+
+
+def check_encode_args(name: str, quality, subsampling, interval_mcus=ENC_INTERVAL_MCUS) -> int:
+    """Pillow's code of `subsampling` after the checks every encoder entry shares: ValueError naming the argument."""
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+        raise ValueError(f"{name}: jpeg_quality {quality!r} is not an integer in 1 .. 100")
+    if subsampling not in SUBSAMPLINGS:
+        raise ValueError(f"{name}: jpeg_subsampling {subsampling!r} is not one of {sorted(SUBSAMPLINGS)}")
+    if isinstance(interval_mcus, bool) or not isinstance(interval_mcus, (int, np.integer)) or not 1 <= interval_mcus <= 65535:
+        raise ValueError(f"{name}: interval_mcus {interval_mcus!r} is not an integer in 1 .. 65535")
+    return SUBSAMPLINGS[subsampling]
+
+
+def check_encoder(name: str, jpeg_encoder) -> str:
+    if jpeg_encoder not in ENCODERS:
+        raise ValueError(f"{name}: jpeg_encoder {jpeg_encoder!r} is not \"host\" or \"device\"")
+    return jpeg_encoder
+
+
+def check_overlay_format(name: str, overlay_format) -> str:
+    if overlay_format not in OVERLAY_FORMATS:
+        raise ValueError(f"{name}: overlay_format {overlay_format!r} is not \"png\" or \"jpeg\"")
+    return overlay_format
+
+
+def quant_tables(quality: int) -> np.ndarray:
+    """int [2, 64] (luma, chroma) in natural order: Annex K scaled by s = 5000 // q below 50, 200 - 2 q from there; (t s + 50) // 100 in 1 .. 255."""
+    check_encode_args("jpeg_device.quant_tables", quality, "4:4:4")
+    s = 5000 // int(quality) if quality < 50 else 200 - 2 * int(quality)
+    return np.clip((_ANNEX_K_QUANT * s + 50) // 100, 1, 255)
+
+
+@functools.lru_cache(maxsize=None)
+def _encode_tables():
+    """(code, length) int64 [256] by symbol of the four Annex K tables: the canonical codes of T.81 Annex C."""
+    out = []
+    for counts, values in ANNEX_K_HUFF:
+        code, length, c, k = np.zeros(256, np.int64), np.zeros(256, np.int64), 0, 0
+        for n, count in enumerate(counts, 1):
+            for _ in range(count):
+                code[values[k]], length[values[k]] = c, n
+                c, k = c + 1, k + 1
+            c <<= 1
+        out.append((code, length))
+    return tuple(out)
+
+
+def _geometry(H: int, W: int, sub: int):
+    hs = 2 if sub == 2 else 1
+    return hs, -(-W // (8 * hs)), -(-H // (8 * hs))              # luma blocks per MCU side, MCUs per row, MCU rows
+
+
+def header_bytes(H: int, W: int, quality: int = 90, subsampling: str = "4:2:0", interval_mcus: int = ENC_INTERVAL_MCUS) -> bytes:
+    """Everything in front of the scan: SOI, APP0, DQT (luma), DQT (chroma), SOF0, DHT x 4, DRI, SOS."""
+    sub = check_encode_args("jpeg_device.header_bytes", quality, subsampling, interval_mcus)
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError(f"jpeg_device.header_bytes: a JPEG of {H} x {W} pixels")
+    seg = lambda marker, body: bytes([0xFF, marker]) + (len(body) + 2).to_bytes(2, "big") + body  # noqa: E731
+    q = quant_tables(quality)
+    out = [b"\xff\xd8", seg(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
+    out += [seg(0xDB, bytes([i]) + bytes(int(v) for v in q[i][ZIGZAG])) for i in range(2)]
+    out.append(seg(0xC0, bytes([8]) + int(H).to_bytes(2, "big") + int(W).to_bytes(2, "big") + bytes([3, 1, 0x22 if sub == 2 else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1])))
+    out += [seg(0xC4, bytes([cls]) + bytes(counts) + values) for cls, (counts, values) in zip((0x00, 0x10, 0x01, 0x11), ANNEX_K_HUFF)]
+    out.append(seg(0xDD, int(interval_mcus).to_bytes(2, "big")))
+    out.append(seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0])))
+    return b"".join(out)
+
+
+def _fdct_pass(d, first: bool):
+    """One pass of the islow forward DCT over the last axis of int64 [..., 8]."""
+    t0, t7, t1, t6 = d[..., 0] + d[..., 7], d[..., 0] - d[..., 7], d[..., 1] + d[..., 6], d[..., 1] - d[..., 6]
+    t2, t5, t3, t4 = d[..., 2] + d[..., 5], d[..., 2] - d[..., 5], d[..., 3] + d[..., 4], d[..., 3] - d[..., 4]
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    shift = 11 if first else 15
+    desc = lambda x, n: (x + (1 << (n - 1))) >> n  # noqa: E731
+    out = np.empty_like(d)
+    out[..., 0] = (t10 + t11) << 2 if first else desc(t10 + t11, 2)
+    out[..., 4] = (t10 - t11) << 2 if first else desc(t10 - t11, 2)
+    z1 = (t12 + t13) * 4433
+    out[..., 2] = desc(z1 + t13 * 6270, shift)
+    out[..., 6] = desc(z1 - t12 * 15137, shift)
+    z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+    z5 = (z3 + z4) * 9633
+    t4, t5, t6, t7 = t4 * 2446, t5 * 16819, t6 * 25172, t7 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    out[..., 7], out[..., 5], out[..., 3], out[..., 1] = desc(t4 + z1 + z3, shift), desc(t5 + z2 + z4, shift), desc(t6 + z2 + z3, shift), desc(t7 + z1 + z4, shift)
+    return out
+
+
+def _plane_blocks(plane: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """The quantised coefficients int64 [rows / 8, cols / 8, 64] in zig-zag order of a sample plane whose sides are multiples of 8."""
+    R, Cc = plane.shape[0] // 8, plane.shape[1] // 8
+    d = plane.astype(np.int64).reshape(R, 8, Cc, 8).transpose(0, 2, 1, 3) - 128
+    c = _fdct_pass(_fdct_pass(d, True).swapaxes(-1, -2), False).swapaxes(-1, -2).reshape(R, Cc, 64)
+    q8 = 8 * q.astype(np.int64)
+    return (np.sign(c) * ((np.abs(c) + (q8 >> 1)) // q8))[..., ZIGZAG]
+
+
+def encode_coefficients(image_u8: np.ndarray, quality: int = 90, subsampling: str = "4:2:0") -> np.ndarray:
+    """The quantised coefficients of the image's JPEG: int16 [MCUs * blocks per MCU, 64], blocks in scan order, each in zig-zag order."""
+    sub = check_encode_args("jpeg_device.encode_coefficients", quality, subsampling)
+    a = np.asarray(image_u8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or not (1 <= a.shape[0] <= 65535 and 1 <= a.shape[1] <= 65535):
+        raise ValueError(f"jpeg_device: a u8 image [H, W, 3] with 1 <= H, W <= 65535 expected, got {a.dtype} {a.shape}")
+    H, W = a.shape[:2]
+    hs, mcux, mcuy = _geometry(H, W, sub)
+    q = quant_tables(quality)
+    r, g, b = (a[..., i].astype(np.int64) for i in range(3))
+    y = (_fix(0.299) * r + _fix(0.587) * g + _fix(0.114) * b + 32768) >> 16
+    cb = (-_fix(0.16874) * r - _fix(0.33126) * g + _fix(0.5) * b + (128 << 16) + 32767) >> 16
+    cr = (_fix(0.5) * r - _fix(0.41869) * g - _fix(0.08131) * b + (128 << 16) + 32767) >> 16
+    edge = lambda p, rows, cols: np.pad(p, ((0, rows - p.shape[0]), (0, cols - p.shape[1])), mode="edge")  # noqa: E731
+    yb = _plane_blocks(edge(y, mcuy * 8 * hs, mcux * 8 * hs), q[0]).reshape(mcuy, hs, mcux, hs, 64).transpose(0, 2, 1, 3, 4).copy()
+    rows, cols = -(-H // 8), -(-W // 8)
+    for by in range(hs):                                           # the dummy blocks, in the order libjpeg fills an MCU
+        for bx in range(hs):
+            dummy = ((np.arange(mcuy) * hs + by >= rows)[:, None] | (np.arange(mcux) * hs + bx >= cols)[None, :])
+            if by == 0 and bx == 0:
+                continue
+            row_real = (np.arange(mcuy) * hs + by < rows)[:, None] & np.ones((1, mcux), bool)
+            src = np.where(row_real, yb[:, :, by, bx - 1, 0], yb[:, :, by - 1, hs - 1, 0])
+            yb[:, :, by, bx, 1:] = np.where(dummy[..., None], 0, yb[:, :, by, bx, 1:])
+            yb[:, :, by, bx, 0] = np.where(dummy, src, yb[:, :, by, bx, 0])
+    chroma = []
+    for p in (cb, cr):
+        if sub == 2:
+            f = edge(p, H + (H & 1), mcux * 16)
+            bias = np.where(np.arange(mcux * 8) % 2 == 0, 1, 2)
+            p = (f[0::2, 0::2] + f[0::2, 1::2] + f[1::2, 0::2] + f[1::2, 1::2] + bias) >> 2
+        chroma.append(_plane_blocks(edge(p, mcuy * 8, mcux * 8), q[1]))
+    out = np.concatenate([yb.reshape(mcuy, mcux, hs * hs, 64), chroma[0][:, :, None], chroma[1][:, :, None]], 2)
+    return out.reshape(-1, 64).astype(np.int16)
+
+
+def scan_of_blocks(blocks: np.ndarray, subsampling: str = "4:2:0", interval_mcus: int = ENC_INTERVAL_MCUS) -> bytes:
+    """The entropy-coded bytes of int16 [n, 64] zig-zag blocks in scan order (n a multiple of the blocks per MCU: 3 or 6): what
+    scan_np makes of encode_coefficients(); category and bound edges are tested through here.  DC in -2047 .. 2047 apart from its
+    predecessor's, AC in -1023 .. 1023."""
+    sub = check_encode_args("jpeg_device.scan_of_blocks", 90, subsampling, interval_mcus)
+    c = np.asarray(blocks).astype(np.int64).reshape(-1, 64)
+    bpm = 6 if sub == 2 else 3
+    n = c.shape[0]
+    if n == 0 or n % bpm:
+        raise ValueError(f"jpeg_device.scan_of_blocks: {n} blocks are not whole MCUs of {bpm}")
+    idx = np.arange(n)
+    interval, j = (idx // bpm) // int(interval_mcus), idx % bpm
+    comp = np.where(j < bpm - 2, 0, j - (bpm - 3))
+    diff = c[:, 0].copy()
+    for k in range(3):                                             # the DC differences per component, 0 predicted at every restart
+        sel = np.flatnonzero(comp == k)
+        prev = np.concatenate([[0], c[sel[:-1], 0]])
+        prev[np.concatenate([[True], interval[sel[1:]] != interval[sel[:-1]]])] = 0
+        diff[sel] = c[sel, 0] - prev
+    size = lambda v: np.where(v == 0, 0, np.floor(np.log2(np.maximum(np.abs(v), 1))).astype(np.int64) + 1)  # noqa: E731
+    extra = lambda v, s: np.where(v < 0, v + (1 << s) - 1, v)  # noqa: E731
+    if np.abs(diff).max() > 2047 or np.abs(c[:, 1:]).max(initial=0) > 1023:
+        raise ValueError("jpeg_device.scan_of_blocks: a coefficient outside the baseline categories")
+    tables = _encode_tables()
+    chroma = comp != 0
+    # tokens [n, 65, 4]: slot 0 the DC symbol, slot k the AC coefficient k (up to three ZRLs in front of its symbol), slot 64 the EOB
+    val, bits = np.zeros((n, 65, 4), np.int64), np.zeros((n, 65, 4), np.int64)
+    s = size(diff)
+    code, length = (np.where(chroma, tables[2][i][s], tables[0][i][s]) for i in range(2))
+    val[:, 0, 3], bits[:, 0, 3] = (code << s) | extra(diff, s), length + s
+    ac = c[:, 1:]
+    nz = ac != 0
+    k = np.arange(1, 64)[None, :]
+    last = np.maximum.accumulate(np.where(nz, k, 0), axis=1)
+    run = k - np.concatenate([np.zeros((n, 1), np.int64), last[:, :-1]], 1) - 1
+    s = size(ac)
+    sym = np.where(nz, ((run & 15) << 4) | s, 0)
+    ch = chroma[:, None]
+    code, length = (np.where(ch, tables[3][i][sym], tables[1][i][sym]) for i in range(2))
+    val[:, 1:64, 3], bits[:, 1:64, 3] = np.where(nz, (code << s) | extra(ac, s), 0), np.where(nz, length + s, 0)
+    zrl_code, zrl_len = (np.where(ch, tables[3][i][0xF0], tables[1][i][0xF0]) for i in range(2))
+    for z in range(3):
+        need = nz & ((run >> 4) > z)
+        val[:, 1:64, 2 - z], bits[:, 1:64, 2 - z] = np.where(need, zrl_code, 0), np.where(need, zrl_len, 0)
+    eob = c[:, 63] == 0
+    val[:, 64, 3] = np.where(eob, np.where(chroma, tables[3][0][0], tables[1][0][0]), 0)
+    bits[:, 64, 3] = np.where(eob, np.where(chroma, tables[3][1][0], tables[1][1][0]), 0)
+    # every interval's bits from the most significant, its last byte filled with ones
+    per_block = bits.reshape(n, -1).sum(1)
+    n_int = int(interval[-1]) + 1
+    int_bits = np.bincount(interval, weights=per_block, minlength=n_int).astype(np.int64)
+    int_at = np.cumsum((int_bits + 7) // 8 * 8) - (int_bits + 7) // 8 * 8
+    val, bits = val.reshape(-1), bits.reshape(-1)
+    within = np.cumsum(bits) - bits
+    tok_int = np.repeat(interval, 65 * 4)
+    first = np.searchsorted(tok_int, np.arange(n_int))
+    off = within - within[first][tok_int] + int_at[tok_int]
+    stream = np.ones(int(int_at[-1] + (int_bits[-1] + 7) // 8 * 8), np.uint8)
+    for b in range(int(bits.max())):
+        sel = bits > b
+        stream[off[sel] + b] = (val[sel] >> (bits[sel] - 1 - b)) & 1
+    data = np.packbits(stream).tobytes()
+    out = []
+    for i in range(n_int):
+        lo = int(int_at[i]) // 8
+        out.append(data[lo:lo + int(int_bits[i] + 7) // 8].replace(b"\xff", b"\xff\x00"))
+        if i + 1 < n_int:
+            out.append(bytes([0xFF, 0xD0 + i % 8]))
+    return b"".join(out)
+
+
+def scan_np(image_u8: np.ndarray, quality: int = 90, subsampling: str = "4:2:0", interval_mcus: int = ENC_INTERVAL_MCUS) -> bytes:
+    """The entropy-coded bytes between the SOS header and EOI, RSTn markers included: what zh_jpeg_encode writes byte for byte (at
+    interval_mcus = ENC_INTERVAL_MCUS)."""
+    check_encode_args("jpeg_device.scan_np", quality, subsampling, interval_mcus)
+    return scan_of_blocks(encode_coefficients(image_u8, quality, subsampling), subsampling, interval_mcus)
+
+
+def encode_np(image_u8: np.ndarray, quality: int = 90, subsampling: str = "4:2:0", interval_mcus: int = ENC_INTERVAL_MCUS) -> bytes:
+    """The complete file: header_bytes, scan_np, FF D9 — byte for byte Pillow's for the same settings (see above)."""
+    a = np.asarray(image_u8)
+    scan = scan_np(a, quality, subsampling, interval_mcus)
+    return header_bytes(a.shape[0], a.shape[1], quality, subsampling, interval_mcus) + scan + b"\xff\xd9"
+
+
+def scan_slot(H: int, W: int) -> int:
+    """The bytes a picture's scan has in the stage's copy back: the raw picture's and ENC_SLOT_EXTRA.  A scan that does not fit (the JPEG
+    would be larger than the pixels: noise at quality 100) is encoded on the host from the raw picture instead."""
+    return int(H) * int(W) * 3 + ENC_SLOT_EXTRA
+
+
+def scan_bound(H: int, W: int, subsampling: str = "4:2:0", interval_mcus: int = ENC_INTERVAL_MCUS) -> int:
+    """The exact worst case of the scan's length.  A block costs at most 11 + 11 bits of DC (the longest DC code, chroma category 11,
+    and its extra bits) and 63 x (16 + 10) bits of AC (every coefficient nonzero: no ZRL and no EOB, which would stand for coefficients
+    at less than 26 bits each): 1660 bits, ENC_BLOCK_BYTES = 208 bytes rounded up.  An interval of m MCUs of bpm blocks is ceil(1660 m
+    bpm / 8) bytes before stuffing, every one of which may be FF and double; a 2-byte marker stands between two intervals.  Nothing
+    real comes close: a luma DC code has at most 9 bits (2 bits a luma block less), the chroma code of run 0 / size 10 has 12 bits, not
+    16 (its 16-bit codes all carry a run, which stands for coefficients at no bits at all: 63 x 4 = 252 bits a chroma block less), and
+    bytes that are all FF would be runs of 1-bits no sequence of codes spells.  scan_of_blocks() of blocks whose DC alternates between
+    -1024 and 1023 inside every component and whose AC are all +-1023 comes to 9 + 11 + 63 x 26 = 1658 bits a luma block and 11 + 11 +
+    63 x 22 = 1408 a chroma block, less at most 2 bits for the first DC of each component in an interval (1023 against a prediction of 0
+    is category 10): its bytes before stuffing are at least ceil((m (1658 lum + 2 x 1408) - 6) / 8) an interval of m MCUs, against the
+    bound's ceil(1660 m bpm / 8)."""
+    sub = check_encode_args("jpeg_device.scan_bound", 90, subsampling, interval_mcus)
+    hs, mcux, mcuy = _geometry(H, W, sub)
+    mcus, bpm = mcux * mcuy, hs * hs + 2
+    full, rest = divmod(mcus, int(interval_mcus))
+    worst = lambda m: 2 * ((1660 * m * bpm + 7) // 8)  # noqa: E731
+    return full * worst(int(interval_mcus)) + (worst(rest) if rest else 0) + 2 * (full + (1 if rest else 0) - 1)
+
+
+def pack_pictures(images: Sequence[np.ndarray], slot_bytes: Optional[int] = None):
+    """The arrays of one zh_jpeg_encode launch over u8 [h, w, 3] images of any sizes: (pixels u8 [sum 3 h w], img_off int64 [B], hw int32
+    [B, 2], out_off int64 [B], slot_bytes, max_mcus at 4:4:4 — no smaller at 4:2:0).  slot_bytes: None -> the largest scan_slot."""
+    arrays = [np.ascontiguousarray(a) for a in images]
+    for a in arrays:
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"jpeg_device: a u8 image [H, W, 3] expected, got {a.dtype} {a.shape}")
+    if slot_bytes is None:
+        slot_bytes = max((scan_slot(*a.shape[:2]) for a in arrays), default=0)
+    sizes = np.asarray([a.size for a in arrays], np.int64)
+    pixels = np.concatenate([a.reshape(-1) for a in arrays]) if arrays else np.zeros(0, np.uint8)
+    hw = np.asarray([a.shape[:2] for a in arrays], np.int32).reshape(-1, 2)
+    max_mcus = max((-(-a.shape[0] // 8) * -(-a.shape[1] // 8) for a in arrays), default=1)
+    return pixels, np.cumsum(sizes) - sizes, hw, np.arange(len(arrays), dtype=np.int64) * int(slot_bytes), int(slot_bytes), int(max_mcus)
+
+
+def scan_host(images: Sequence[np.ndarray], quality: int = 90, subsampling: str = "4:2:0", slot_bytes: Optional[int] = None, fill: int = 0xA5):
+    """zh_jpeg_encode_host over one launch of images: (out u8 [B, slot_bytes] — `fill` where nothing was written —, lengths int32 [B]).
+    The CPU twin of zh_jpeg_encode: same codec functions, same checks."""
+    import ctypes
+    sub = check_encode_args("jpeg_device.scan_host", quality, subsampling)
+    pixels, img_off, hw, out_off, slot, max_mcus = pack_pictures(images, slot_bytes)
+    B = len(hw)
+    out, lengths = np.full(B * slot, fill, np.uint8), np.zeros(B, np.int32)
+    quant = np.ascontiguousarray(quant_tables(quality), np.uint16)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    rc = _lib.load().zh_jpeg_encode_host(ptr(pixels), pixels.size, ptr(img_off), ptr(hw), B, sub, max_mcus, ptr(quant), ptr(out_off), ptr(out), out.size,
+                                         slot, ptr(lengths))
+    _lib.check(rc, "zh_jpeg_encode_host")
+    return out.reshape(B, slot), lengths
+
+
+def quant_tensor(quality: int, device):
+    """quant_tables(quality) as zh_jpeg_encode reads them: int16 [2, 64] on the device (values 1 .. 255)."""
+    import torch
+    return torch.from_numpy(quant_tables(quality).astype(np.int16)).to(device)
+
+
+def encode_device(images, quality: int = 90, subsampling: str = "4:2:0") -> List[bytes]:
+    """The JPEG files of a u8 [B, H, W, 3] tensor on the GPU, encoded there (ops.jpeg_encode): encode_np of every image, byte for byte.
+    One launch sequence and one copy back of scan_slot bytes a picture; a scan that does not fit its slot (larger than the pixels) is
+    encoded by encode_np from the pixels instead."""
+    import torch
+    from . import ops
+    sub = check_encode_args("jpeg_device.encode_device", quality, subsampling)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_cuda:
+        raise ValueError(f"jpeg_device.encode_device: a u8 [B, H, W, 3] tensor on the GPU expected, got {images.dtype} {tuple(images.shape)} on {images.device}")
+    B, H, W, _ = images.shape
+    if B == 0:
+        return []
+    images, slot, dev = images.contiguous(), scan_slot(H, W), images.device
+    hs, mcux, mcuy = _geometry(H, W, sub)
+    off = torch.arange(B, dtype=torch.int64, device=dev)
+    out, lengths = torch.empty(B * slot, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+    ops.jpeg_encode(images, off * (H * W * 3), torch.tensor([[H, W]] * B, dtype=torch.int32, device=dev), sub, quant_tensor(quality, dev), out, off * slot,
+                    slot, lengths, mcux * mcuy)
+    scans, n = out.cpu().numpy().reshape(B, slot), lengths.cpu().numpy()
+    if (n <= 0).any():
+        raise RuntimeError(f"jpeg_device.encode_device: zh_jpeg_encode refused an image of {H} x {W} pixels")
+    head = header_bytes(H, W, quality, subsampling)
+    return [head + scans[b, :n[b]].tobytes() + b"\xff\xd9" if n[b] <= slot else encode_np(images[b].cpu().numpy(), quality, subsampling) for b in range(B)]
+
+
+@functools.lru_cache(maxsize=None)
+def pillow_writes_restart_blocks() -> bool:
+    """Whether the installed Pillow knows save(..., restart_marker_blocks=): it then writes the DRI segment encode_np defines."""
+    import io
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.new("RGB", (8, 8)).save(buf, "JPEG", restart_marker_blocks=1)
+    return b"\xff\xdd\x00\x04\x00\x01" in buf.getvalue()
+
+
+def require_host_encoder(name: str):
+    """jpeg_encoder="host" is Pillow with restart_marker_blocks: a clear error, before any work, where the installed one lacks it."""
+    if not pillow_writes_restart_blocks():
+        raise RuntimeError(f"{name}: jpeg_encoder=\"host\" needs a Pillow whose JPEG writer takes restart_marker_blocks (the files carry a restart "
+                           f"marker every {ENC_INTERVAL_MCUS} MCUs); use jpeg_encoder=\"device\" or a newer Pillow")
+
+
+def write_scan(path: str, scan, H: int, W: int, quality: int, subsampling: str):
+    """What a writer thread does with a finished scan: the header in front, FF D9 behind, the file."""
+    data = header_bytes(H, W, quality, subsampling) + bytes(scan) + b"\xff\xd9"
+    with open(path, "wb") as f:
+        f.write(data)

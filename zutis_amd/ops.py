@@ -998,6 +998,35 @@ def png_deflate(images, img_off, hw, c, out, out_off, lengths, max_segments, wor
     return lengths
 
 
+def jpeg_encode(images, img_off, hw, subsampling, quant, out, out_off, slot_bytes, lengths, max_mcus, workspace=None):
+    """The entropy-coded scans of the baseline JPEGs of B RGB images in one call (zh_jpeg_encode; jpeg_device.scan_np byte for byte).
+    images u8 (any shape, contiguous): image b is [h, w, 3] at img_off[b] of its bytes; img_off int64 [B], hw int32 [B, 2] = (h, w);
+    subsampling 0 (4:4:4) or 2 (4:2:0); quant u16 / int16 [2, 64]: jpeg_device.quant_tables on the device; out u8: image b's scan at
+    out_off[b] (int64 [B]), at most slot_bytes of it; lengths int32 [B]: the TRUE lengths (above slot_bytes: the scan did not fit and the
+    caller encodes that image another way; -1: the image does not fit, see zutis_hip.h); max_mcus: the most MCUs of an image of the
+    batch (the caller holds the sizes on the host).  Everything on the device; nothing is copied.  Returns lengths."""
+    _chk(images, torch.uint8, "jpeg_encode images"); _chk(out, torch.uint8, "jpeg_encode out")
+    _chk(img_off, torch.int64, "jpeg_encode img_off"); _chk(out_off, torch.int64, "jpeg_encode out_off")
+    _chk(hw, torch.int32, "jpeg_encode hw"); _chk(lengths, torch.int32, "jpeg_encode lengths")
+    if quant.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)):
+        raise _lib.ZutisHipError(f"jpeg_encode quant: a 16-bit integer tensor expected, got {quant.dtype}")
+    _chk(quant, quant.dtype, "jpeg_encode quant")
+    if subsampling not in (0, 2):
+        raise _lib.ZutisHipError(f"jpeg_encode: subsampling {subsampling!r} is not 0 (4:4:4) or 2 (4:2:0)")
+    B = img_off.numel()
+    if hw.numel() != 2 * B or out_off.numel() != B or lengths.numel() != B or quant.numel() != 128:
+        raise _lib.ZutisHipError("jpeg_encode: img_off [B], hw [B, 2], out_off [B], lengths [B] and quant [2, 64] do not describe one batch")
+    if B > 65535:
+        raise _lib.ZutisHipError(f"jpeg_encode: {B} images in one call, at most 65535")
+    if B and (int(max_mcus) < 1 or int(slot_bytes) < 0):
+        raise _lib.ZutisHipError(f"jpeg_encode: max_mcus {max_mcus!r} / slot_bytes {slot_bytes!r} for {B} images")
+    if B:
+        ws, need = _workspace_or(workspace, "jpeg_encode", "zh_jpeg_encode_workspace_size", images.device, B, int(max_mcus), int(subsampling))
+        _call("zh_jpeg_encode", _p(images), images.numel(), _p(img_off), _p(hw), B, int(subsampling), int(max_mcus), _p(quant), _p(out_off), _p(out),
+              out.numel(), int(slot_bytes), _p(lengths), _p(ws), need, _stream())
+    return lengths
+
+
 def jpeg_decode(scan, segments, images, tables, n_blocks, max_image_blocks, max_image_pixels, out, status, workspace=None):
     """B baseline JPEG files to interleaved RGB in one call (zh_jpeg_decode; jpeg_device.decode_np byte for byte).  The arrays of
     jpeg_device.pack on the device: scan u8 [bytes], segments int32 [S, 4], images int32 [B, 12], tables u8 [n_sets, TABLE_SET_BYTES];

@@ -78,9 +78,11 @@ def normalise_palette(palette, n: int) -> np.ndarray:
     return np.ascontiguousarray(a.astype(np.uint8))
 
 
-def resolve_output_paths(p_images: Sequence[str], out_dir: Optional[str], out_paths: Optional[Sequence[str]], overlay: bool = False):
+def resolve_output_paths(p_images: Sequence[str], out_dir: Optional[str], out_paths: Optional[Sequence[str]], overlay: bool = False,
+                         overlay_ext: str = ".png"):
     """(label paths, overlay paths or None): out_paths[i] as given, or {out_dir}/{stem of the image}.png; the overlay goes to
-    {stem of the label map}_overlay.png beside it.  Exactly one of out_dir / out_paths; two outputs on one path: ValueError."""
+    {stem of the label map}_overlay.png (overlay_ext: ".jpg" for a JPEG overlay) beside it.  Exactly one of out_dir / out_paths; two
+    outputs on one path: ValueError."""
     if (out_dir is None) == (out_paths is None):
         raise ValueError("predict_from_files: give exactly one of out_dir and out_paths")
     if out_paths is not None:
@@ -89,7 +91,7 @@ def resolve_output_paths(p_images: Sequence[str], out_dir: Optional[str], out_pa
             raise ValueError("predict_from_files: one output path per image")
     else:
         labels = [os.path.join(os.fspath(out_dir), os.path.splitext(os.path.basename(os.fspath(p)))[0] + ".png") for p in p_images]
-    overlays = [os.path.splitext(p)[0] + "_overlay.png" for p in labels] if overlay else None
+    overlays = [os.path.splitext(p)[0] + "_overlay" + overlay_ext for p in labels] if overlay else None
     seen = {}
     for i, p in enumerate(labels + (overlays or [])):
         key = os.path.normpath(os.path.abspath(p))
@@ -101,12 +103,13 @@ def resolve_output_paths(p_images: Sequence[str], out_dir: Optional[str], out_pa
 
 
 def resolve_instance_paths(p_images: Sequence[str], label_paths: Sequence[str], written: Sequence[Optional[Sequence[str]]], instance_map: bool,
-                           instance_overlay: bool):
-    """(id-map paths or None, instance-overlay paths or None): {stem of the label map}_instances.png and {stem}_instances_overlay.png beside
+                           instance_overlay: bool, overlay_ext: str = ".png"):
+    """(id-map paths or None, instance-overlay paths or None): {stem of the label map}_instances.png and {stem}_instances_overlay.png (or
+    overlay_ext in its place) beside
     where image i's label map goes (or would go: label_paths, resolve_output_paths' first result).  They take part in the
     one-path-one-output check together with `written`, the lists of files the call writes besides them (None entries are skipped)."""
     maps = [os.path.splitext(p)[0] + "_instances.png" for p in label_paths] if instance_map else None
-    overlays = [os.path.splitext(p)[0] + "_instances_overlay.png" for p in label_paths] if instance_overlay else None
+    overlays = [os.path.splitext(p)[0] + "_instances_overlay" + overlay_ext for p in label_paths] if instance_overlay else None
     seen = {}
     for paths in list(written) + [maps, overlays]:
         for i, p in enumerate(paths or []):
@@ -200,7 +203,8 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
                        label_id_to_category: Optional[Dict[int, str]] = None, nms_type: Optional[str] = "hard",
                        predictions_json: Optional[str] = None, instance_map: bool = False, instance_overlay: bool = False,
                        instance_colours="instance", instance_min_score: float = 0.0, instance_outline: bool = True,
-                       png_encoder: str = "host", decoder: str = "host") -> dict:
+                       png_encoder: str = "host", decoder: str = "host", overlay_format: str = "png", jpeg_quality: int = 90,
+                       jpeg_subsampling: str = "4:2:0", jpeg_encoder: str = "host") -> dict:
     """The segmenter over a list of image files: label PNGs (and overlays) on disk, and / or the instance predictions.
 
     network: the drop-in ZUTIS (zutis_amd/dropin/networks/zutis.py) on a GPU; its text embeddings are the n categories.
@@ -242,6 +246,17 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     Pillow's), everything else — and any file whose scan the device reports as damaged — is decoded by Pillow as ever, so the files
     written do not depend on it.  "device-split": as "device", with every file's scan split among lanes (zh_jpeg_decode_split), which is
     what a file without restart markers needs to be decoded in parallel.  Any other value: ValueError before any work.
+    overlay_format "png": the two overlays are PNG files, as above.  "jpeg": {stem}_overlay.jpg and {stem}_instances_overlay.jpg take
+    their place — baseline JPEG at jpeg_quality (1 .. 100) and jpeg_subsampling ("4:2:0" | "4:4:4") with the Annex K Huffman tables and a
+    restart marker every 16 MCUs: the file zutis_amd/jpeg_device.encode_np defines, about a tenth of the PNG's bytes — under the same
+    result keys and the same one-path check; label maps and id maps stay PNG under png_encoder whatever these say.  jpeg_encoder "host":
+    the writer threads encode with Pillow (save(..., restart_marker_blocks=16); a Pillow without that option: RuntimeError before any
+    work).  "device": the overlays are encoded on the device (one zh_jpeg_encode per kind of overlay and batch, behind the
+    zh_png_deflate calls), their scans travel in the batch's one copy back at jpeg_device.scan_slot stride and a writer puts the header
+    and FF D9 around them; the files are the same bytes either way.  A scan that does not fit its slot — the JPEG would be larger than
+    the pixels: noise at quality 100 — is copied back raw and encoded by the host arm; the result then counts it in
+    "jpeg_host_fallbacks" (a key of the result with overlay_format="jpeg" only).  Any other value of the four: ValueError naming the
+    argument, before any work.
     Returns {"label_paths": [...] | None, "overlay_paths": [...] | None, "instance_predictions": the dicts predict gave (with "bbox"),
     in input-path order, "n_images": int}.
     A missing or unreadable image (FileNotFoundError / OSError / ValueError) and a directory or file that cannot be written (OSError)
@@ -249,6 +264,11 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     p_images = [os.fspath(p) for p in p_images]
     on_device = png_device.check_encoder("predict_from_files", png_encoder) == "device"
     jpeg_device.check_decoder("predict_from_files", decoder)
+    as_jpeg = jpeg_device.check_overlay_format("predict_from_files", overlay_format) == "jpeg"
+    jpeg_device.check_encode_args("predict_from_files", jpeg_quality, jpeg_subsampling)
+    if jpeg_device.check_encoder("predict_from_files", jpeg_encoder) == "host" and as_jpeg:
+        jpeg_device.require_host_encoder("predict_from_files")
+    overlay_ext, overlay_kind = (".jpg", (3, "JPEG", None)) if as_jpeg else (".png", (3, "RGB", None))
     _require_dropin(network, "predict_from_files")
     n = int(network.text_embeddings.shape[0])
     pal = _validate(n, len(p_images), semantic, instance, label_format, palette, overlay, alpha, image_ids, compress_level)
@@ -256,10 +276,10 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     paint = colour_mode is not None
     label_paths = overlay_paths = map_paths = iovl_paths = None
     if semantic or paint:
-        would_be, overlay_paths = resolve_output_paths(p_images, out_dir, out_paths, overlay)
+        would_be, overlay_paths = resolve_output_paths(p_images, out_dir, out_paths, overlay, overlay_ext)
         label_paths = would_be if semantic else None
         if paint:
-            map_paths, iovl_paths = resolve_instance_paths(p_images, would_be, [label_paths, overlay_paths], instance_map, instance_overlay)
+            map_paths, iovl_paths = resolve_instance_paths(p_images, would_be, [label_paths, overlay_paths], instance_map, instance_overlay, overlay_ext)
         for d in sorted({os.path.dirname(p) or "." for paths in (label_paths, map_paths, iovl_paths) for p in (paths or [])}):
             os.makedirs(d, exist_ok=True)
     elif out_dir is not None and out_paths is not None:
@@ -278,11 +298,12 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
         colour_dev = torch.from_numpy(colour_table).to(dev) if colour_table is not None else None
         loader = preprocess.PredictBatchLoader(p_images, max_size, batch_size, n_decode, window=window, decoder=decoder)
         # name -> (paths, (c, mode, palette bytes)) of the kinds of picture the call writes, in layout order; the id map's once Q is known
-        kinds = {name: kind for name, kind in (("labels", (label_paths, (ch, mode, pal_bytes))), ("overlay", (overlay_paths, (3, "RGB", None))),
-                                               ("ids", (map_paths, None)), ("instance_overlay", (iovl_paths, (3, "RGB", None)))) if kind[0] is not None}
+        kinds = {name: kind for name, kind in (("labels", (label_paths, (ch, mode, pal_bytes))), ("overlay", (overlay_paths, overlay_kind)),
+                                               ("ids", (map_paths, None)), ("instance_overlay", (iovl_paths, overlay_kind))) if kind[0] is not None}
         with preprocess.device_batches(loader, dev, preprocess.resize_normalize_of(lut)) as steps, \
                 picture_out.PictureStage(png_encoder, loader.pin, n_write, dev, compress_level=compress_level,
-                                         error="predict_from_files: the device encoder left no stream for {path} ({h} x {w} x {c})") as stage:
+                                         error="predict_from_files: the device encoder left no stream for {path} ({h} x {w} x {c})",
+                                         jpeg_encoder=jpeg_encoder if as_jpeg else "host", jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling) as stage:
             for k, (batch, (packed, desc), x) in enumerate(steps):
                 B, (H, W) = len(batch.paths), batch.size_hw
                 if (overlay or instance_overlay) and batch.n_host:
@@ -295,7 +316,7 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
                     if instance_map:
                         kinds["ids"] = (map_paths, (LABEL_CHANNELS[id_format], "L" if id_format == "u8" else "RGB", None))
                 if kinds:
-                    layout = picture_out.Layout([(H, W)] * B, [kind for _, kind in kinds.values()])
+                    layout = picture_out.Layout([(H, W)] * B, [kind for _, kind in kinds.values()], stage.jpeg_encoder)
                     view = dict(zip(kinds, layout.views(stage.take(k, layout, [paths[i] for paths, _ in kinds.values() for i in batch.indices]))))
                 if semantic:
                     eng.label_bytes(out["patch_tokens"], network.text_embeddings, (H, W), label_format=label_format, labels_out=view["labels"],
@@ -324,6 +345,7 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
                         per_image_ids[i].append(pid)
                     stage.commit()                                                         # labels + overlay + instance pictures: one D2H
         eng.check_finite()                                                                 # the forwards' status word: one read for the whole run
+        fallbacks = stage.jpeg_host_fallbacks
     predictions = [p for ps in per_image for p in ps]
     if predictions_json is not None:
         d = os.path.dirname(os.fspath(predictions_json))
@@ -334,6 +356,8 @@ def predict_from_files(network, p_images: Sequence[str], *, out_dir: Optional[st
     result = {"label_paths": label_paths, "overlay_paths": overlay_paths, "instance_predictions": predictions, "n_images": len(p_images)}
     if paint:
         result.update(instance_map_paths=map_paths, instance_overlay_paths=iovl_paths, instance_ids=[i for ids in per_image_ids for i in ids])
+    if as_jpeg:
+        result["jpeg_host_fallbacks"] = fallbacks if p_images else 0
     return result
 
 
