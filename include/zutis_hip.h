@@ -447,7 +447,10 @@ int zh_mask_runs_kept(const unsigned char* masks, const int* kept_index, const i
  * PACKED list and nruns table: mask b*Q + j (j < kept_count[b]) gets its string at out + 5 * off + 16 * rank, off = start of its list in
  * `positions` (sum of min(transitions, max_runs) over the kept masks in front of it), rank = number of kept masks in front of it;
  * out_len int32 [B*Q] = the string's length, -1 when the mask has more than max_runs transitions or its list / string does not fit the
- * capacities (the caller encodes that mask from its pixels).  HW = pixels per mask. */
+ * capacities (the caller encodes that mask from its pixels).  HW = pixels per mask.  A mask's string is never written outside
+ * [5 * off + 16 * rank, min(that + 5 * transitions + 16, out_capacity)): for HW < 2^24 a string of nc = transitions + 1 + (pixel 0 set)
+ * values is at most 5 * nc characters and `out` is checked for those; for 2^24 <= HW < 2^31, where a value can take 6 or 7 characters,
+ * the string is measured first and reported -1, with no character written, when it does not fit that window. */
 int zh_mask_rle_kept(const int* positions, long packed_capacity, const int* nruns, const int* kept_count, int B, int Q, int max_runs, long HW,
                      unsigned char* out, long out_capacity, int* out_len, zh_stream_t stream);
 

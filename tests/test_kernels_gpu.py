@@ -669,7 +669,8 @@ def test_paint_behind_the_fused_and_the_chain_path_agree(dev):
 def test_device_rle_strings_equal_the_host_encoder(dev):
     """zh_mask_rle_kept: the COCO RLE strings the device writes from the packed run list are byte for byte the host encoder's
     (= pycocotools.mask.encode, tests/test_rle.py pins that one): noisy masks (long strings, several 256-run chunks), blobs, an empty and
-    a full mask, pixel 0 set, a single pixel at the very end; a mask over max_runs and lists past the capacity report -1."""
+    a full mask, pixel 0 set, a single pixel at the very end; a mask over max_runs and lists past the capacity report -1.  That nothing is
+    written past a capacity, byte for byte inside guard bands: tests/test_rle_guard_gpu.py."""
     from zutis_amd import ops, rle
     rng = np.random.default_rng(11)
     B, Q, H, W = 2, 9, 61, 83
@@ -721,7 +722,8 @@ def test_device_rle_strings_equal_the_host_encoder(dev):
 def test_fused_run_box_string_kernel(dev, H, W):
     """zh_mask_rle_fused_kept (one workgroup per kept mask: bits in LDS, word-parallel transitions, string placed by an atomic cursor):
     strings byte for byte the host encoder's, boxes / areas = numpy's, for widths that are / are not multiples of 64 and pixel counts
-    that are / are not multiples of 16; a mask over max_runs and strings past the capacity report length -1 with box and area intact."""
+    that are / are not multiples of 16; a mask over max_runs and strings past the capacity report length -1 with box and area intact.  The
+    byte-level proof (guard bands, `out` at the exact sum of the strings, more items than threads): tests/test_rle_guard_gpu.py."""
     from zutis_amd import ops, rle
     assert ops.mask_rle_fused_supported(H, W, 8192) and not ops.mask_rle_fused_supported(64, 1025, 8192)
     rng = np.random.default_rng(H * 1000 + W)

@@ -244,7 +244,10 @@ __global__ __launch_bounds__(256) void mask_rle_kernel(RleArgs a) {
   const long off = s_a[0], cstart = 5L * s_a[0] + 16L * s_b[0];
   const int nt = a.nruns[2 * mi], lead = a.nruns[2 * mi + 1] != 0 ? 1 : 0;
   const int nc = nt + 1 + lead;
-  if (nt > a.max_runs || off + nt > a.packed_cap || cstart + 5L * nc > a.out_cap) {
+  // H*W < 2^24: a value takes at most 5 characters, so 5 nc bounds the string and the slot of 5 nt + 16 holds it (rle_codec.h, "the
+  // character bound").  Larger masks: the string is measured below, before a character is written.
+  const bool big = a.HW >= RLE_FIVE_CHAR_PIXELS;
+  if (nt > a.max_runs || off + nt > a.packed_cap || (!big && cstart + 5L * nc > a.out_cap)) {
     if (tid == 0) a.out_len[mi] = -1;
     return;
   }
@@ -256,6 +259,22 @@ __global__ __launch_bounds__(256) void mask_rle_kernel(RleArgs a) {
     for (int i = tid; i < nt; i += 256) s_p[i] = p[i];
     __syncthreads();
     p = s_p;
+  }
+  if (big) {
+    // values of 2^24 and more in magnitude take 6 or 7 characters: the string's true length against its window
+    // [cstart, min(cstart + 5 nt + 16, out_cap)) — the neighbour's slot starts behind it — decides, for the whole workgroup
+    __shared__ long s_len[4];
+    long len = 0;
+    for (int k = tid; k < nc; k += 256) len += rle_groups(rle_value(p, nt, lead != 0, a.HW, k));
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) len += __shfl_xor(len, d, 64);
+    if (lane == 0) s_len[wave] = len;
+    __syncthreads();
+    len = s_len[0] + s_len[1] + s_len[2] + s_len[3];
+    if (len > min(5L * nt + 16, a.out_cap - cstart)) {
+      if (tid == 0) a.out_len[mi] = -1;
+      return;
+    }
   }
   unsigned char* o = a.out + cstart;
   int base = 0;

@@ -15,11 +15,13 @@
 //     string is at most 5 nt + 10 characters.  This is the range in which zh_mask_rle_kept's budget — mask mi's string starts at
 //     5 * off(mi) + 16 * rank(mi), i.e. 5 nt + 16 characters to the next mask's slot, and `out` is checked for 5 nc — is GUARANTEED.
 //     zh_mask_rle_fused_kept (string buffer: 5 (max_runs + 2) bytes of LDS) is always inside it: the mask's bits must fit 150 KB of LDS.
-//   * H*W < 2^31 (all that zh_mask_rle_kept's argument check asks for): at most 7 characters per value.  The budget above then has
-//     16 - 5 (1 + lead) spare characters per mask and no more: a mask whose values of 2^24 and more in magnitude outnumber that (e.g.
-//     17 runs A, A, 1, 1, A, A, 1, 1, ... with A = 2^24 + 2, about 151 M pixels: 6 * 17 - 5 = 97 characters against 5 * 16 + 16 = 96)
-//     writes into its neighbour's slot, or past `out` when `out` holds no more than the 5 nc it is checked for.  Recorded as a finding
-//     in DESIGN.md (instance post-processing) and profiles/NOTES.md; the check and the budget are unchanged here.
+//   * 2^24 <= H*W < 2^31 (RLE_FIVE_CHAR_PIXELS and up; all that zh_mask_rle_kept's argument check asks for): at most 7 characters
+//     per value.  The budget above then has 16 - 5 (1 + lead) spare characters per mask and no more: a mask whose values of 2^24 and
+//     more in magnitude outnumber that (e.g. 17 runs A, A, 1, 1, A, A, 1, 1, ... with A = 2^24 + 2, about 151 M pixels: 6 * 17 - 5 =
+//     97 characters against 5 * 16 + 16 = 96) does not fit its slot.  In this range zh_mask_rle_kept therefore MEASURES the string
+//     first (the sum of rle_groups over the mask's values) and writes it only when it fits [cstart, min(cstart + 5 nt + 16,
+//     out_capacity)); otherwise it reports -1 and writes no character (the host encodes that mask).  Below 2^24 the kernel takes no
+//     such pass: the 5 nc check is exact enough there.  tests/test_rle_guard_gpu.py runs the 17-run list between two neighbours.
 //   * the host buffers of rle.py (_host_capacity) allow 8 characters per value: enough for every |x| < 2^34; the host entry points
 //     check `cap` for every value all the same and return -1.
 #pragma once
@@ -29,6 +31,9 @@
 #else
 #define RLE_HD inline
 #endif
+
+// masks of fewer pixels than this have no value of more than 5 characters (the character bound above)
+#define RLE_FIVE_CHAR_PIXELS (1L << 24)
 
 // number of 5-bit groups (= characters) of a value
 RLE_HD int rle_groups(long x) {
