@@ -16,7 +16,8 @@
  *     argument (0 = write the plain fp16 tensor only; the hi plane alone IS that tensor); zh_gemm_f16x3 and the split-pair
  *     form of zh_attention_f16 consume them.
  *   - Re-entrant.  Process-wide state: none on the product path; the developer entry zh_dev_set_gemm_overrides() (forced GEMM tile /
- *     super-tile height, used by tests and tools only) is process-wide by design, and zh_last_error() text is thread-local.
+ *     super-tile height, used by tests and tools only) is process-wide by design, and zh_last_error() text is thread-local, as is the
+ *     number of launches in flight that a plan replay loop sets while it runs (zh_dev_set_gemm_inflight).
  */
 #ifndef ZUTIS_HIP_H
 #define ZUTIS_HIP_H
@@ -44,7 +45,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 245 /* 245: zh_jpeg_encode / zh_jpeg_encode_host (the device JPEG encoder: overlays leave the GPU as the scan of a baseline JPEG, ZH_JPEG_ENC_*); 244: zh_jpeg_decode_split / zh_jpeg_decode_split_host (a scan without restart markers split among lanes, ZH_JPEG_CHUNK_*, ZH_JPEG_SPLIT_*, ZH_JPEG_STATUS_UNSYNCED); 243: zh_jpeg_decode / zh_jpeg_decode_host (the device JPEG decoder: baseline files reach the GPU as file bytes, ZH_JPEG_*); 242: the attention entries take head_dim 128 (a behaviour change: a stale build would refuse the ViT-L decoder); 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 246 /* 246: zh_dev_set_gemm_inflight / zh_dev_gemm_plan_inflight; the replay loops zh_plan_run_multi / zh_plan_run2 tell the GEMM tile chooser how many launches meet on the chip (a behaviour change: other tiles in flight, the same bits); 245: zh_jpeg_encode / zh_jpeg_encode_host (the device JPEG encoder: overlays leave the GPU as the scan of a baseline JPEG, ZH_JPEG_ENC_*); 244: zh_jpeg_decode_split / zh_jpeg_decode_split_host (a scan without restart markers split among lanes, ZH_JPEG_CHUNK_*, ZH_JPEG_SPLIT_*, ZH_JPEG_STATUS_UNSYNCED); 243: zh_jpeg_decode / zh_jpeg_decode_host (the device JPEG decoder: baseline files reach the GPU as file bytes, ZH_JPEG_*); 242: the attention entries take head_dim 128 (a behaviour change: a stale build would refuse the ViT-L decoder); 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -58,7 +59,8 @@ const char* zh_last_error(void);
 int zh_dev_set_gemm_overrides(int group_m, int tile, int tile_small);
 
 /* DEVELOPER entry: what the GEMM dispatcher (csrc/gemm_dispatch.h) decides for a call, without launching; it is the function the three
- * GEMM entries below ask, under the overrides in force (zh_dev_set_gemm_overrides).  Nothing is dereferenced: it runs without a GPU.
+ * GEMM entries below ask, under the overrides in force (zh_dev_set_gemm_overrides) and for the launches in flight that the calling
+ * thread's next launch would see (1 unless forced, zh_dev_set_gemm_inflight).  Nothing is dereferenced: it runs without a GPU.
  * mode: 0 = zh_gemm_f16, 1 = zh_gemm_f16_res16, 2 = zh_gemm_f16x3, 3 = zh_gemm_f16x3 with planeW = 0; out_kind: 0 f32, 1 f16, 2 split pair
  * (modes 0 / 1: out_f16); C / bias / residual: the pointer VALUES of the call (alignment only, NULL = absent); has_pos: pos tables given.
  * plan (HOST int[6]) = {family (0 LDS ring, 1 few-row kernel), tile code as launched (0 = the base tile of the scalar / direct paths,
@@ -76,6 +78,17 @@ int zh_dev_gemm_plan(int mode, int M, int N, int K, int batch, long lda, long ld
  * many (tests use 8 to make small problems walk several tiles per workgroup).  Process-wide: the library's one mutable word that
  * steers product launches, written only here. */
 int zh_dev_set_gemm_persist(int workgroups);
+
+/* DEVELOPER entries: the number of copies of a GEMM launch that meet on the chip, which the tile chooser counts against the chip's
+ * rounds (csrc/gemm_dispatch.h).  On the product path it is 1, and the stream count inside the replay loops zh_plan_run_multi (count)
+ * and zh_plan_run2 (2): set for the duration of the loop on the calling thread, restored when it returns.  The bits of a result do not
+ * depend on it.  zh_dev_set_gemm_inflight forces one value for every GEMM launch of the process (tests / tools: eager calls at a
+ * forced value); 0 = not forced.  zh_dev_gemm_plan_inflight is zh_dev_gemm_plan for a given number (1 .. 64) instead of the one the
+ * calling thread's next launch would see. */
+int zh_dev_set_gemm_inflight(int inflight);
+int zh_dev_gemm_plan_inflight(int mode, int M, int N, int K, int batch, long lda, long ldw, long ldc, long strideC, long planeC,
+                              long ldr, long strideR, int res_rows, int out_kind, int act, int flags,
+                              const void* C, const void* bias, const void* residual, int has_pos, int inflight, int* plan);
 
 /* C[b][m][n] = act(sum_k A[b][m][k]*W[b][n][k] + bias[n] + pos[m][n]) + residual[b][m % res_rows][n]
  * A [M,K] f16 (lda), W [N,K] f16 (ldw) — torch Linear layout; C f32 or f16 (out_f16); bias/residual f32 or NULL.

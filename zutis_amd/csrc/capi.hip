@@ -39,17 +39,39 @@ extern "C" int zh_dev_set_gemm_overrides(int group_m, int tile, int tile_small) 
   return ZH_OK;
 }
 
+// ---- launches in flight (gemm_dispatch.h): how many copies of a GEMM launch meet on the chip.  The replay loops of plan.hip set the
+//      calling thread's number for the duration of their loop (GemmInflightScope); everywhere else it is 1.  The developer setter
+//      forces one value for every launch of the process (tests and tools: eager calls at a forced value), 0 = not forced.
+static thread_local int t_gemm_inflight = 1;
+static int g_gemm_inflight_forced = 0;
+int gemm_inflight() { return g_gemm_inflight_forced ? g_gemm_inflight_forced : t_gemm_inflight; }
+GemmInflightScope::GemmInflightScope(int n) : prev(t_gemm_inflight) { t_gemm_inflight = n < 1 ? 1 : (n > ZH_GEMM_INFLIGHT_MAX ? ZH_GEMM_INFLIGHT_MAX : n); }
+GemmInflightScope::~GemmInflightScope() { t_gemm_inflight = prev; }
+extern "C" int zh_dev_set_gemm_inflight(int inflight) {
+  ZH_CHECK_ARG(inflight >= 0 && inflight <= ZH_GEMM_INFLIGHT_MAX, "zh_dev_set_gemm_inflight: %d is not 0 (not forced) or 1 .. %d", inflight, ZH_GEMM_INFLIGHT_MAX);
+  g_gemm_inflight_forced = inflight;
+  return ZH_OK;
+}
+
 // What the dispatcher decides for a GEMM, asked without launching: the plan functions the three entries call, under the process's
-// current overrides.  Pointer VALUES only (alignment); runs without a GPU.
+// current overrides.  Pointer VALUES only (alignment); runs without a GPU.  zh_dev_gemm_plan: for the number of launches in flight the
+// calling thread's next launch would see (gemm_inflight()); zh_dev_gemm_plan_inflight: for a given number.
 extern "C" int zh_dev_gemm_plan(int mode, int M, int N, int K, int batch, long lda, long ldw, long ldc, long strideC, long planeC,
                                 long ldr, long strideR, int res_rows, int out_kind, int act, int flags,
                                 const void* C, const void* bias, const void* residual, int has_pos, int* plan) {
+  return zh_dev_gemm_plan_inflight(mode, M, N, K, batch, lda, ldw, ldc, strideC, planeC, ldr, strideR, res_rows, out_kind, act, flags, C, bias, residual,
+                                   has_pos, gemm_inflight(), plan);
+}
+extern "C" int zh_dev_gemm_plan_inflight(int mode, int M, int N, int K, int batch, long lda, long ldw, long ldc, long strideC, long planeC,
+                                         long ldr, long strideR, int res_rows, int out_kind, int act, int flags,
+                                         const void* C, const void* bias, const void* residual, int has_pos, int inflight, int* plan) {
   ZH_CHECK_ARG(plan && mode >= GEMM_F16 && mode <= GEMM_X2, "zh_dev_gemm_plan: null plan or mode %d not in {0 f16, 1 res16, 2 x3, 3 x2}", mode);
   ZH_CHECK_ARG(M > 0 && N > 0 && K > 0 && batch > 0, "zh_dev_gemm_plan: bad shape M=%d N=%d K=%d batch=%d", M, N, K, batch);
+  ZH_CHECK_ARG(inflight >= 1 && inflight <= ZH_GEMM_INFLIGHT_MAX, "zh_dev_gemm_plan_inflight: inflight %d not in 1 .. %d", inflight, ZH_GEMM_INFLIGHT_MAX);
   const GemmProblem q = {mode, M, N, K, batch, lda, ldw, ldc, strideC, planeC, ldr, strideR, res_rows, out_kind, act, flags,
                          (uintptr_t)C, (uintptr_t)bias, (uintptr_t)residual, has_pos != 0, mode == GEMM_RES16};
   GemmPlan g;
-  const int rc = mode <= GEMM_RES16 ? gemm_plan_f16(q, gemm_dev_overrides(), &g) : gemm_plan_x3(q, gemm_dev_overrides(), &g);
+  const int rc = mode <= GEMM_RES16 ? gemm_plan_f16(q, gemm_dev_overrides(), &g, inflight) : gemm_plan_x3(q, gemm_dev_overrides(), &g, inflight);
   if (rc != ZH_OK) return rc;
   const GemmTile* t = gemm_plan_tile(mode, g.code);
   ZH_CHECK_ARG(t || g.family == GEMM_SKINNY, "zh_dev_gemm_plan: the plan's tile code %d has no table row", g.code);

@@ -32,7 +32,7 @@ static int gemm_f16_impl(const void* A, long lda, long strideA, const void* W, l
                         bias, residual, ldr, strideR, res_rows, pos_y, pos_x, ld_pos, pos_h, pos_w, pos_f16, act, M, N, K, batch, 0, &p, &q);
   if (rc != ZH_OK) return rc;
   ZH_CHECK_ARG(!res_f16 || (out_f16 && act == ZH_ACT_NONE), "zh_gemm_f16_res16: an fp16 residual goes with an fp16 output and no activation");
-  if ((rc = gemm_plan_f16(q, gemm_dev_overrides(), &plan)) != ZH_OK) return rc;
+  if ((rc = gemm_plan_f16(q, gemm_dev_overrides(), &plan, gemm_inflight())) != ZH_OK) return rc;
   if (plan.peel_rows)
     return gemm_tail_peel(plan.peel_rows, M, A, lda, C, ldc, out_f16 ? 2 : 4, residual, ldr, res_f16 ? 2 : 4, res_rows,
                           [&](const void* a, void* c, const void* r, int rows, int m) {

@@ -63,7 +63,7 @@ extern "C" int zh_gemm_f16x3(const void* A, long lda, long strideA, long planeA,
   // the decoder's query_pos terms) that is BEFORE the one rounding, and only without an activation
   ZH_CHECK_ARG(!residual || out_kind == 0 || act == ZH_ACT_NONE, "zh_gemm_f16x3: a residual of an fp16 / split output goes with no activation");
   ZH_CHECK_ARG(out_scale > 0.0f, "zh_gemm_f16x3: out_scale must be positive");
-  if ((rc = gemm_plan_x3(q, gemm_dev_overrides(), &plan)) != ZH_OK) return rc;
+  if ((rc = gemm_plan_x3(q, gemm_dev_overrides(), &plan, gemm_inflight())) != ZH_OK) return rc;
   if (plan.peel_rows)
     return gemm_tail_peel(plan.peel_rows, M, A, lda, C, ldc, out_kind == 0 ? 4 : 2, residual, ldr, 4, res_rows,
                           [&](const void* a, void* c, const void* r, int rows, int m) {
