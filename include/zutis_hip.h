@@ -45,7 +45,7 @@ typedef struct ihipStream_t* zh_stream_t; /* == hipStream_t */
 /* ABI version: bumped whenever an entry point's signature changes.  zh_version() returns the value the library was BUILT
  * with; a binding compiled / written against this header must refuse a library that reports another one (zutis_amd/_lib.py
  * does) — ctypes cannot see a changed argument list. */
-#define ZH_ABI_VERSION 246 /* 246: zh_dev_set_gemm_inflight / zh_dev_gemm_plan_inflight; the replay loops zh_plan_run_multi / zh_plan_run2 tell the GEMM tile chooser how many launches meet on the chip (a behaviour change: other tiles in flight, the same bits); 245: zh_jpeg_encode / zh_jpeg_encode_host (the device JPEG encoder: overlays leave the GPU as the scan of a baseline JPEG, ZH_JPEG_ENC_*); 244: zh_jpeg_decode_split / zh_jpeg_decode_split_host (a scan without restart markers split among lanes, ZH_JPEG_CHUNK_*, ZH_JPEG_SPLIT_*, ZH_JPEG_STATUS_UNSYNCED); 243: zh_jpeg_decode / zh_jpeg_decode_host (the device JPEG decoder: baseline files reach the GPU as file bytes, ZH_JPEG_*); 242: the attention entries take head_dim 128 (a behaviour change: a stale build would refuse the ViT-L decoder); 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
+#define ZH_ABI_VERSION 247 /* 247: zh_second_largest_component / zh_components_workspace_size (the mask post-processing of bilateral_solver_output on the device: fill holes, label, second largest, ZH_CCL_TILE_*); 246: zh_dev_set_gemm_inflight / zh_dev_gemm_plan_inflight; the replay loops zh_plan_run_multi / zh_plan_run2 tell the GEMM tile chooser how many launches meet on the chip (a behaviour change: other tiles in flight, the same bits); 245: zh_jpeg_encode / zh_jpeg_encode_host (the device JPEG encoder: overlays leave the GPU as the scan of a baseline JPEG, ZH_JPEG_ENC_*); 244: zh_jpeg_decode_split / zh_jpeg_decode_split_host (a scan without restart markers split among lanes, ZH_JPEG_CHUNK_*, ZH_JPEG_SPLIT_*, ZH_JPEG_STATUS_UNSYNCED); 243: zh_jpeg_decode / zh_jpeg_decode_host (the device JPEG decoder: baseline files reach the GPU as file bytes, ZH_JPEG_*); 242: the attention entries take head_dim 128 (a behaviour change: a stale build would refuse the ViT-L decoder); 241: zh_dev_attention_plan (what the attention launcher decides, asked without launching), ZH_ATTN_QUERY_BLOCK / ZH_ATTN_KEY_TILE_*; 240: zh_topk_rows orders every NaN first and -0.0 equal to +0.0 (a behaviour change: a stale build would select other columns); 239: zh_png_deflate (the device PNG encoder: pictures leave the GPU as the zlib stream of their PNG, ZH_PNG_SEGMENT_BYTES); 238: zh_dev_gemm_plan (what the GEMM dispatcher decides, asked without launching); 237: zh_runs_label_maps (semantic ground truth painted from the annotations' run lengths, ZH_OVERLAP_*, ZH_LABEL_TILE_*); 236: zh_polygon_runs (polygon annotations to run lengths on the device, ZH_POLYGON_LDS_CROSSINGS); 235: zh_instance_paint (instance predictions as pictures: id map and colour overlay of the kept masks); 234: COCO mask AP on the device (zh_rle_prefix, zh_rle_pair_iou, zh_coco_match, ZH_RLE_IOU_LDS_RUNS); 233: zh_upsample_argmax_bytes (predictions as file bytes: the label PNG's bytes and a colour overlay from the arg-max launch); 232: the criterion's assignment and mask packing on the device (zh_linear_assignment, zh_pack_masks_u8); 231: zh_upsample_argmax_score (evaluation: the confusion matrix fused into the arg-max launch, ZH_GT_*); 230: the training sample on the device (zh_synth_geometry_u8, zh_synth_photometric_u8, zh_synth_blur_u8, zh_synth_compose); 229: zh_resize_normalize_u8 (MaskDataset's resize + normalise of a ragged u8 batch, ZH_FILTER_*); 228: zh_resize_crop_normalize_u8 (CLIP pre-processing of a ragged u8 batch); 227: the fp16 residual stream (zh_gemm_f16_res16, zh_layernorm_f16, zh_assemble_tokens_ln_f16); 226: the training criterion (zh_mask_match_cost, zh_mask_match_grad, zh_upsample_ce_fwd / _bwd, zh_gemm_f32_strided), ZH_STATUS_LABEL; 225: zh_dev_set_gemm_persist; 224: zero_word of zh_mask_nms; 223: zh_mask_rle_fused_kept; 222: zh_mask_rle_kept; 221: packed_capacity of zh_mask_runs_kept (the kept masks' transitions as one list), packed form of zh_rle_from_transitions_host; 220: flags argument of zh_gemm_f16x3 (ZH_GEMM_FIXED_K_ORDER); 219: workspace of zh_mask_runs / zh_mask_runs_kept (two-launch run extraction); 218: status word of the LayerNorm family, f16_scale of the unit-norm producers; 217: zh_mask_runs_kept, range_flag / packed arguments of zh_instance_mask_stats / zh_mask_nms; 216: zh_sum_layernorm_f32, few-row kernel behind zh_gemm_f16x3; 215: zh_rle_from_transitions_host; 214: zh_gemm_f16x3 accepts planeW = 0 (fp16-valued weight: two products); 213: workspace argument of zh_masked_mean_tokens; 212: zh_attention_f16_splitk; 211: zh_dev_set_gemm_overrides; 210: pos_y / pos_x tables on zh_gemm_f16 / zh_gemm_f16x3 */
 int zh_version(void);
 const char* zh_arch(void);
 const char* zh_last_error(void);
@@ -415,6 +415,26 @@ int zh_bilateral_solve_batch(const unsigned char* rgb, const unsigned char* targ
 
 /* output_solver > 0.5 on the device (networks/selfmask/selfmask.py:231): x f64 [n] -> out u8 {0,1} [n]. */
 int zh_threshold_f64_u8(const double* x, double threshold, unsigned char* out, long n, zh_stream_t stream);
+
+/* The post-processing of bilateral_solver_output, utils/bilateral_solver.py:185-193, for B images of one size in ONE fixed sequence of
+ * launches (blockIdx.y = image; nothing is read back, so the entry is stream-ordered and capturable): binary_fill_holes(soft > 0.5),
+ * ndimage.label (4-connected), a count per label with the background as label 0, and the label that is SECOND largest under the key
+ * (count, label) = np.argsort(counts, kind="stable")[-2]; all ones when there is no object.  The reference's plain np.argsort is not
+ * stable: where the largest or the second-largest count is not unique its answer is implementation-defined, and this rule is the one
+ * kept (zutis_amd/components.py).  Everywhere else the outputs are scipy's, bit for bit.
+ * Exactly one of soft (f64 [B,H,W]; foreground = soft > threshold, a NaN is background) and binary (u8 [B,H,W]; foreground = non-zero)
+ * is non-NULL.  mask_out u8 {0,1} [B,H,W]; filled_out u8 {0,1} [B,H,W] (the filled foreground) and labels_out int32 [B,H,W] (scipy's
+ * numbering: 1 .. nr in raster order of each component's first pixel, 0 = background) may be NULL; stats int32 [B,4] = {nr_objects,
+ * chosen label, chosen count, 1 if the all-ones fallback was taken (then label -1, count H*W)}.  workspace: B *
+ * zh_components_workspace_size(H, W) bytes, 4-byte aligned (ZH_ERR_WORKSPACE when short; nothing is written then); up to (H*W + 1) / 2
+ * components, H = 1 and W = 1 included, H*W <= 2^31 - 1.  Tiles of ZH_CCL_TILE_H x ZH_CCL_TILE_W pixels are labelled in LDS and merged
+ * across their borders in global memory (csrc/components.hip). */
+#define ZH_CCL_TILE_H 32
+#define ZH_CCL_TILE_W 32
+size_t zh_components_workspace_size(int H, int W); /* per image */
+int zh_second_largest_component(const double* soft, const unsigned char* binary, double threshold, int B, int H, int W,
+                                unsigned char* mask_out, unsigned char* filled_out, int* labels_out, int* stats, void* workspace,
+                                size_t workspace_bytes, zh_stream_t stream);
 
 /* Retrieval (datasets/index_dataset.py:163-167): per row of scores [rows, N] (row stride ld) the k largest entries, score
  * descending, ties by ascending index — replaces torch.argsort(descending=True)[:n_images] per category.  NaNs of either

@@ -37,7 +37,7 @@ MIN_OCCUPANCY = {"attention.hip": {"attn_f16_kernelILi64ELi4ELi1ELi0EE": 3, "att
                               "sum_layernorm_kernelILi0EE": 8, "sum_layernorm_kernelILi1EE": 8, "sum_layernorm_kernelILi2EE": 6,
                               "sum_layernorm_kernelILi4EE": 4, "assemble_ln_kernelIfE": 8, "assemble_ln_kernelIDF16_E": 8,
                               "l2norm_rows_kernel": 8, "gln_partial_kernel": 8, "gln_apply_kernel": 8}}
-SOURCES = ["capi.hip", "rle_host.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "mask_rle.hip", "instance_paint.hip", "bilateral.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "assign.hip", "cocoeval.hip", "polygon.hip", "label_paint.hip", "png.hip", "jpeg_host.hip", "jpeg.hip", "jpeg_enc.hip", "synth.hip", "plan.hip"]
+SOURCES = ["capi.hip", "rle_host.hip", "gemm.hip", "gemm_x3.hip", "attention.hip", "norm.hip", "resample.hip", "metrics.hip", "instance.hip", "mask_rle.hip", "instance_paint.hip", "bilateral.hip", "components.hip", "preprocess.hip", "retrieval.hip", "text.hip", "criterion.hip", "assign.hip", "cocoeval.hip", "polygon.hip", "label_paint.hip", "png.hip", "jpeg_host.hip", "jpeg.hip", "jpeg_enc.hip", "synth.hip", "plan.hip"]
 
 
 def _hipcc() -> str:

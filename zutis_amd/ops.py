@@ -846,6 +846,48 @@ def threshold_f64_u8(x, threshold=0.5, out=None):
     return out
 
 
+def components_workspace_size(H, W) -> int:
+    """Bytes of workspace ONE H x W image needs in second_largest_component (a batch needs B times that)."""
+    return int(_lib.load(raw=True).zh_components_workspace_size(int(H), int(W)))
+
+
+def second_largest_component(x, threshold=0.5, *, filled=None, labels=None, stats=None, workspace=None, out=None):
+    """utils/bilateral_solver.py:185-193 on the device (zutis_amd/components.py is the definition): x f64 (foreground = x > threshold,
+    NaN is background) or u8 (non-zero), [H,W] or [B,H,W] -> u8 {0,1} mask of the same shape: holes filled, 4-connected components,
+    the second largest under the key (count, label), all ones without an object.  One sequence of launches for all B images.
+    Caller buffers, as in bilateral_solve (each contiguous, of the dtype and element count of what it fills, returned viewed at its
+    shape): `out` u8 (the mask), `stats` int32 [B,4] = {nr_objects, chosen label, chosen count, fallback}, `workspace` (any dtype,
+    >= B * components_workspace_size(H, W) bytes) and the optional outputs `filled` u8 (the filled foreground) and `labels` int32
+    (scipy's numbering) — pass True to have one allocated.  Returns the mask, or (mask, stats[, filled][, labels]) when any of
+    stats / filled / labels was asked for."""
+    batched = x.dim() == 3
+    x3 = x if batched else x[None]
+    if x3.dim() != 3 or x3.dtype not in (torch.float64, torch.uint8) or not x3.is_contiguous():
+        raise _lib.ZutisHipError(f"second_largest_component: expected contiguous f64 or u8 [H,W] / [B,H,W], got {x.dtype} {tuple(x.shape)}")
+    B, H, W = x3.shape
+    dev = x3.device
+    need = B * components_workspace_size(H, W)
+    ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=dev)
+    if not ws.is_contiguous() or _nbytes(ws) < need:
+        raise _lib.ZutisHipError(f"second_largest_component: workspace holds {_nbytes(ws)} bytes (contiguous={ws.is_contiguous()}), {need} needed")
+    mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if out is None else _caller_buffer(out, torch.uint8, (B, H, W), "second_largest_component out")
+    want_stats = stats is not None
+    st = torch.empty((B, 4), dtype=torch.int32, device=dev) if stats is None or stats is True else _caller_buffer(stats, torch.int32, (B, 4), "second_largest_component stats")
+    fl = lb = None
+    if filled is not None:
+        fl = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if filled is True else _caller_buffer(filled, torch.uint8, (B, H, W), "second_largest_component filled")
+    if labels is not None:
+        lb = torch.empty((B, H, W), dtype=torch.int32, device=dev) if labels is True else _caller_buffer(labels, torch.int32, (B, H, W), "second_largest_component labels")
+    soft = x3 if x3.dtype == torch.float64 else None
+    binary = x3 if x3.dtype == torch.uint8 else None
+    _call("zh_second_largest_component", _p(soft), _p(binary), float(threshold), B, H, W, _p(mask), _p(fl), _p(lb), _p(st), _p(ws), _nbytes(ws), _stream())
+    if not batched:
+        mask, st, fl, lb = mask[0], st[0], (None if fl is None else fl[0]), (None if lb is None else lb[0])
+    if not (want_stats or fl is not None or lb is not None):
+        return mask
+    return (mask, st) + ((fl,) if fl is not None else ()) + ((lb,) if lb is not None else ())
+
+
 def select_upsample_mask(obj, masks, out_u8, index, B, Q, h, w, H, W, scale_h, scale_w, threshold=0.5):
     _chk(obj, f32, "objectness"); _chk(masks, f32, "masks"); _chk(out_u8, torch.uint8, "mask out")
     _call("zh_select_upsample_mask", _p(obj), _p(masks), _p(out_u8), _p(index), B, Q, h, w, H, W, float(scale_h), float(scale_w),
